@@ -2,6 +2,7 @@
 """bench.py — throughput of the tiled DEM super-resolution hot path on MI355X.
 
     python bench.py --gpus N --steps K --warmup W [--workload spade512|spade256] [--precision bf16x3|fp32]
+                    [--dump-outputs DIR] [--full]
 
 A "step" is one generator(call) — `self.model(np.array(batch), training=False)` of process_full_tiles.py:338 —
 over one batch of synthetic (ortho, low-res DEM) patches that is already resident in HBM:
@@ -16,9 +17,14 @@ that fill the chip (2 / 1.5 MFMA-equivalents per product: main convs / SPADE lay
 oracle on these very shapes (tests/test_gpu_baseline_configs.py), inside the 1e-3 bar of BASELINE.json; "bf16x3" = 3-term
 split-bf16 everywhere (1.7-2.0e-5); "fp32" = exact fp32 MFMA; "bf16x3_gbf16" opt-in; "fp8" declared non-parity.
 
-At N = 1 the one JSON line also carries, under "also", the driver-timed figures of the other modes and of the other
-single-GPU configuration (spade512 in fp32 / bf16x3 / bf16x3_gbf16 / fp8, spade256 in f16c / bf16x3 / fp32: value, ms_per_step,
-roofline each, same K and W), the B = 1 single-call latency ("p50_ms_per_call_b1"), and the CPU baseline.
+A plain run sets up, warms up, times the K steps and prints the headline line (value, ms_per_step, ...): nothing else runs.
+--full adds everything else: HIP-event brackets of the conv launches inside the timed region (roofline), the per-call latency
+and per-kernel passes after it, the non-finite output check, and at N = 1, under "also", the driver-timed figures of the other
+modes and of the other single-GPU configuration (spade512 in fp32 / bf16x3 / bf16x3_gbf16 / fp8, spade256 in f16c / bf16x3 /
+fp32: value, ms_per_step, roofline each, same K and W), the B = 1 single-call latency ("p50_ms_per_call_b1"), and the CPU
+baseline (--no-profile / --no-also / --no-cpu-baseline leave pieces of --full out).
+--dump-outputs DIR writes what the last timed step computed, the generator output [B,S,S,1] float32 of rank 0, to
+DIR/output.npy.  Weights, latent noise and input batches are seeded, so equal arguments give equal inputs.
 
 N > 1: `python bench.py --gpus N` launches its own N workers (fresh child processes of torch.distributed.run, before
 this process touches HIP); under an outer `python -m torch.distributed.run ... bench.py --gpus N` (WORLD_SIZE set) it
@@ -197,8 +203,9 @@ class Dist:
             self.dist.destroy_process_group()
 
 
-def run_workload(args, D: Dist, workload: str, precision: str, with_cpu: bool, with_b1: bool):
-    """Warm up, time exactly K steps between barriers, and return the result dict of one (workload, precision)."""
+def run_workload(args, D: Dist, workload: str, precision: str, with_cpu: bool, with_b1: bool, dump_dir=None):
+    """Warm up, time exactly K steps between barriers, and return the result dict of one (workload, precision).
+    Without --full only the timed steps run; dump_dir receives the last timed step's output (rank 0)."""
     import torch
     from moonsuperresolution_amd import Generator, make_latent_noise, make_weights, synthetic_patches
     wl = WORKLOADS[workload]
@@ -238,8 +245,9 @@ def run_workload(args, D: Dist, workload: str, precision: str, with_cpu: bool, w
         with torch.cuda.stream(streams[i % ns]):
             gens[i % ns].forward_device(pool[i % len(pool)], out=outs[i % ns])
     D.barrier()
+    profiled = args.full and not args.no_profile
     for g in gens:
-        g.profile(0 if args.no_profile else 2)    # dominant kernel family only, one event pair per run of launches
+        g.profile(2 if profiled else 0)           # dominant kernel family only, one event pair per run of launches
     ref = torch.cuda.Event(enable_timing=True)
     ref.record()
     t0 = time.perf_counter()
@@ -256,8 +264,36 @@ def run_workload(args, D: Dist, workload: str, precision: str, with_cpu: bool, w
         assert gathered[0].shape[0] == n_blocks * world * T
     D.barrier()
     elapsed = D.max(time.perf_counter() - t0)
+    if dump_dir is not None and rank == 0:
+        import numpy as np
+        os.makedirs(dump_dir, exist_ok=True)
+        np.save(os.path.join(dump_dir, "output.npy"), outs[(args.steps - 1) % ns].cpu().numpy().astype(np.float32))
+    tiles_per_step = B * (S / 512.0) ** 2
+    res = {
+        "metric": "512x512 DEM tiles/s (whole job)", "value": world * args.steps * tiles_per_step / elapsed,
+        "unit": "tiles/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
+        "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
+        "vs_baseline": None, "dtype": DTYPE[precision], "data": "synthetic",
+        "config": {"workload": wl["name"], "image_size": S, "batch_size": B, "variant": "gaugan",
+                   "weights": "random-init (Keras default distributions), seed 1234",
+                   "tiles_per_step_per_gpu": tiles_per_step, "parallelism": f"tile-sharded x{world}",
+                   "streams_per_gpu": ns},
+        "patches_per_s": world * args.steps * B / elapsed,
+        "forward_gflop_per_call": gen.forward_flops() / 1e9,
+        "achieved_tflops_whole_call": world * gen.forward_flops() * args.steps / elapsed / 1e12,
+        "device_mem_gib": ns * gen.device_bytes() / 2 ** 30,
+    }
+    if world > 1:
+        res["exchange"] = {"collective": f"all_gather_into_tensor x3 ({D.backend}) of the finished rows, inside the timed region",
+                           "bytes_per_rank": n_blocks * T * width * 9, "seconds_rank0": t_gather}
+    if not args.full:
+        for g in gens:
+            g.close()
+        del gens, gen, pool, outs
+        torch.cuda.empty_cache()
+        return res
     stats = {}
-    if not args.no_profile:
+    if profiled:
         for g in gens:
             for k, v in g.profile_read().items():
                 acc = stats.setdefault(k, dict(launches=0, device_ms=0.0, flops=0.0, bytes=0.0))
@@ -266,7 +302,7 @@ def run_workload(args, D: Dist, workload: str, precision: str, with_cpu: bool, w
     # With several streams the conv intervals of different handles overlap (a run that starts while the other stream's
     # kernel holds the CUs includes its wait), so the family's time is the UNION of the intervals, not their sum.
     conv_union_ms = 0.0
-    if not args.no_profile:
+    if profiled:
         runs = sorted(r[:2] for g in gens for r in g.profile_runs(ref))
         cur_a, cur_b = None, None
         for a, b in runs:
@@ -292,7 +328,7 @@ def run_workload(args, D: Dist, workload: str, precision: str, with_cpu: bool, w
     torch.cuda.synchronize()
     step_ms = [a.elapsed_time(b) for a, b in ev]
     all_stats, extra = {}, 3
-    if not args.no_profile:
+    if profiled:
         # every family, every launch bracketed: a separate short pass AFTER the timed region (it costs ~7 %)
         gen.profile(1)
         for i in range(extra):
@@ -300,27 +336,9 @@ def run_workload(args, D: Dist, workload: str, precision: str, with_cpu: bool, w
         all_stats = gen.profile_read()
         gen.profile(False)
 
-    tiles_per_step = B * (S / 512.0) ** 2
-    res = {
-        "metric": "512x512 DEM tiles/s (whole job)", "value": world * args.steps * tiles_per_step / elapsed,
-        "unit": "tiles/s", "n_gpus": world, "steps": args.steps, "warmup": args.warmup,
-        "ms_per_step": 1e3 * elapsed / args.steps, "higher_is_better": True, "scaling": "weak",
-        "vs_baseline": None, "dtype": DTYPE[precision], "data": "synthetic",
-        "config": {"workload": wl["name"], "image_size": S, "batch_size": B, "variant": "gaugan",
-                   "weights": "random-init (Keras default distributions), seed 1234",
-                   "tiles_per_step_per_gpu": tiles_per_step, "parallelism": f"tile-sharded x{world}",
-                   "streams_per_gpu": ns},
-        "patches_per_s": world * args.steps * B / elapsed,
-        "p50_latency_ms_per_tile": statistics.median(step_ms) / tiles_per_step,
-        "p50_ms_per_call": statistics.median(step_ms),
-        "latency_note": f"p50 of {lat_n} calls on one stream with nothing else in flight (after the timed region)",
-        "forward_gflop_per_call": gen.forward_flops() / 1e9,
-        "achieved_tflops_whole_call": world * gen.forward_flops() * args.steps / elapsed / 1e12,
-        "device_mem_gib": ns * gen.device_bytes() / 2 ** 30,
-    }
-    if world > 1:
-        res["exchange"] = {"collective": f"all_gather_into_tensor x3 ({D.backend}) of the finished rows, inside the timed region",
-                           "bytes_per_rank": n_blocks * T * width * 9, "seconds_rank0": t_gather}
+    res["p50_latency_ms_per_tile"] = statistics.median(step_ms) / tiles_per_step
+    res["p50_ms_per_call"] = statistics.median(step_ms)
+    res["latency_note"] = f"p50 of {lat_n} calls on one stream with nothing else in flight (after the timed region)"
     kname = "conv_igemm_f32" if precision == "fp32" else "conv_igemm_bf16x3"      # the library names the family by its base mode
     conv = stats.get(kname)
     if conv and conv_union_ms > 0:
@@ -413,10 +431,18 @@ def main():
                          "parity), bf16x3 = 3-term split-bf16 (parity), fp32 = exact fp32 MFMA (parity), bf16x3_gbf16 = opt-in "
                          "2-term gamma|beta convs, fp8 = declared non-parity")
     ap.add_argument("--streams", type=int, default=1, help="generator handles / HIP streams the steps alternate over")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="skip the other single-GPU configurations and the B=1 latency")
-    ap.add_argument("--no-profile", action="store_true", help="do not bracket kernels with HIP events")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure and check everything beyond the headline: roofline and per-kernel figures, latencies, "
+                         "the other configurations, the CPU baseline, the non-finite output check")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the last timed step's generator output (rank 0) to DIR/output.npy")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
+    ap.add_argument("--no-also", action="store_true",
+                    help="with --full: skip the other single-GPU configurations and the B=1 latency")
+    ap.add_argument("--no-profile", action="store_true", help="with --full: do not bracket kernels with HIP events")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be >= 1 and --warmup >= 0")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args)
 
@@ -425,9 +451,10 @@ def main():
         raise SystemExit("bench.py needs an MI355X; there is no CPU fallback")
     D = Dist(args)
     solo = D.world == 1
-    res = run_workload(args, D, args.workload, args.precision, with_cpu=solo and not args.no_cpu_baseline,
-                       with_b1=solo and not args.no_also)
-    if solo and not args.no_also:
+    full = args.full
+    res = run_workload(args, D, args.workload, args.precision, with_cpu=full and solo and not args.no_cpu_baseline,
+                       with_b1=full and solo and not args.no_also, dump_dir=args.dump_outputs)
+    if full and solo and not args.no_also:
         also = {}
         for wl, prec in (("spade512", "fp32"), ("spade512", "bf16x3"), ("spade512", "bf16x3_gbf16"), ("spade512", "fp8"), ("spade512", "f16"),
                          ("spade256", "f16c"), ("spade256", "bf16x3"), ("spade256", "fp32")):

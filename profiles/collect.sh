@@ -25,12 +25,12 @@ python profiles/pmc_util.py $O/pmc_sq/p_counter_collection.csv conv > $O/spade25
 rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VALU SQ_INSTS_LDS SQ_ACTIVE_INST_LDS SQ_WAIT_INST_LDS --kernel-trace -d $O/pmc_lds -o p --output-format csv -- python3 profiles/run_forwards.py spade256 3 > $O/pmc_lds.log 2>&1 || exit 1
 python profiles/pmc_util.py $O/pmc_lds/p_counter_collection.csv conv >> $O/spade256_bf16x3_sq_counters.txt || exit 1
 echo "pmc sq done"
-rocprofv3 --kernel-trace --stats -d $O/kt_bench -o kt --output-format csv -- python3 bench.py --no-cpu-baseline > $O/kt_bench.log 2>&1 || exit 1
+rocprofv3 --kernel-trace --stats -d $O/kt_bench -o kt --output-format csv -- python3 bench.py --full --no-cpu-baseline > $O/kt_bench.log 2>&1 || exit 1
 echo "trace of bench.py done"
-python bench.py > $O/bench_spade256_bf16x3.json 2> $O/bench_spade256_bf16x3.err || exit 1
-python bench.py --streams 2 --no-cpu-baseline > $O/bench_spade256_bf16x3_2streams.json 2> /dev/null || exit 1
-python bench.py --workload spade512 > $O/bench_spade512_bf16x3.json 2> $O/bench_spade512_bf16x3.err || exit 1
-python bench.py --precision fp32 --steps 20 > $O/bench_spade256_fp32.json 2> $O/bench_spade256_fp32.err || exit 1
+python bench.py --full > $O/bench_spade256_bf16x3.json 2> $O/bench_spade256_bf16x3.err || exit 1
+python bench.py --full --streams 2 --no-cpu-baseline > $O/bench_spade256_bf16x3_2streams.json 2> /dev/null || exit 1
+python bench.py --full --workload spade512 > $O/bench_spade512_bf16x3.json 2> $O/bench_spade512_bf16x3.err || exit 1
+python bench.py --full --precision fp32 --steps 20 > $O/bench_spade256_fp32.json 2> $O/bench_spade256_fp32.err || exit 1
 echo "bench done"
 python tools/gpu_latency.py > $O/latency.txt 2>&1 || exit 1
 python tools/gpu_p2p_latency.py > $O/p2p_latency.txt 2>&1 || exit 1

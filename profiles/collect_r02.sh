@@ -36,11 +36,11 @@ rocprofv3 --pmc SQ_WAVE_CYCLES SQ_BUSY_CYCLES SQ_VALU_MFMA_BUSY_CYCLES SQ_WAIT_A
 python profiles/pmc_util.py $O/pmc_sq_gb/p_counter_collection.csv conv > $O/spade512_bf16x3_gbf16_sq_counters.txt || exit 1
 echo "pmc sq done"
 # the driver's own command under the kernel trace: its per-kernel averages must agree with bench.py's event timing
-rocprofv3 --kernel-trace --stats -d $O/kt_bench -o kt --output-format csv -- python3 bench.py --no-cpu-baseline --no-also > $O/kt_bench.log 2>&1 || exit 1
+rocprofv3 --kernel-trace --stats -d $O/kt_bench -o kt --output-format csv -- python3 bench.py --full --no-cpu-baseline --no-also > $O/kt_bench.log 2>&1 || exit 1
 cp $O/kt_bench/kt_kernel_stats.csv $O/bench_py_kernel_stats.csv
 echo "trace of bench.py done"
-python bench.py > $O/bench.json 2> $O/bench.err || exit 1
-python bench.py --streams 2 --no-cpu-baseline --no-also > $O/bench_2streams.json 2> /dev/null || exit 1
+python bench.py --full > $O/bench.json 2> $O/bench.err || exit 1
+python bench.py --full --streams 2 --no-cpu-baseline --no-also > $O/bench_2streams.json 2> /dev/null || exit 1
 echo "bench done"
 # tile loop: trace by kernel family (idle gaps between tiles), end to end against generator-only
 rocprofv3 --kernel-trace --stats -d $O/kt_raster -o kt --output-format csv -- python3 raster_bench.py --image-size 512 --stride 64 --batch-size 8 --no-reference > $O/kt_raster.log 2>&1 || exit 1

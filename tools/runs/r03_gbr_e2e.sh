@@ -3,13 +3,14 @@ cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 timeout -k 10 900 python -m pytest tests/test_gpu_conv_kernel.py tests/test_gpu_baseline_configs.py tests/test_gpu_generator.py -m gpu -x -q -s > gpurun_out/r03_gbr_e2e_tests.log 2>&1; rc=$?
 grep -E "resident kernel|rel_linf|passed|failed|Error|error" gpurun_out/r03_gbr_e2e_tests.log | tail -30
 [ $rc -ne 0 ] && { tail -30 gpurun_out/r03_gbr_e2e_tests.log; exit $rc; }
+J=$(mktemp -d); export J   # scratch directory for the A/B bench lines
 for i in 1 2; do
-  MSR_GBR=0 python bench.py --no-cpu-baseline --no-also --steps 40 --warmup 10 > gpurun_out/r03_gbr_off_$i.json 2>/dev/null || exit 1
-  python bench.py --no-cpu-baseline --no-also --steps 40 --warmup 10 > gpurun_out/r03_gbr_on_$i.json 2>/dev/null || exit 1
+  MSR_GBR=0 python bench.py --full --no-cpu-baseline --no-also --steps 40 --warmup 10 > $J/r03_gbr_off_$i.json 2>/dev/null || exit 1
+  python bench.py --full --no-cpu-baseline --no-also --steps 40 --warmup 10 > $J/r03_gbr_on_$i.json 2>/dev/null || exit 1
 done
 python - <<'PY'
-import json
+import json, os
 for n in ("off_1","on_1","off_2","on_2"):
-    d=json.loads(open(f"gpurun_out/r03_gbr_{n}.json").read().strip().splitlines()[-1])
+    d=json.loads(open(os.path.join(os.environ["J"], f"r03_gbr_{n}.json")).read().strip().splitlines()[-1])
     print(n, round(d["value"],1), round(d["ms_per_step"],3), round(d["roofline"]["frac"],4), {k: round(v,3) for k,v in d["kernel_ms_per_call"].items()}, d.get("p50_ms_per_call_b1"), d.get("p50_ms_per_call_b1_eager"))
 PY

@@ -2,14 +2,15 @@ set -o pipefail
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT" || exit 1
 python -m pytest tests/test_gpu_conv_kernel.py tests/test_gpu_baseline_configs.py -m gpu -x -q > gpurun_out/r03_walk_tests.log 2>&1 || { tail -20 gpurun_out/r03_walk_tests.log; exit 1; }
 tail -3 gpurun_out/r03_walk_tests.log
+J=$(mktemp -d); export J   # scratch directory for the A/B bench lines
 for i in 1 2; do
-  MSR_TILE_WALK=0 python bench.py --no-cpu-baseline --no-also --steps 40 --warmup 10 > gpurun_out/r03_walk_off_$i.json 2>/dev/null || exit 1
-  python bench.py --no-cpu-baseline --no-also --steps 40 --warmup 10 > gpurun_out/r03_walk_on_$i.json 2>/dev/null || exit 1
+  MSR_TILE_WALK=0 python bench.py --full --no-cpu-baseline --no-also --steps 40 --warmup 10 > $J/r03_walk_off_$i.json 2>/dev/null || exit 1
+  python bench.py --full --no-cpu-baseline --no-also --steps 40 --warmup 10 > $J/r03_walk_on_$i.json 2>/dev/null || exit 1
 done
 python - <<'PY'
-import json
+import json, os
 for n in ("off_1","on_1","off_2","on_2"):
-    d=json.loads(open(f"gpurun_out/r03_walk_{n}.json").read().strip().splitlines()[-1])
+    d=json.loads(open(os.path.join(os.environ["J"], f"r03_walk_{n}.json")).read().strip().splitlines()[-1])
     print(n, round(d["value"],1), round(d["ms_per_step"],3), d["kernel_ms_per_call"])
 PY
 O=gpurun_out/collect_r03_walk; mkdir -p $O
