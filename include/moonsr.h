@@ -297,6 +297,12 @@ int msr_op_spade_gbr(msr_handle* h, const float* src_dev, int32_t S, const float
  *   (both are [kh][kw][C] in memory).  x_dev dense [B, r, r, C] (r, C multiples of 16); out_dev [B, 2r, 2r]. */
 int msr_op_head(msr_handle* h, const float* x_dev, const float* kernel_host, float bias, float* out_dev, int32_t B,
                 int32_t r, int32_t C, float slope, int32_t variant, void* stream);
+/* Kernel-level entry of the moments kernels (csrc/small_kernels.hip launch_moments), synchronous: per group and channel,
+ *   mean_dev[g, c] = mean over p of x[g, p, c] and std_dev[g, c] = sqrtf(float(biased variance) + eps), the form every
+ *   normalisation of the generator uses (G = 1: batch moments, spade.py:21; G = B: instance moments, blocks.py:63).
+ *   x_dev [G, P, C] fp32 (C a multiple of 32, P >= 1, G >= 1); mean_dev / std_dev [G, C]. */
+int msr_op_moments(msr_handle* h, const float* x_dev, int32_t G, int32_t P, int32_t C, float eps, float* mean_dev,
+                   float* std_dev, void* stream);
 /* HOST helper: the fp32 -> fp8 e4m3 (OCP "fn", round to nearest even, saturating at 448) conversion msr_load_weight
  * applies to the weights of the fp8 mode, exposed so that it can be checked against an independent implementation. */
 int64_t msr_quantize_e4m3(const float* host, int64_t n, uint8_t* out);
@@ -317,6 +323,10 @@ int msr_op_split_bf16(msr_handle* h, const float* in_dev, float* out_dev, int64_
 /* Debug / per-block parity aid: copy a named workspace tensor of the last msr_forward to a HOST buffer
  * (names: "ws.gen.x0", "ws.gen.rb3.x1", "ws.gen.rb3.out", "ws.enc.mv", ...).  Synchronises the device. */
 int msr_debug_tensor(msr_handle* h, const char* name, float* host_out, int64_t count);
+/* Debug, read-only: one line "<mean tensor name> <form>" per planned moments site of the network, in plan order: A (moments
+ * kernels over the tensor), B (split-K epilogue), E1 | E2 (one- | two-stage finalize of conv slabs) followed by /C (slabs of
+ * the conv_igemm epilogue) or /D (ping-pong / stream kernels).  NUL-terminated; MSR_ERR_INVALID when cap is too small. */
+int msr_debug_moment_forms(msr_handle* h, char* out, int64_t cap);
 /* Bytes of device memory held by the handle (weights + workspace). */
 int msr_device_bytes(const msr_handle* h, int64_t* bytes);
 

@@ -75,11 +75,13 @@ SYMBOLS = [
                                       C.c_int32, _P, _P, C.c_int32, C.c_int32, _P]),
     ("msr_op_spade_gbr", C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P]),
     ("msr_op_head", C.c_int, [_P, _P, _P, C.c_float, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P]),
+    ("msr_op_moments", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P, _P, _P]),
     ("msr_quantize_e4m3", C.c_int64, [_P, C.c_int64, _P]),
     ("msr_op_conv3x3_fp8", C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P,
                                      C.c_int32, _P, _P, C.c_int32, C.c_int32, _P]),
     ("msr_op_split_bf16", C.c_int, [_P, _P, _P, C.c_int64, _P]),
     ("msr_debug_tensor", C.c_int, [_P, C.c_char_p, _P, C.c_int64]),
+    ("msr_debug_moment_forms", C.c_int, [_P, _P, C.c_int64]),
     ("msr_device_bytes", C.c_int, [_P, C.POINTER(C.c_int64)]),
 ]
 

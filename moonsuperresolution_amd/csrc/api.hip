@@ -1797,6 +1797,21 @@ int msr_op_head(msr_handle* h, const float* x_dev, const float* kernel_host, flo
     return MSR_OK;
 }
 
+int msr_op_moments(msr_handle* h, const float* x_dev, int32_t G, int32_t P, int32_t C, float eps, float* mean_dev,
+                   float* std_dev, void* stream) {
+    if (!h) return MSR_ERR_INVALID;
+    if (!x_dev || !mean_dev || !std_dev || G < 1 || G > 65535 || P < 1 || C < 32 || C % 32 || !(eps >= 0.f))
+        return fail(h, MSR_ERR_INVALID, "msr_op_moments: bad argument (G in [1, 65535], P >= 1, C a multiple of 32, eps >= 0)");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    double* partial = nullptr;
+    HIPCHK(h, hipMalloc(&partial, (size_t)G * moments_chunks(G, P) * C * 2 * sizeof(double)));
+    hipError_t e = launch_moments(x_dev, G, P, C, eps, partial, mean_dev, std_dev, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    hipFree(partial);
+    if (e != hipSuccess) return fail(h, MSR_ERR_DEVICE, "msr_op_moments failed: %s", hipGetErrorString(e));
+    return MSR_OK;
+}
+
 int64_t msr_quantize_e4m3(const float* host, int64_t n, uint8_t* out) {
     if (!host || !out || n < 0) return -1;
     for (int64_t i = 0; i < n; ++i) out[i] = msr_f32_to_e4m3(host[i]);
@@ -1853,6 +1868,32 @@ int msr_debug_tensor(msr_handle* h, const char* name, float* host_out, int64_t c
     HIPCHK(h, hipSetDevice(h->cfg.device));
     HIPCHK(h, hipDeviceSynchronize());
     HIPCHK(h, hipMemcpy(host_out, it->second, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
+    return MSR_OK;
+}
+
+int msr_debug_moment_forms(msr_handle* h, char* out, int64_t cap) {
+    if (!h || !out || cap < 1) return MSR_ERR_INVALID;
+    // one line "<mean tensor> <form>" per planned moments site, in plan order.  Forms: A moments kernels over the tensor,
+    // B split-K epilogue, E1 / E2 one- / two-stage slab finalize after the slabs of the conv_igemm epilogue (/C) or of
+    // the ping-pong / stream kernels (/D)
+    auto name_of = [&](const float* ptr) -> std::string {
+        for (const auto& kv : h->dev) if (kv.second == ptr) return kv.first;
+        return "?";
+    };
+    std::string txt;
+    for (size_t i = 0; i < h->ops.size(); ++i) {
+        const Op& op = h->ops[i];
+        if (op.type == OP_MOMENTS) {
+            txt += name_of(op.mom.mean) + " A\n";
+        } else if (op.type == OP_CONV && op.conv.mom_mean) {
+            txt += name_of(op.conv.mom_mean) + " B\n";
+        } else if (op.type == OP_MOMENTS_SLABS && i > 0) {
+            const bool two = op.mom.P >= 512;
+            txt += name_of(op.mom.mean) + (two ? " E2/" : " E1/") + (h->ops[i - 1].tile == TILE_256x128_PP ? "D\n" : "C\n");
+        }
+    }
+    if ((int64_t)txt.size() + 1 > cap) return fail(h, MSR_ERR_INVALID, "msr_debug_moment_forms: %zu bytes needed", txt.size() + 1);
+    memcpy(out, txt.c_str(), txt.size() + 1);
     return MSR_OK;
 }
 

@@ -384,7 +384,9 @@ __device__ __forceinline__ void halo16_epilogue_body(const ConvParams& p, f32x4 
                 for (int i = 0; i < 4; ++i)
                     res[i] = *reinterpret_cast<const float4*>(abase + ((y0 + i) >> p.aux_shift) * p.aux_py);
             }
-            float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
+            // the lane's 4 values are shifted by its first one (a data value: offsets of the accumulator or of the residual
+            // cancel, not only the bias); the 16 lanes of a row are combined as (mean, M2) with the between-lane term
+            float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f}, pv[4];
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
                 float d[4];
@@ -394,15 +396,20 @@ __device__ __forceinline__ void halo16_epilogue_body(const ConvParams& p, f32x4 
                 *reinterpret_cast<float4*>(obase + (y0 + i) * p.out_py + col) =
                     make_float4(d[0] + bq[0], d[1] + bq[1], d[2] + bq[2], d[3] + bq[3]);
 #pragma unroll
-                for (int k = 0; k < 4; ++k) { s1[k] += d[k]; s2[k] += d[k] * d[k]; }
+                for (int k = 0; k < 4; ++k) {
+                    if (i == 0) pv[k] = d[k];
+                    const float e = d[k] - pv[k];
+                    s1[k] += e; s2[k] += e * e;
+                }
             }
             if (p.stat_partial) {
                 float mean[4], m2[4];
 #pragma unroll
                 for (int k = 0; k < 4; ++k) {
-                    const float t1 = row16_sum(s1[k]), t2 = row16_sum(s2[k]);
-                    mean[k] = bq[k] + t1 * (1.f / 64.f);
-                    const float t = t2 - t1 * t1 * (1.f / 64.f);
+                    const float mu = row16_sum(4.f * pv[k] + s1[k]) * (1.f / 64.f);
+                    const float dl = (pv[k] - mu) + s1[k] * 0.25f;
+                    const float t = row16_sum(s2[k] - s1[k] * s1[k] * 0.25f + 4.f * dl * dl);
+                    mean[k] = bq[k] + mu;
                     m2[k] = t > 0.f ? t : 0.f;
                 }
                 if (px == 0) {

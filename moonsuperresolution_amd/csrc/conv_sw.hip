@@ -122,7 +122,8 @@ __device__ __forceinline__ void sw_epilogue_body(const ConvParams& p, const SwGe
                     for (int ii = 0; ii < 4; ++ii)
                         res[ii] = *reinterpret_cast<const float4*>(abase + ((ty0 + q4 * 4 + ii) >> p.aux_shift) * p.aux_py);
                 }
-                float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f};
+                // shifted by the lane's first value, lanes combined as (mean, M2): as the ping-pong kernel (conv_igemm.hip)
+                float s1[4] = {0.f, 0.f, 0.f, 0.f}, s2[4] = {0.f, 0.f, 0.f, 0.f}, pv[4];
 #pragma unroll
                 for (int ii = 0; ii < 4; ++ii) {
                     const int i = q4 * 4 + ii;
@@ -133,15 +134,20 @@ __device__ __forceinline__ void sw_epilogue_body(const ConvParams& p, const SwGe
                     *reinterpret_cast<float4*>(obase + (ty0 + i) * p.out_py + col) =
                         make_float4(d[0] + bq[0], d[1] + bq[1], d[2] + bq[2], d[3] + bq[3]);
 #pragma unroll
-                    for (int k = 0; k < 4; ++k) { s1[k] += d[k]; s2[k] += d[k] * d[k]; }
+                    for (int k = 0; k < 4; ++k) {
+                        if (ii == 0) pv[k] = d[k];
+                        const float e = d[k] - pv[k];
+                        s1[k] += e; s2[k] += e * e;
+                    }
                 }
                 if (p.stat_partial) {
                     float mean[4], m2[4];
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
-                        const float t1 = sw_row16_sum(s1[k]), t2 = sw_row16_sum(s2[k]);
-                        mean[k] = bq[k] + t1 * (1.f / 64.f);
-                        const float t = t2 - t1 * t1 * (1.f / 64.f);
+                        const float mu = sw_row16_sum(4.f * pv[k] + s1[k]) * (1.f / 64.f);
+                        const float dl = (pv[k] - mu) + s1[k] * 0.25f;
+                        const float t = sw_row16_sum(s2[k] - s1[k] * s1[k] * 0.25f + 4.f * dl * dl);
+                        mean[k] = bq[k] + mu;
                         m2[k] = t > 0.f ? t : 0.f;
                     }
                     if (px == 0) {

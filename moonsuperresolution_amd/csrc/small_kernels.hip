@@ -209,8 +209,11 @@ hipError_t launch_split_bf16(const float* in, float* out, long n, hipStream_t s)
 }
 
 // ------------------------------------------------------------------------------------------------
-// moments: per-group per-channel mean and sqrt(biased var + eps), fp64 accumulation of sum and sum of
-// squares (exact to fp64 rounding, so the one-pass form equals TF's two-pass moments at fp32 precision).
+// moments: per-group per-channel mean and sqrt(biased var + eps).  Every pixel chunk sums x - pivot and (x - pivot)^2, the
+// pivot being the chunk's first value of the channel (short fp32 runs flushed into fp64), and leaves its (mean, M2); the
+// final kernel combines the chunks in fp64 (mean first, then M2 plus the between-chunk term).  Shifting by a data value
+// keeps the error of the variance at ~2^-24 of the variance itself: the unshifted sum of x^2 lost ~2^-24 m^2, a 1e-3
+// relative error of var at |m| / sigma = 100 (tests/test_gpu_moments.py).
 // Stage 1: grid (chunks, G); thread = (channel quad, pixel slot); Stage 2: one thread per (g, c).
 // ------------------------------------------------------------------------------------------------
 // Pixels per stage-1 workgroup: 128 for the big tensors (thousands of workgroups keep enough bytes in flight); the
@@ -233,25 +236,31 @@ int moments_chunks(int G, int P) {
     return (P + px - 1) / px;
 }
 
-// sums of one pixel chunk: the values come from `load(pixel, quad)` (a tensor in memory, or the split-K epilogue's freshly
-// combined output).  partial layout: [G][chunks][C][2]
+// (mean, M2) of one pixel chunk: the values come from `load(pixel, quad)` (a tensor in memory, or the split-K epilogue's
+// freshly combined output; every pixel is loaded exactly once).  partial layout: [G][chunks][C][2]
 // A workgroup covers the channel quads [q_lo, q_lo + quads) of its pixel chunk (blockIdx.z cuts the channels when the
-// pixels alone do not give ~256 workgroups).
+// pixels alone do not give ~256 workgroups).  piv: 256 float4 of LDS.
 template <typename Load>
 __device__ __forceinline__ void moments_chunk_sums(Load load, int p0, int p1, int C, int q_lo, int quads, int g, int chunk,
-                                                   int chunks, double* __restrict__ partial, double* red) {
+                                                   int chunks, double* __restrict__ partial, double* red, float4* piv) {
     for (int qb = 0; qb < quads; qb += 256) {
         // layout A (quads >= 256): every thread one quad, all pixels.  layout B: several pixel slots per quad.
         const int tq = quads >= 256 ? 256 : quads;     // threads along channel quads
         const int slots = 256 / tq;                    // pixel slots
         const int q = q_lo + qb + threadIdx.x % tq;
         const int slot = threadIdx.x / tq;
+        // the pivot: pixel p0, loaded by slot 0 (its deviation is 0, so slot 0 goes on at p0 + slots)
+        if (slot == 0 && q < q_lo + quads) piv[threadIdx.x] = load(p0, q);
+        __syncthreads();
         double s[4] = {0, 0, 0, 0}, ss[4] = {0, 0, 0, 0};
+        const float4 pv = piv[threadIdx.x % tq];
         if (q < q_lo + quads) {
+            auto dev = [&](float4 v) { return make_float4(v.x - pv.x, v.y - pv.y, v.z - pv.z, v.w - pv.w); };
             // 4 independent 16-byte loads in flight per thread; short fp32 runs flushed into fp64 accumulators
-            int pix = p0 + slot;
+            int pix = p0 + (slot == 0 ? slots : slot);
             for (; pix + 3 * slots < p1; pix += 4 * slots) {
-                const float4 v0 = load(pix, q), v1 = load(pix + slots, q), v2 = load(pix + 2 * slots, q), v3 = load(pix + 3 * slots, q);
+                const float4 v0 = dev(load(pix, q)), v1 = dev(load(pix + slots, q)), v2 = dev(load(pix + 2 * slots, q)),
+                             v3 = dev(load(pix + 3 * slots, q));
                 s[0] += (double)((v0.x + v1.x) + (v2.x + v3.x)); s[1] += (double)((v0.y + v1.y) + (v2.y + v3.y));
                 s[2] += (double)((v0.z + v1.z) + (v2.z + v3.z)); s[3] += (double)((v0.w + v1.w) + (v2.w + v3.w));
                 ss[0] += (double)((v0.x * v0.x + v1.x * v1.x) + (v2.x * v2.x + v3.x * v3.x));
@@ -260,7 +269,7 @@ __device__ __forceinline__ void moments_chunk_sums(Load load, int p0, int p1, in
                 ss[3] += (double)((v0.w * v0.w + v1.w * v1.w) + (v2.w * v2.w + v3.w * v3.w));
             }
             for (; pix < p1; pix += slots) {
-                const float4 v = load(pix, q);
+                const float4 v = dev(load(pix, q));
                 s[0] += v.x; s[1] += v.y; s[2] += v.z; s[3] += v.w;
                 ss[0] += (double)v.x * v.x; ss[1] += (double)v.y * v.y;
                 ss[2] += (double)v.z * v.z; ss[3] += (double)v.w * v.w;
@@ -270,57 +279,74 @@ __device__ __forceinline__ void moments_chunk_sums(Load load, int p0, int p1, in
         for (int k = 0; k < 4; ++k) { red[threadIdx.x * 8 + k] = s[k]; red[threadIdx.x * 8 + 4 + k] = ss[k]; }
         __syncthreads();
         if (slot == 0 && q < q_lo + quads) {
+            const double n = p1 - p0;
+            const float pk[4] = {pv.x, pv.y, pv.z, pv.w};
             for (int k = 0; k < 4; ++k) {
                 double a = 0, b = 0;
                 for (int sl = 0; sl < slots; ++sl) {
                     a += red[(sl * tq + threadIdx.x) * 8 + k];
                     b += red[(sl * tq + threadIdx.x) * 8 + 4 + k];
                 }
+                const double m2 = b - a * (a / n);
                 double* o = partial + (((size_t)g * chunks + chunk) * C + q * 4 + k) * 2;
-                o[0] = a; o[1] = b;
+                o[0] = (double)pk[k] + a / n;
+                o[1] = m2 > 0 ? m2 : 0.0;
             }
         }
         __syncthreads();
     }
 }
 
-// one workgroup per (group, 32 channels): 32 chunk slots x 32 channels, fixed-order tree -> deterministic
+// one workgroup per (group, 32 channels): 32 chunk slots x 32 channels, fixed-order tree -> deterministic.  Two passes over
+// the chunks' (mean, M2): the mean, then M2 = sum of M2_k + n_k (mean_k - mean)^2.
 __global__ void __launch_bounds__(1024) moments_final_kernel(const double* __restrict__ partial, int G, int chunks,
-                                                            int C, int P, float eps, float* __restrict__ mean,
+                                                            int chunk_px, int C, int P, float eps, float* __restrict__ mean,
                                                             float* __restrict__ stdv) {
-    __shared__ double red[32][32][2];
+    __shared__ double red[32][32];
+    __shared__ double mu_c[32];
     const int cblocks = C / 32;
     const int g = blockIdx.x / cblocks, c = (blockIdx.x % cblocks) * 32 + (threadIdx.x & 31);
     const int slot = threadIdx.x >> 5;
-    double s = 0, ss = 0;
-    for (int k = slot; k < chunks; k += 32) {
-        const double2 v = *reinterpret_cast<const double2*>(partial + (((size_t)g * chunks + k) * C + c) * 2);
-        s += v.x; ss += v.y;
-    }
-    red[slot][threadIdx.x & 31][0] = s;
-    red[slot][threadIdx.x & 31][1] = ss;
+    const double* pc = partial + ((size_t)g * chunks * C + c) * 2;
+    auto count = [&](int k) { return (double)(min(P, (k + 1) * chunk_px) - k * chunk_px); };
+    double s = 0;
+    for (int k = slot; k < chunks; k += 32) s += count(k) * pc[(size_t)k * C * 2];
+    red[slot][threadIdx.x & 31] = s;
     __syncthreads();
     if (slot == 0) {
-        for (int k = 1; k < 32; ++k) { s += red[k][threadIdx.x][0]; ss += red[k][threadIdx.x][1]; }
-        const double m = s / P;
-        double var = ss / P - m * m;
-        if (var < 0) var = 0;
+        for (int k = 1; k < 32; ++k) s += red[k][threadIdx.x];
+        mu_c[threadIdx.x] = s / P;
+    }
+    __syncthreads();
+    const double m = mu_c[threadIdx.x & 31];
+    double m2 = 0;
+    for (int k = slot; k < chunks; k += 32) {
+        const double2 v = *reinterpret_cast<const double2*>(pc + (size_t)k * C * 2);
+        const double d = v.x - m;
+        m2 += v.y + count(k) * d * d;
+    }
+    __syncthreads();
+    red[slot][threadIdx.x & 31] = m2;
+    __syncthreads();
+    if (slot == 0) {
+        for (int k = 1; k < 32; ++k) m2 += red[k][threadIdx.x];
         mean[(size_t)g * C + c] = (float)m;
         // the reference adds eps in float32 and takes a float32 sqrt (spade.py:22); mirror that rounding
-        stdv[(size_t)g * C + c] = sqrtf((float)var + eps);
+        stdv[(size_t)g * C + c] = sqrtf((float)(m2 / P) + eps);
     }
 }
 
 __global__ void __launch_bounds__(256) moments_partial_kernel(const float* __restrict__ x, int P, int C, int chunk_px,
                                                               double* __restrict__ partial) {
     __shared__ double red[256 * 8];
+    __shared__ float4 piv[256];
     const int chunk = blockIdx.x, g = blockIdx.y, chunks = gridDim.x;
     const int p0 = chunk * chunk_px;
     const int p1 = min(P, p0 + chunk_px);
     const int quads = C / 4 / gridDim.z;
     const float* xg = x + (size_t)g * P * C;
     moments_chunk_sums([&](int pix, int q) { return *reinterpret_cast<const float4*>(xg + (size_t)pix * C + q * 4); },
-                       p0, p1, C, blockIdx.z * quads, quads, g, chunk, chunks, partial, red);
+                       p0, p1, C, blockIdx.z * quads, quads, g, chunk, chunks, partial, red, piv);
 }
 
 hipError_t launch_moments(const float* x, int G, int P, int C, float eps, double* partial, float* mean, float* stdv,
@@ -329,7 +355,7 @@ hipError_t launch_moments(const float* x, int G, int P, int C, float eps, double
     const int chunks = moments_chunks(G, P);
     moments_partial_kernel<<<dim3(chunks, G, moments_channel_blocks(G, P, C)), 256, 0, s>>>(x, P, C, moments_chunk_pixels(G, P),
                                                                                           partial);
-    moments_final_kernel<<<G * (C / 32), 1024, 0, s>>>(partial, G, chunks, C, P, eps, mean, stdv);
+    moments_final_kernel<<<G * (C / 32), 1024, 0, s>>>(partial, G, chunks, moments_chunk_pixels(G, P), C, P, eps, mean, stdv);
     return hipGetLastError();
 }
 
@@ -344,6 +370,7 @@ hipError_t launch_moments(const float* x, int G, int P, int C, float eps, double
 template <int EPI>
 __global__ void __launch_bounds__(256) splitk_epilogue_mom_kernel(const ConvParams p, int chunk_px) {
     __shared__ double red[256 * 8];
+    __shared__ float4 piv[256];
     const int chunk = blockIdx.x, g = blockIdx.y, chunks = gridDim.x;
     const int P = (p.mom_G > 1 ? 1 : p.B) * p.Hout * p.Wout;        // pixels per group: one sample, or the whole batch
     const int p0 = chunk * chunk_px;
@@ -377,7 +404,7 @@ __global__ void __launch_bounds__(256) splitk_epilogue_mom_kernel(const ConvPara
         return v;
     };
     const int quads = p.N / 4 / gridDim.z;
-    moments_chunk_sums(load, p0, p1, p.N, blockIdx.z * quads, quads, g, chunk, chunks, p.mom_partial, red);
+    moments_chunk_sums(load, p0, p1, p.N, blockIdx.z * quads, quads, g, chunk, chunks, p.mom_partial, red, piv);
 }
 
 hipError_t launch_splitk_epilogue_mom(const ConvParams& p, int epi, hipStream_t s) {
@@ -389,7 +416,8 @@ hipError_t launch_splitk_epilogue_mom(const ConvParams& p, int epi, hipStream_t 
     const dim3 grid(chunks, G, moments_channel_blocks(G, P, p.N));
     if (epi == EPI_BIAS) splitk_epilogue_mom_kernel<EPI_BIAS><<<grid, 256, 0, s>>>(p, moments_chunk_pixels(G, P));
     else splitk_epilogue_mom_kernel<EPI_RES><<<grid, 256, 0, s>>>(p, moments_chunk_pixels(G, P));
-    moments_final_kernel<<<G * (p.N / 32), 1024, 0, s>>>(p.mom_partial, G, chunks, p.N, P, p.mom_eps, p.mom_mean, p.mom_std);
+    moments_final_kernel<<<G * (p.N / 32), 1024, 0, s>>>(p.mom_partial, G, chunks, moments_chunk_pixels(G, P), p.N, P, p.mom_eps,
+                                                         p.mom_mean, p.mom_std);
     return hipGetLastError();
 }
 

@@ -178,6 +178,13 @@ class Generator:
         _lib.raise_for(self._lib, self._h, rc, f"msr_debug_tensor({name})")
         return out
 
+    def moment_forms(self) -> dict:
+        """{mean tensor name: form} of every planned moments site (msr_debug_moment_forms: A, B, E1/C, E1/D, E2/C, E2/D)."""
+        buf = C.create_string_buffer(1 << 16)
+        rc = self._lib.msr_debug_moment_forms(self._h, buf, len(buf))
+        _lib.raise_for(self._lib, self._h, rc, "msr_debug_moment_forms")
+        return dict(line.split(" ") for line in buf.value.decode().splitlines())
+
     # -- measurement ---------------------------------------------------------------------------------
     def forward_flops(self) -> float:
         v = C.c_double()

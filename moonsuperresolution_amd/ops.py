@@ -389,6 +389,19 @@ def f16c_decode(img: torch.Tensor):
     return hi, h8, l8 / 2048.0
 
 
+def moments(ctx: OpContext, x: torch.Tensor, eps: float):
+    """One run of the moments kernels (msr_op_moments): x [G, P, C] float32 -> (mean, std), each [G, C], with
+    std = sqrtf(float(biased variance) + eps) — the moments of every normalisation in the generator."""
+    G, P, Cc = x.shape
+    x = x.contiguous()
+    mean = torch.empty((G, Cc), dtype=torch.float32, device=x.device)
+    std = torch.empty_like(mean)
+    rc = ctx.lib.msr_op_moments(ctx.h, x.data_ptr(), G, P, Cc, float(eps), mean.data_ptr(), std.data_ptr(),
+                                torch.cuda.current_stream(x.device).cuda_stream)
+    _lib.raise_for(ctx.lib, ctx.h, rc, "msr_op_moments")
+    return mean, std
+
+
 def head(ctx: OpContext, x: torch.Tensor, kernel: "np.ndarray", bias: float, slope: float = 0.2, transpose_tanh: bool = False) -> torch.Tensor:
     """One launch of the head kernel (msr_op_head): x dense [B, r, r, C] -> [B, 2r, 2r].  kernel [4, 4, C] float32 (host):
     the Conv2D(1, 4, 'same') kernel applied after UpSampling2D(2) (networks.py:54-56), or with ``transpose_tanh`` the

@@ -25,6 +25,9 @@ from tests.helpers import rel_linf
 
 pytestmark = pytest.mark.gpu
 TOL = 1e-3
+# per-mode regression bounds, ~5x the largest recorded output error of each mode (profiles/r03_parity_baseline_configs.jsonl:
+# fp32 4.8e-6, bf16x3 1.9e-5, f16c 5.5e-5 with the opt-in fp6 cross pieces); bf16x3_gbf16 keeps the bar
+MODE_TOL = {"fp32": 2.5e-5, "bf16x3": 1e-4, "f16c": 2.5e-4, "bf16x3_gbf16": TOL}
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 GEN_FILTERS = [1024, 1024, 1024, 512, 256, 128]
 
@@ -89,17 +92,26 @@ def test_baseline_config_matches_oracle(hip_lib, S, B, precision):
     s_ref = np.sqrt(x1_ref.var((0, 1, 2)) + 1e-5)
     e_mean = float(np.abs(gen.debug_tensor("ws.gen.rb5.mean1", (256,)) - m_ref).max() / s_ref.max())
     e_std = rel_linf(gen.debug_tensor("ws.gen.rb5.std1", (256,)), s_ref)
+    # the moments the GPU took of its own x1, against float64 (tests/test_gpu_moments.py: 2^-21 max|x| and 2e-6 relative)
+    m_gpu, s_gpu = gen.debug_tensor("ws.gen.rb5.mean1", (256,)), gen.debug_tensor("ws.gen.rb5.std1", (256,))
+    x1d = x1.astype(np.float64).reshape(-1, 256)
+    m_own = x1d.mean(0)
+    s_own = np.sqrt((((x1d - m_own) ** 2).mean(0)).astype(np.float32) + np.float32(1e-5)).astype(np.float64)
+    self_mean_ok = bool((np.abs(m_gpu - m_own) <= 2.0 ** -21 * np.abs(x1d).max(0)).all())
+    self_std = float((np.abs(s_gpu - s_own) / s_own).max())
     e_rb4 = rel_linf(gen.debug_tensor("ws.gen.rb4.out", (B, r4, r4, 512)), cap["gen.rb4.out"])
     e_z = rel_linf(gen.last_latent(), cap["z"])
     _record(S=S, B=B, precision=precision + ("+fp6 main-conv cross pieces (MSR_F16C_FP6=1)" if os.environ.get("MSR_F16C_FP6") == "1" else ""),
             oracle=oracle_dtype, rel_linf_output=err, rel_linf_rb5_x1=e_x1,
-            rb5_mean1=e_mean, rb5_std1=e_std, rel_linf_rb4_out=e_rb4, rel_linf_z=e_z)
+            rb5_mean1=e_mean, rb5_std1=e_std, rb5_std1_vs_own_x1=self_std, rel_linf_rb4_out=e_rb4, rel_linf_z=e_z)
     gen.close()
     del gen
     torch.cuda.empty_cache()
     assert y.shape == (B, S, S, 1) and np.isfinite(y).all()
     assert err <= TOL, err
     assert max(e_x1, e_rb4, e_z, e_mean, e_std) <= TOL, (e_x1, e_rb4, e_z, e_mean, e_std)
+    assert err <= MODE_TOL[precision], (precision, err)
+    assert self_mean_ok and self_std <= 2e-6, self_std
 
 
 def test_f16c_with_the_opt_in_fp6_cross_pieces_matches_oracle():
