@@ -55,6 +55,35 @@ struct Op {
 
 struct ProfRec { int fam; hipEvent_t a, b; double flops, bytes; int launches; };
 
+// Weight image of a conv: what msr_load_weight builds from the [taps][N][Cin] kernel layout (upload_conv_weight)
+enum WeightImage {
+    IMG_F32,         // fp32 as is
+    IMG_BF16,        // split-bf16 words: every 32 consecutive k become [32 hi | 32 lo]
+    IMG_BF16_FRAG,   // split-bf16 in MFMA-fragment order (conv_igemm_bf16x3: B fragments straight to VGPRs)
+    IMG_F16,         // split-fp16 words (PREC_F16X2)
+    IMG_FP8,         // fp8 e4m3 bytes + key.wexp (PREC_FP8)
+    IMG_F16C,        // f16c chunk image + key.wexp (PREC_F16C)
+    IMG_F16C6,       // f16c6 chunk image, scales inside (PREC_F16C6)
+    IMG_GBR,         // the weight stream of conv_gb_resident (gbr_weight_stream)
+};
+
+// Form of one conv layer: the kernel that runs it and the weight image that kernel reads.  msr_load_weight and the planner
+// both take it from the handle's form table (fill_forms), so a layer's weights are always in the layout its launch expects.
+struct ConvForm {
+    int prec = PREC_F32, tile = TILE_64x64, ksplit = 1, wt_frag = 0;
+    int no_cross = 0;                 // f16 mode: the stream / resident kernels leave the cross terms out
+    WeightImage img = IMG_F32;
+};
+
+// Form of one SPADE layer of the generator and of the conv it feeds (gen.rbI.spade_J -> gen.rbI.conv_J)
+struct SpadeForm {
+    bool gbr = false;                 // conv_gb_resident: embedding + gamma|beta conv + SPADE epilogue in one launch
+    int h_split = 0, hslots = 128;    // mask embedding (not run under gbr): out_split, float slots per pixel of its output
+    ConvForm gb;                      // gamma|beta conv
+    int a_split = 0, aslots = 0;      // the format the gamma|beta conv writes for the consumer, float slots per pixel
+    ConvForm cv;                      // consumer conv
+};
+
 }  // namespace
 
 struct msr_handle {
@@ -65,6 +94,8 @@ struct msr_handle {
     bool fp8 = false;                            // MSR_FLAG_FP8: declared non-parity mode (fp8 weights x bf8 activations)
     bool f16c = false;                           // MSR_FLAG_F16C: fp16 main term + fp8 cross terms in the chip-filling convs
     bool f16m = false;                           // MSR_FLAG_F16_MAIN: F16C without the cross terms in the stream / resident kernels
+    ConvForm enc_forms[6];                       // [i]: enc.ds<i> (i = 2..5)
+    SpadeForm spade_forms[7][4];                 // [i][j]: gen.rb<i>.spade_<j> and gen.rb<i>.conv_<j> (i = 1..6, j = 1..3)
     std::string err;
     std::vector<WeightSpec> specs;
     std::map<std::string, int> spec_index;
@@ -252,22 +283,22 @@ void hwio_to_tap_oc_ic(const float* src, float* dst, int taps, int cin, int cout
         }
 }
 
-// Weights consumed by conv_igemm_bf16x3 are uploaded in MFMA-fragment order (conv_igemm.hip):
+// The split images IMG_BF16, IMG_BF16_FRAG and IMG_F16 of [taps][N][Cin] weights.  Weights consumed by conv_igemm_bf16x3
+// are uploaded in MFMA-fragment order (conv_igemm.hip):
 //   [tap][chunk of 32 k][n-tile of 32][kg][hi|lo][lane = 32*h + j][8 bf16],  value = W[tap][32*nt + j][32*cc + 16*kg + 8*h + e]
-// `host` is the kernel layout [taps][N][Cin].
-int upload_conv_weight(msr_handle* h, const std::string& key, const float* host, size_t floats, int taps, int N,
-                       int Cin, bool frag, bool f16 = false) {
-    if (h->prec != PREC_BF16X3) return upload(h, key, host, floats);
-    if (N % 32 || Cin % 32 || (size_t)taps * N * Cin != floats)
+int upload_conv_weight_split(msr_handle* h, const std::string& key, const float* host, int taps, int N, int Cin,
+                             WeightImage img) {
+    if (N % 32 || Cin % 32)
         return fail(h, MSR_ERR_INVALID, "%s: bf16x3 needs Cin and Cout multiples of 32", key.c_str());
+    const size_t floats = (size_t)taps * N * Cin;
     std::vector<float> t(floats);
-    if (f16) {
+    if (img == IMG_F16) {
         // split-fp16 image of [tap][N][Cin] (PREC_F16X2 reads only the hi half of every chunk)
         for (size_t i = 0; i + 3 < floats; i += 4)
             msr_store_split4_f16(t.data() + (i & ~(size_t)31), (int)(i & 31), host[i], host[i + 1], host[i + 2], host[i + 3]);
         return upload(h, key, t.data(), floats);
     }
-    if (!frag) {
+    if (img == IMG_BF16) {
         // split-bf16 image of [tap][N][Cin]: every 32 consecutive k become [32 hi | 32 lo]
         for (size_t i = 0; i + 3 < floats; i += 4)
             msr_store_split4(t.data() + (i & ~(size_t)31), (int)(i & 31), host[i], host[i + 1], host[i + 2], host[i + 3]);
@@ -328,66 +359,12 @@ std::vector<float> head_weff_transpose(const float* k44c, int C) {
     return weff;
 }
 
-struct ConvVariant { int tile; int wt_frag; int ksplit; };   // ksplit 0: conv_pick_ksplit decides (small tiles)
-ConvVariant pick_conv_variant(int B, int rout, int N, int stride, int epi, int prec, int cin);
-
-// MSR_FLAG_FP8: a 3x3 stride-1 conv runs the fp8 form of the persistent ping-pong kernel when it fills the chip with
-// whole tiles (B * (r/16)^2 * (N/128) >= 256, no K split); its input then holds one byte per channel: 128 channels (one
-// 128-byte chunk) or a multiple of 256 (chunk pairs).
-bool conv_fills_pp(int B, int rout, int N) {
-    return rout >= 16 && N % 128 == 0 && (long)B * (rout / 16) * (rout / 16) * (N / 128) >= 256;
-}
 // channels of an fp8 tensor: 128 (one chunk: the two-tiles-per-body form of the kernel) or a multiple of 256 (chunk pairs)
 int fp8_pad(int cin) { return cin <= 128 ? 128 : (cin + 255) / 256 * 256; }
-// gamma|beta conv of a SPADE layer normalising C channels at resolution r
-bool gb_uses_fp8(msr_handle* h, int rout, int C) { return h->fp8 && conv_fills_pp(h->B, rout, 2 * C); }
-// main conv cin -> cout fed by that SPADE layer (its producer must be a whole-tile ping-pong launch too: its epilogue
-// is the one that writes bf8)
-bool main_uses_fp8(msr_handle* h, int rout, int cin, int cout) {
-    return h->fp8 && conv_fills_pp(h->B, rout, cout) && conv_fills_pp(h->B, rout, 2 * cin);
-}
 
-int upload(msr_handle* h, const std::string& key, const float* host, size_t floats);
-// MSR_FLAG_F16C: same coverage rule as the fp8 mode (whole-tile ping-pong launches; a main conv only if the gamma|beta
-// conv that writes its input is one too)
-// Since the second half of round 2 the K-range launches of the ping-pong kernel (fewer tiles than CUs: rb2 at the BASELINE
-// sizes, most layers of a B = 1 call) run the f16c form too, their split-K epilogue writes the f16c image
-// (MSR_F16C_KSPLIT=0: the earlier rule, whole-tile launches only).
-int pp_ksplit(int B, int rout, int N, int stride, int cin, long min_items);
-bool conv_on_pp_f16c(int B, int rout, int N, int cin) {
-    static const bool ks_off = std::getenv("MSR_F16C_KSPLIT") && std::atoi(std::getenv("MSR_F16C_KSPLIT")) == 0;
-    if (ks_off) return conv_fills_pp(B, rout, N);
-    return pp_ksplit(B, rout, N, 1, cin, 128) >= 1;
-}
-bool gb_uses_f16c(msr_handle* h, int rout, int C) { return h->f16c && conv_on_pp_f16c(h->B, rout, 2 * C, 128); }
-bool main_uses_f16c(msr_handle* h, int rout, int cin, int cout) {
-    return h->f16c && cin % 64 == 0 && conv_on_pp_f16c(h->B, rout, cout, cin) && conv_on_pp_f16c(h->B, rout, 2 * cin, 128);
-}
-
-// conv_gb_resident (conv_gbr.hip) takes a SPADE layer whose gamma|beta conv AND consumer conv run f16c, when the layer has
-// enough 16 x 16 pixel tiles x channel-block ranges to fill the chip (conv_gbr_ranges; MSR_GBR=0 switches it off).  Its
-// weights are the f16c6 image with the input channels of every 32-chunk in the kernel's position order (GBR_PERM below).
-bool main_uses_f16c(msr_handle* h, int rout, int cin, int cout);
-bool main_uses_f16c6(msr_handle* h, int rout, int cin, int cout);
-bool gb_uses_gbr(msr_handle* h, int rout, int C, int cout) {
-    return h->f16c && gb_uses_f16c(h, rout, C) && main_uses_f16c(h, rout, C, cout) && !main_uses_f16c6(h, rout, C, cout) &&
-           conv_gbr_ranges(h->B, rout, 2 * C) > 0;
-}
 // position e of a 32-channel chunk holds channel GBR_PERM(e): the order in which phase 1 of conv_gb_resident leaves a pixel's
 // channels in a lane (32 x 32 MFMA rows 8q + 4h + r, halves interleaved by v_cvt_scalef32_2xpk16_fp6_f32)
 inline int gbr_perm(int e) { return 8 * (e >> 3) + 4 * (e & 1) + ((e >> 1) & 3); }
-
-// PREC_F16C6 (fp6 cross terms, kernels.h), OPT-IN with MSR_F16C_FP6=1: the main convs that run the stream kernel (conv_sw.hip:
-// whole tiles, Cin % 128 == 0) behind a gamma|beta conv that is a whole-tile ping-pong launch (its LDS-assembled epilogue
-// writes the fp6 image).  Measured: the consumer gains 6.5 % on those convs, the producer's block-scale and 6-bit
-// packing cost the gamma|beta epilogues more, net -1 % per call — it pays only once the gamma|beta convs consume fp6 too.
-// Any MSR_F16C_SW other than 1 (the A/B dispatches) switches it off.
-bool main_uses_f16c6(msr_handle* h, int rout, int cin, int cout) {
-    static const bool off = !(std::getenv("MSR_F16C_FP6") && std::atoi(std::getenv("MSR_F16C_FP6")) == 1) ||
-                            (std::getenv("MSR_F16C_SW") && std::atoi(std::getenv("MSR_F16C_SW")) != 1);
-    return !off && main_uses_f16c(h, rout, cin, cout) && cin % 128 == 0 && conv_fills_pp(h->B, rout, cout) &&
-           conv_fills_pp(h->B, rout, 2 * cin);
-}
 
 // f16c6 image of [taps][N][Cin] weights (kernels.h PREC_F16C6): per 32-channel chunk [32 x hi f16 | 24 B l6 | e8m0 | 0.. |
 // 24 B h6 | e8m0 | 0..], one power-of-two scale per output channel and piece (2^E >= max / 7.5)
@@ -543,26 +520,159 @@ int upload_conv_weight_fp8(msr_handle* h, const std::string& key, const float* h
     return upload(h, key + ".wexp", reinterpret_cast<const float*>(wexp.data()), wexp.size());
 }
 
-// Output resolution of the conv a weight belongs to ("enc.ds3.kernel" -> S>>3, "gen.rb4...." -> sw<<3).
-bool weight_conv_shape(msr_handle* h, const std::string& name, int* rout, int* stride) {
-    int i = 0;
-    *stride = 1;
-    if (std::sscanf(name.c_str(), "enc.ds%d.", &i) == 1) { *rout = h->S >> i; *stride = 2; return true; }
-    if (std::sscanf(name.c_str(), "gen.rb%d.", &i) == 1) { *rout = (h->S / 64) << (i - 1); return true; }
-    return false;
+// Uploads the [taps][N][Cin] weights `host` of a conv as the image its form reads, under `key` (+ key.wexp: the per-channel
+// scales of the fp8 / f16c images).
+int upload_conv_weight(msr_handle* h, const std::string& key, const float* host, int taps, int N, int Cin, WeightImage img) {
+    switch (img) {
+        case IMG_F32: return upload(h, key, host, (size_t)taps * N * Cin);
+        case IMG_FP8: return upload_conv_weight_fp8(h, key, host, taps, N, Cin);
+        case IMG_F16C: return upload_conv_weight_f16c(h, key, host, taps, N, Cin);
+        case IMG_F16C6: return upload_conv_weight_f16c6(h, key, host, taps, N, Cin);
+        case IMG_GBR: {
+            if (taps != 9 || Cin != 128)
+                return fail(h, MSR_ERR_INVALID, "%s: conv_gb_resident takes 3x3 x 128 inputs", key.c_str());
+            const std::vector<float> ws = gbr_weight_stream(host, N);
+            return upload(h, key, ws.data(), ws.size());
+        }
+        default: return upload_conv_weight_split(h, key, host, taps, N, Cin, img);
+    }
 }
-bool weight_uses_frag(msr_handle* h, const std::string& name, int N, int epi, int cin) {
-    if (h->prec != PREC_BF16X3) return false;
-    int rout = 0, stride = 1;
-    if (!weight_conv_shape(h, name, &rout, &stride)) return false;
-    return pick_conv_variant(h->B, rout, N, stride, epi, h->prec, cin).wt_frag != 0;
+
+// K split of the persistent ping-pong kernel for layers with fewer 16 x 16 x 128 tiles than CUs: whole chunk pairs
+// per range, a power of two, as many ranges as it takes to give every CU a work item.  0 = the layer is not one for
+// that kernel (it needs stride 1, r >= 16, Cin % 64 == 0, an input below the 2 GiB buffer-descriptor range and, split
+// or not, at least `min_items` work items — below that the small-tile split-K kernels are faster).
+int pp_ksplit(int B, int rout, int N, int stride, int cin, long min_items = 128) {
+    static const bool off = env_int("MSR_PP_KSPLIT", 1) == 0;
+    if (stride != 1 || rout < 16 || cin % 64 || N % 128) return 0;
+    if ((size_t)B * (rout + 2) * (rout + 2) * cin * sizeof(float) >= ((size_t)1 << 31)) return 0;
+    const long tiles = (long)B * (rout / 16) * (rout / 16) * (N / 128);
+    if (tiles >= 256) return 1;
+    if (off) return 0;
+    const int pairs = cin / 64;
+    int ks = 1;
+    while (tiles * ks * 2 <= 256 && pairs % (ks * 2) == 0) ks *= 2;
+    return tiles * ks >= min_items ? ks : 0;
 }
-// MSR_FLAG_GB_F16X2: the gamma|beta convs that run the persistent ping-pong kernel take 2-term fp16 products; the
-// planner (conv precision, format of the mask embedding that feeds them) and the weight upload both ask this.
-bool gb_uses_f16x2(msr_handle* h, int rout, int N, int cin) {
-    if (!h->gb_f16x2) return false;
-    const ConvVariant v = pick_conv_variant(h->B, rout, N, 1, EPI_SPADE, PREC_BF16X3, cin);
-    return v.tile == TILE_256x128_PP && v.ksplit == 1;      // the K-split launches run the 3-term form
+
+// A conv form; its weight image follows from the precision (and, under bf16x3, from the fragment order).
+ConvForm make_form(int prec, int tile, int ksplit, int wt_frag = 0, int no_cross = 0) {
+    ConvForm f;
+    f.prec = prec; f.tile = tile; f.ksplit = ksplit; f.wt_frag = wt_frag; f.no_cross = no_cross;
+    switch (prec) {
+        case PREC_BF16X3: f.img = wt_frag ? IMG_BF16_FRAG : IMG_BF16; break;
+        case PREC_F16X2: f.img = IMG_F16; break;
+        case PREC_FP8: f.img = IMG_FP8; break;
+        case PREC_F16C: f.img = IMG_F16C; break;
+        case PREC_F16C6: f.img = IMG_F16C6; break;
+        default: f.img = IMG_F32;
+    }
+    return f;
+}
+
+// Form of a plain conv in `prec` (PREC_F32 or PREC_BF16X3): the encoder's stride-2 convs, the pix2pix convs, the kernel-level
+// entries and every generator conv that no quantised form covers.  The tile and the K split follow the shape
+// (conv_pick_tile / conv_pick_ksplit, conv_igemm.hip); under bf16x3 the persistent ping-pong kernel takes the layers that
+// pp_ksplit accepts.
+ConvForm conv_form(int B, int rout, int N, int stride, int epi, int prec, int cin, int taps = 9) {
+    const int M = B * rout * rout, ksteps = taps * (cin / 32);
+    int tile = conv_pick_tile(M, N, epi, prec, ksteps), wt_frag = 0, ksplit = 0;   // ksplit 0: conv_pick_ksplit decides
+    if (prec == PREC_BF16X3) {
+        const long big_blocks = (long)((M + 127) / 128) * (N / 128);
+        const int pks = pp_ksplit(B, rout, N, stride, cin);
+        if (pks >= 1) {
+            // LDS-staged input halo, 512-thread ping-pong form (one persistent workgroup per CU, 16 x 16 pixels x 128
+            // channels per tile): 10-25 % faster than two 256-thread workgroups per CU as soon as it fills the chip
+            // once; with fewer tiles than CUs, K ranges supply the work items (pks > 1).
+            tile = TILE_256x128_PP;
+            ksplit = pks;
+        } else if (tile == TILE_64x64 || big_blocks < 256) {
+            wt_frag = 1;   // few workgroups (with split-K): B fragments straight to VGPRs, +18 % on the small tile
+        } else if (stride == 1 && rout >= 16 && cin % 64 == 0 &&
+                   (size_t)B * (rout + 2) * (rout + 2) * cin * sizeof(float) < ((size_t)1 << 31)) {   // raw buffer loads: 2 GiB
+            tile = TILE_128x128_HALO16;     // only reached with MSR_PP_KSPLIT=0: two 256-thread workgroups per CU
+            ksplit = 1;
+        }
+    }
+    return make_form(prec, tile, ksplit > 0 ? ksplit : conv_pick_ksplit(M, N, ksteps, tile, prec), wt_frag);
+}
+
+// out_split of a producer whose output feeds a conv in `prec`: the operand image that conv reads
+int split_for(int prec) {
+    switch (prec) {
+        case PREC_BF16X3: return 1;     // split-bf16 words
+        case PREC_F16X2: return 2;      // split-fp16 words
+        case PREC_FP8: return 3;        // bf8 bytes
+        case PREC_F16C: return 4;       // f16c chunk image
+        case PREC_F16C6: return 5;      // f16c6 chunk image
+        default: return 0;              // fp32
+    }
+}
+
+// Form of the SPADE layer that normalises C channels at resolution r, and of the conv C -> cout (epilogue epi) it feeds.
+// Under the quantised modes a conv takes the quantised form when it runs the persistent ping-pong kernel, and a consumer
+// only when its gamma|beta conv does too: that conv's epilogue writes the consumer's operand image.  Every other conv runs
+// the plain form of the handle's precision.
+//  * MSR_FLAG_FP8: a conv whose whole tiles fill the chip (B * (r/16)^2 * (N/128) >= 256, no K split).  Its input holds one
+//    byte per channel: 128 channels (one 128-byte chunk) or a multiple of 256 (chunk pairs), in float slots of 4 channels.
+//  * MSR_FLAG_F16C: the same rule, with the K-range launches of the ping-pong kernel (fewer tiles than CUs) taken too: their
+//    split-K epilogue writes the f16c image (MSR_F16C_KSPLIT=0: whole-tile launches only).
+//  * PREC_F16C6 (fp6 cross terms, kernels.h), OPT-IN with MSR_F16C_FP6=1: the f16c consumers that run the stream kernel
+//    (conv_sw.hip: whole tiles, Cin % 128 == 0) behind a whole-tile gamma|beta conv (its LDS-assembled epilogue writes the
+//    fp6 image).  Measured: the consumer gains 6.5 % on those convs, the producer's block-scale and 6-bit packing
+//    cost the gamma|beta epilogues more, net -1 % per call: it pays only once the gamma|beta convs consume fp6 too.  Any
+//    MSR_F16C_SW other than 1 (the A/B dispatches) switches it off.
+//  * conv_gb_resident (conv_gbr.hip) takes a layer whose gamma|beta conv and f16c consumer (not f16c6) run f16c, when the
+//    layer has enough 16 x 16 pixel tiles x channel-block ranges to fill the chip (conv_gbr_ranges; MSR_GBR=0 switches it
+//    off).  Its weights are the f16c6 image with the input channels of every 32-chunk in the kernel's order (gbr_perm).
+//  * MSR_FLAG_GB_F16X2: a gamma|beta conv that runs the ping-pong kernel on whole tiles takes 2-term fp16 products (the
+//    K-split launches run the 3-term form).
+SpadeForm spade_form(const msr_handle* h, int r, int C, int cout, int epi) {
+    static const bool f16c_ks_off = env_int("MSR_F16C_KSPLIT", 1) == 0;
+    static const bool fp6_on = env_int("MSR_F16C_FP6", 0) == 1 && env_int("MSR_F16C_SW", 1) == 1;
+    const int B = h->B;
+    auto fills = [&](int N) { return r >= 16 && N % 128 == 0 && (long)B * (r / 16) * (r / 16) * (N / 128) >= 256; };
+    auto f16c_pp = [&](int N, int cin) { return f16c_ks_off ? fills(N) : pp_ksplit(B, r, N, 1, cin) >= 1; };
+    const bool gb8 = h->fp8 && fills(2 * C), cv8 = gb8 && fills(cout);
+    const bool gbc = h->f16c && f16c_pp(2 * C, 128), cvc = gbc && C % 64 == 0 && f16c_pp(cout, C);
+    const bool cv6 = cvc && fp6_on && C % 128 == 0 && fills(cout) && fills(2 * C);
+    SpadeForm s;
+    s.gbr = cvc && !cv6 && conv_gbr_ranges(B, r, 2 * C) > 0;
+    if (gb8) {
+        s.gb = make_form(PREC_FP8, TILE_256x128_PP, 1);
+    } else if (s.gbr) {
+        s.gb = make_form(PREC_F16C6, TILE_256x128_PP, 1, 0, h->f16m);
+        s.gb.img = IMG_GBR;
+    } else if (gbc) {
+        s.gb = make_form(PREC_F16C, TILE_256x128_PP, pp_ksplit(B, r, 2 * C, 1, 128));   // > 1: K ranges
+    } else {
+        s.gb = conv_form(B, r, 2 * C, 1, EPI_SPADE, h->prec, 128);
+        if (h->gb_f16x2 && s.gb.tile == TILE_256x128_PP && s.gb.ksplit == 1) s.gb = make_form(PREC_F16X2, TILE_256x128_PP, 1);
+    }
+    if (cv8) s.cv = make_form(PREC_FP8, TILE_256x128_PP, 1);
+    else if (cv6) s.cv = make_form(PREC_F16C6, TILE_256x128_PP, 1);
+    else if (cvc) s.cv = make_form(PREC_F16C, TILE_256x128_PP, pp_ksplit(B, r, cout, 1, C), 0, h->f16m);
+    else s.cv = conv_form(B, r, cout, 1, epi, h->prec, C);
+    s.h_split = split_for(s.gb.prec);
+    s.hslots = gb8 ? fp8_pad(128) / 4 : 128;
+    s.a_split = split_for(s.cv.prec);
+    s.aslots = cv8 ? fp8_pad(C) / 4 : C;
+    return s;
+}
+
+// The forms of the SPADE generator's convs, fixed by the handle's batch, size and flags: msr_load_weight builds every
+// weight image from this table and plan_spade launches every layer by it.
+void fill_forms(msr_handle* h) {
+    if (h->variant == MSR_PIX2PIX) return;
+    for (int i = 2; i <= 5; ++i)
+        h->enc_forms[i] = conv_form(h->B, h->S >> i, kEncChannels[i - 1], 2, EPI_BIAS, h->prec, kEncChannels[i - 2]);
+    int cin = 1024;
+    for (int i = 1; i <= 6; ++i) {
+        const int f = kGenFilters[i - 1], r = (h->S / 64) << (i - 1);
+        for (int j = 1; j <= (f != cin ? 3 : 2); ++j)       // spade_2 normalises conv_1's output
+            h->spade_forms[i][j] = spade_form(h, r, j == 2 ? f : cin, f, j == 2 ? EPI_RES : EPI_BIAS);
+        cin = f;
+    }
 }
 
 }  // namespace
@@ -631,7 +741,7 @@ int msr_create(const msr_config* cfg, msr_handle** out) {
                     cfg->device, prop.gcnArchName);
     if (hipSetDevice(cfg->device) != hipSuccess) return fail(nullptr, MSR_ERR_DEVICE, "hipSetDevice failed");
 #ifdef MSR_DIAG_BUILD   // stamp / what-if object (kernels.h): never the product
-    if (!(std::getenv("MSR_ALLOW_DIAG_BUILD") && std::atoi(std::getenv("MSR_ALLOW_DIAG_BUILD")) == 1))
+    if (env_int("MSR_ALLOW_DIAG_BUILD", 0) != 1)
         return fail(nullptr, MSR_ERR_STATE, "this libmoonsr_hip.so is a diagnostic build (-DMSR_DIAG_BUILD: in-kernel stamps "
                     "or what-if switches that change results); set MSR_ALLOW_DIAG_BUILD=1 to use it for measurements");
 #endif
@@ -655,6 +765,7 @@ int msr_create(const msr_config* cfg, msr_handle** out) {
     h->f16m = h->f16c && (cfg->flags & MSR_FLAG_F16_MAIN);
     if (cfg->variant == MSR_PIX2PIX) { h->prec = PREC_F32; h->gb_f16x2 = false; }   // the parity config runs on the fp32 MFMA
     build_specs(h.get());
+    fill_forms(h.get());
     *out = h.release();
     return MSR_OK;
 }
@@ -799,20 +910,9 @@ int msr_load_weight(msr_handle* h, const char* name_c, const float* host, const 
             std::vector<float>& img = h->host_small[base + ".gb.kernel"];
             img.resize((size_t)9 * 2 * C * cin);
             hwio_to_tap_oc_ic(host, img.data(), 9, cin, C, 2 * C, rowmap.data());
-            int rout = 0, stride = 1;
-            weight_conv_shape(h, name, &rout, &stride);
-            int blk = 0, sj = 0;
-            std::sscanf(name.c_str(), "gen.rb%d.spade_%d.", &blk, &sj);
-            const int cout_main = blk >= 1 && blk <= 6 ? kGenFilters[blk - 1] : 0;     // every conv of block i has kGenFilters[i-1] outputs
-            if (gb_uses_fp8(h, rout, C)) rc = upload_conv_weight_fp8(h, base + ".gb.kernel", img.data(), 9, 2 * C, cin);
-            else if (cin == 128 && cout_main && gb_uses_gbr(h, rout, C, cout_main)) {
-                const std::vector<float> ws = gbr_weight_stream(img.data(), 2 * C);
-                rc = upload(h, base + ".gb.kernel", ws.data(), ws.size());
-            }
-            else if (gb_uses_f16c(h, rout, C)) rc = upload_conv_weight_f16c(h, base + ".gb.kernel", img.data(), 9, 2 * C, cin);
-            else
-                rc = upload_conv_weight(h, base + ".gb.kernel", img.data(), img.size(), 9, 2 * C, cin,
-                                        weight_uses_frag(h, name, 2 * C, EPI_SPADE, cin), gb_uses_f16x2(h, rout, 2 * C, cin));
+            int i = 0, j = 0;
+            std::sscanf(name.c_str(), "gen.rb%d.spade_%d.", &i, &j);
+            rc = upload_conv_weight(h, base + ".gb.kernel", img.data(), 9, 2 * C, cin, h->spade_forms[i][j].gb.img);
         }
     } else if (ends_with(name, ".conv_gamma.bias") || ends_with(name, ".conv_beta.bias")) {
         const bool is_beta = ends_with(name, ".conv_beta.bias");
@@ -823,17 +923,15 @@ int msr_load_weight(msr_handle* h, const char* name_c, const float* host, const 
         for (int c = 0; c < C; ++c) img[(c / 32) * 64 + (is_beta ? 32 : 0) + (c % 32)] = host[c];
         rc = upload(h, base + ".gb.bias", img.data(), img.size());
     } else if (ends_with(name, ".kernel")) {
-        // encoder ds2..5 and ResidualBlock conv_1/2/3: HWIO -> [tap][Cout][Cin]
+        // encoder ds2..5 and ResidualBlock conv_1/2/3 (conv_j is fed by spade_j): HWIO -> [tap][Cout][Cin]
         const int taps = (int)(s[0] * s[1]), cin = (int)s[2], cout = (int)s[3];
         std::vector<float> t(count);
         hwio_to_tap_oc_ic(host, t.data(), taps, cin, cout, cout, nullptr);
-        int rout = 0, stride = 1;
-        const bool gen_conv = name.rfind("gen.rb", 0) == 0 && weight_conv_shape(h, name, &rout, &stride);
-        if (gen_conv && main_uses_fp8(h, rout, cin, cout)) rc = upload_conv_weight_fp8(h, name, t.data(), taps, cout, cin);
-        else if (gen_conv && main_uses_f16c6(h, rout, cin, cout)) rc = upload_conv_weight_f16c6(h, name, t.data(), taps, cout, cin);
-        else if (gen_conv && main_uses_f16c(h, rout, cin, cout)) rc = upload_conv_weight_f16c(h, name, t.data(), taps, cout, cin);
-        else
-            rc = upload_conv_weight(h, name, t.data(), count, taps, cout, cin, weight_uses_frag(h, name, cout, EPI_BIAS, cin));
+        int i = 0, j = 0;
+        const bool gen_conv = std::sscanf(name.c_str(), "gen.rb%d.conv_%d.", &i, &j) == 2;
+        if (!gen_conv) std::sscanf(name.c_str(), "enc.ds%d.", &i);
+        const ConvForm& form = gen_conv ? h->spade_forms[i][j].cv : h->enc_forms[i];
+        rc = upload_conv_weight(h, name, t.data(), taps, cout, cin, form.img);
     } else {
         rc = upload(h, name, host, count);
     }
@@ -862,55 +960,11 @@ int alloc_padded(msr_handle* h, const std::string& key, int r, int C, Padded* ou
     return dev_alloc(h, key, (size_t)h->B * (r + 2) * (r + 2) * C, true, &out->base);
 }
 
-// Kernel variant of one conv layer.  Under bf16x3 it also fixes the weight layout, so msr_load_weight and the
-// planner must agree: both call this.
-// K split of the persistent ping-pong kernel for layers with fewer 16 x 16 x 128 tiles than CUs: whole chunk pairs
-// per range, a power of two, as many ranges as it takes to give every CU a work item.  0 = the layer is not one for
-// that kernel (it needs stride 1, r >= 16, Cin % 64 == 0, an input below the 2 GiB buffer-descriptor range and, split
-// or not, at least `min_items` work items — below that the small-tile split-K kernels are faster).
-int pp_ksplit(int B, int rout, int N, int stride, int cin, long min_items = 128);
-int pp_ksplit(int B, int rout, int N, int stride, int cin, long min_items) {
-    static const bool off = std::getenv("MSR_PP_KSPLIT") && std::atoi(std::getenv("MSR_PP_KSPLIT")) == 0;
-    if (stride != 1 || rout < 16 || cin % 64 || N % 128) return 0;
-    if ((size_t)B * (rout + 2) * (rout + 2) * cin * sizeof(float) >= ((size_t)1 << 31)) return 0;
-    const long tiles = (long)B * (rout / 16) * (rout / 16) * (N / 128);
-    if (tiles >= 256) return 1;
-    if (off) return 0;
-    const int pairs = cin / 64;
-    int ks = 1;
-    while (tiles * ks * 2 <= 256 && pairs % (ks * 2) == 0) ks *= 2;
-    return tiles * ks >= min_items ? ks : 0;
-}
-
-ConvVariant pick_conv_variant(int B, int rout, int N, int stride, int epi, int prec, int cin) {
-    ConvVariant v;
-    const int M = B * rout * rout;
-    v.tile = conv_pick_tile(M, N, epi, prec, 9 * (cin / 32));
-    v.wt_frag = 0;
-    v.ksplit = 0;
-    if (prec == PREC_BF16X3) {
-        const long big_blocks = (long)((M + 127) / 128) * (N / 128);
-        const int pks = pp_ksplit(B, rout, N, stride, cin);
-        if (pks >= 1) {
-            // LDS-staged input halo, 512-thread ping-pong form (one persistent workgroup per CU, 16 x 16 pixels x 128
-            // channels per tile): 10-25 % faster than two 256-thread workgroups per CU as soon as it fills the chip
-            // once; with fewer tiles than CUs, K ranges supply the work items (pks > 1).
-            v.tile = TILE_256x128_PP;
-            v.ksplit = pks;
-        } else if (v.tile == TILE_64x64 || big_blocks < 256) {
-            v.wt_frag = 1;   // few workgroups (with split-K): B fragments straight to VGPRs, +18 % on the small tile
-        } else if (stride == 1 && rout >= 16 && cin % 64 == 0 &&
-                   (size_t)B * (rout + 2) * (rout + 2) * cin * sizeof(float) < ((size_t)1 << 31)) {   // raw buffer loads: 2 GiB
-            v.tile = TILE_128x128_HALO16;     // only reached with MSR_PP_KSPLIT=0: two 256-thread workgroups per CU
-            v.ksplit = 1;
-        }
-    }
-    return v;
-}
-
-Op conv_op(const Padded& in, const float* wt, const float* bias, int B, int rout, int N, int stride, int epi,
-           int prec = PREC_F32) {
-    Op op; op.type = OP_CONV; op.epi = epi;
+// A 3x3 conv of `cin` channels (in.C float slots per pixel: fewer for the byte-per-channel fp8 input) in form f.  The
+// output format (out_split) is the caller's: a SPADE output feeds a conv whose form decides it.
+Op conv_op(const Padded& in, int cin, const float* wt, const float* bias, int B, int rout, int N, int stride, int epi,
+           const ConvForm& f) {
+    Op op; op.type = OP_CONV; op.epi = epi; op.tile = f.tile;
     ConvParams& c = op.conv;
     c.in = stride == 1 ? in.base : in.base + in.interior();
     c.wt = wt; c.bias = bias;
@@ -918,14 +972,9 @@ Op conv_op(const Padded& in, const float* wt, const float* bias, int B, int rout
     c.KH = 3; c.KW = 3; c.stride = stride;
     c.in_px = in.C; c.in_py = in.py(); c.in_pb = in.pb();
     c.slope = 0.2f;
-    c.prec = prec;
-    c.out_split = (epi == EPI_SPADE && prec == PREC_BF16X3) ? 1 : 0;   // a SPADE output always feeds a conv
-    const ConvVariant cv = pick_conv_variant(B, rout, N, stride, epi, prec, in.C);
-    op.tile = cv.tile;
-    c.wt_frag = cv.wt_frag;
-    c.ksplit = cv.ksplit > 0 ? cv.ksplit : conv_pick_ksplit(B * rout * rout, N, 9 * (in.C / 32), op.tile, prec);
+    c.prec = f.prec; c.ksplit = f.ksplit; c.wt_frag = f.wt_frag; c.no_cross = f.no_cross;
     c.partial = nullptr;   // bound to the handle's workspace at launch
-    op.flops = 2.0 * B * rout * rout * (double)in.C * N * 9;
+    op.flops = 2.0 * B * rout * rout * (double)cin * N * 9;
     return op;
 }
 
@@ -950,7 +999,7 @@ Op moments_op(const float* x, int G, int P, int C, float eps, float* mean, float
 bool fuse_moments_into_splitk(Op& cv, int G, float eps, float* mean, float* stdv) {
     if (cv.type != OP_CONV || cv.conv.ksplit <= 1 || (cv.epi != EPI_BIAS && cv.epi != EPI_RES) || cv.conv.N % 32)
         return false;
-    static const bool off = std::getenv("MSR_FUSE_MOMENTS") && std::atoi(std::getenv("MSR_FUSE_MOMENTS")) == 0;
+    static const bool off = env_int("MSR_FUSE_MOMENTS", 1) == 0;
     if (off) return false;
     cv.conv.mom_mean = mean; cv.conv.mom_std = stdv; cv.conv.mom_eps = eps; cv.conv.mom_G = G;
     return true;
@@ -989,7 +1038,7 @@ int plan_spade(msr_handle* h) {
         snprintf(n, sizeof n, "ws.enc.std%d", i); rc = dev_alloc(h, n, (size_t)B * c, false, &stdv); if (rc) return rc;
         float* zero_bias; rc = dev_alloc(h, "ws.zero_bias", 2048, true, &zero_bias); if (rc) return rc;
         snprintf(n, sizeof n, "enc.ds%d.kernel", i);
-        Op cv = conv_op(e_in, need(n), zero_bias, B, r, c, 2, EPI_BIAS, h->prec);
+        Op cv = conv_op(e_in, e_in.C, need(n), zero_bias, B, r, c, 2, EPI_BIAS, h->enc_forms[i]);
         set_out_dense(cv.conv, raw, r, c);
         const bool fused = fuse_moments_into_splitk(cv, B, 1e-3f, mean, stdv);
         h->ops.push_back(cv);
@@ -1059,21 +1108,20 @@ int plan_spade(msr_handle* h) {
         snprintf(n, sizeof n, "ws.gen.rb%d.stdo", i); rc = dev_alloc(h, n, f, false, &so); if (rc) return rc;
         if (learned) { snprintf(n, sizeof n, "ws.gen.rb%d.skip", i); rc = dev_alloc(h, n, (size_t)B * r * r * f, false, &skip); if (rc) return rc; }
 
-        // one SPADE layer + its consumer conv:  a = lrelu(SPADE(x)) ; y = conv(a)
-        auto spade_then_conv = [&](int j, const float* x, int rx, int xshift, int C, const float* mean,
-                                   const float* stdv, int conv_idx, float* y, int epi, const float* res, int res_r,
-                                   int res_shift, bool want_stats) -> int {
+        // one SPADE layer + its consumer conv:  a = lrelu(SPADE(x)) ; y = conv_j(a), both in the forms of the handle's table
+        auto spade_then_conv = [&](int j, const float* x, int rx, int xshift, int C, const float* mean, const float* stdv,
+                                   float* y, int epi, const float* res, int res_r, int res_shift, bool want_stats) -> int {
+            const SpadeForm& sf = h->spade_forms[i][j];
             char k[160];
+            // the per-channel scales that go with the fp8 / f16c weight images
+            auto wexp = [&](const char* key, const ConvForm& cf) -> const int* {
+                if (cf.img != IMG_FP8 && cf.img != IMG_F16C) return nullptr;
+                return reinterpret_cast<const int*>(need(std::string(key) + ".wexp"));
+            };
             Padded hb, ab;
-            // MSR_FLAG_FP8: tensors that feed an fp8 conv hold one byte per channel, padded to 256 channels; the kernels
-            // address them in float slots of 4 channels
-            const bool gb8 = gb_uses_fp8(h, r, C), cv8 = main_uses_fp8(h, r, C, f);
-            const bool gbc = gb_uses_f16c(h, r, C), cvc = main_uses_f16c(h, r, C, f), cv6 = main_uses_f16c6(h, r, C, f);
-            const int hslots = gb8 ? fp8_pad(128) / 4 : 128, aslots = cv8 ? fp8_pad(C) / 4 : C;
-            const bool gbr = gb_uses_gbr(h, r, C, f);
             int rc2;
-            snprintf(k, sizeof k, "ws.gen.rb%d.a%d", i, j); rc2 = alloc_padded(h, k, r, aslots, &ab); if (rc2) return rc2;
-            if (gbr) {
+            snprintf(k, sizeof k, "ws.gen.rb%d.a%d", i, j); rc2 = alloc_padded(h, k, r, sf.aslots, &ab); if (rc2) return rc2;
+            if (sf.gbr) {
                 // conv_gb_resident: the embedding never exists in HBM (no mask-embedding launch, no h buffer); one launch
                 // does resize + embedding + gamma|beta conv + SPADE epilogue and writes the consumer's f16c image
                 Op g; g.type = OP_GBR; g.src_is_input = true;
@@ -1087,86 +1135,44 @@ int plan_spade(msr_handle* h) {
                 q.aux = x; q.aux_px = C; q.aux_py = rx * C; q.aux_pb = rx * rx * C; q.aux_shift = xshift;
                 q.mean = mean; q.stdv = stdv;
                 q.out = ab.base; q.out_px = ab.C; q.out_py = ab.py(); q.out_pb = ab.pb(); q.out_off = ab.interior();
-                q.out_split = 4; q.slope = 0.2f;
+                q.out_split = sf.a_split; q.slope = 0.2f;
                 q.B = B; q.r = r; q.N = 2 * C;
-                q.no_cross = h->f16m ? 1 : 0;
+                q.no_cross = sf.gb.no_cross;
                 g.flops = 2.0 * B * r * r * 128.0 * (2 * C) * 9 + 2.0 * B * r * r * 18.0 * 128;
                 h->ops.push_back(g);
             } else {
-            snprintf(k, sizeof k, "ws.gen.rb%d.h%d", i, j); rc2 = alloc_padded(h, k, r, hslots, &hb); if (rc2) return rc2;
-            Op em; em.type = OP_SMALLCIN; em.src_is_input = true;
-            SmallCinParams& p = em.sc;
-            snprintf(k, sizeof k, "gen.rb%d.spade_%d.conv.kernel", i, j); p.w = need(k);
-            snprintf(k, sizeof k, "gen.rb%d.spade_%d.conv.bias", i, j); p.bias = need(k);
-            p.out = hb.base; p.B = B; p.S = S; p.Hout = r; p.Cout = 128;
-            p.ay = 1; p.cy = -1; p.lim = r; p.f = S / r; p.o = (S / r) / 2;
-            p.out_px = hslots; p.out_py = hb.py(); p.out_pb = hb.pb(); p.out_off = hb.interior();
-            p.act = 1; p.slope = 0.f;
-            const bool f16x2 = gb_uses_f16x2(h, r, 2 * C, 128);
-            p.out_split = gb8 ? 3 : gbc ? 4 : f16x2 ? 2 : (h->prec == PREC_BF16X3 ? 1 : 0);
-            em.flops = 2.0 * B * r * r * 18.0 * 128;
-            em.on_aux = true;
-            em.aux_group = i <= 4 ? 0 : 1;        // rb1-4 embeds are small and done early; rb5-6 carry the bytes
-            if (hipEventCreateWithFlags(&em.done, hipEventDisableTiming) != hipSuccess)
-                return fail(h, MSR_ERR_DEVICE, "hipEventCreate failed");
-            h->ops.push_back(em);
-            snprintf(k, sizeof k, "gen.rb%d.spade_%d.gb.kernel", i, j); const float* gbw = need(k);
-            snprintf(k, sizeof k, "gen.rb%d.spade_%d.gb.bias", i, j); const float* gbb = need(k);
-            Op gb = conv_op(hb, gbw, gbb, B, r, 2 * C, 1, EPI_SPADE, h->prec);
-            if (f16x2) gb.conv.prec = PREC_F16X2;     // same tile, same layouts; fp16 encodings, 2 MFMAs per product
-            if (gb8) {
-                snprintf(k, sizeof k, "gen.rb%d.spade_%d.gb.kernel.wexp", i, j);
-                gb.conv.prec = PREC_FP8;
-                gb.conv.wexp = reinterpret_cast<const int*>(need(k));
-                gb.flops = 2.0 * B * r * r * 128.0 * (2 * C) * 9;
-                gb.tile = TILE_256x128_PP;            // gb_uses_fp8 checked that it fills the chip with whole tiles
-                gb.conv.ksplit = 1;
-                gb.conv.wt_frag = 0;
+                snprintf(k, sizeof k, "ws.gen.rb%d.h%d", i, j); rc2 = alloc_padded(h, k, r, sf.hslots, &hb); if (rc2) return rc2;
+                Op em; em.type = OP_SMALLCIN; em.src_is_input = true;
+                SmallCinParams& p = em.sc;
+                snprintf(k, sizeof k, "gen.rb%d.spade_%d.conv.kernel", i, j); p.w = need(k);
+                snprintf(k, sizeof k, "gen.rb%d.spade_%d.conv.bias", i, j); p.bias = need(k);
+                p.out = hb.base; p.B = B; p.S = S; p.Hout = r; p.Cout = 128;
+                p.ay = 1; p.cy = -1; p.lim = r; p.f = S / r; p.o = (S / r) / 2;
+                p.out_px = sf.hslots; p.out_py = hb.py(); p.out_pb = hb.pb(); p.out_off = hb.interior();
+                p.act = 1; p.slope = 0.f;
+                p.out_split = sf.h_split;
+                em.flops = 2.0 * B * r * r * 18.0 * 128;
+                em.on_aux = true;
+                em.aux_group = i <= 4 ? 0 : 1;        // rb1-4 embeds are small and done early; rb5-6 carry the bytes
+                if (hipEventCreateWithFlags(&em.done, hipEventDisableTiming) != hipSuccess)
+                    return fail(h, MSR_ERR_DEVICE, "hipEventCreate failed");
+                h->ops.push_back(em);
+                snprintf(k, sizeof k, "gen.rb%d.spade_%d.gb.bias", i, j); const float* gbb = need(k);
+                snprintf(k, sizeof k, "gen.rb%d.spade_%d.gb.kernel", i, j);
+                Op gb = conv_op(hb, 128, need(k), gbb, B, r, 2 * C, 1, EPI_SPADE, sf.gb);
+                gb.conv.wexp = wexp(k, sf.gb);
+                gb.conv.out_split = sf.a_split;
+                set_out_padded(gb.conv, ab);
+                set_aux_dense(gb.conv, x, rx, C, xshift);
+                gb.conv.mean = mean; gb.conv.stdv = stdv;
+                gb.wait = em.done;
+                gb.aux_group = em.aux_group;
+                h->ops.push_back(gb);
             }
-            if (gbc) {
-                snprintf(k, sizeof k, "gen.rb%d.spade_%d.gb.kernel.wexp", i, j);
-                gb.conv.prec = PREC_F16C;
-                gb.conv.wexp = reinterpret_cast<const int*>(need(k));
-                gb.tile = TILE_256x128_PP;
-                gb.conv.ksplit = pp_ksplit(B, r, 2 * C, 1, 128);      // > 1: K ranges (fewer tiles than CUs)
-                gb.conv.wt_frag = 0;
-            }
-            if (cv8) gb.conv.out_split = 3;           // its epilogue writes bf8 bytes for the fp8 consumer
-            if (cvc) gb.conv.out_split = cv6 ? 5 : 4; // ... the f16c (fp8 pieces) / f16c6 (fp6 pieces) chunk image for the consumer
-            set_out_padded(gb.conv, ab);
-            set_aux_dense(gb.conv, x, rx, C, xshift);
-            gb.conv.mean = mean; gb.conv.stdv = stdv;
-            gb.wait = em.done;
-            gb.aux_group = em.aux_group;
-            h->ops.push_back(gb);
-            }
-            snprintf(k, sizeof k, "gen.rb%d.conv_%d.kernel", i, conv_idx); const float* cw = need(k);
-            snprintf(k, sizeof k, "gen.rb%d.conv_%d.bias", i, conv_idx); const float* cb = need(k);
-            Op cv = conv_op(ab, cw, cb, B, r, f, 1, epi, h->prec);
-            if (cv8) {
-                snprintf(k, sizeof k, "gen.rb%d.conv_%d.kernel.wexp", i, conv_idx);
-                cv.conv.prec = PREC_FP8;
-                cv.conv.wexp = reinterpret_cast<const int*>(need(k));
-                cv.flops = 2.0 * B * r * r * (double)C * f * 9;
-                cv.tile = TILE_256x128_PP;
-                cv.conv.ksplit = 1;
-                cv.conv.wt_frag = 0;
-            }
-            if (cv6) {
-                cv.conv.prec = PREC_F16C6;                    // the weight image carries its scales
-                cv.conv.wexp = nullptr;
-                cv.tile = TILE_256x128_PP;
-                cv.conv.ksplit = 1;
-                cv.conv.wt_frag = 0;
-            } else if (cvc) {
-                snprintf(k, sizeof k, "gen.rb%d.conv_%d.kernel.wexp", i, conv_idx);
-                cv.conv.prec = PREC_F16C;
-                cv.conv.wexp = reinterpret_cast<const int*>(need(k));
-                cv.tile = TILE_256x128_PP;
-                cv.conv.ksplit = pp_ksplit(B, r, f, 1, C);
-                cv.conv.wt_frag = 0;
-                cv.conv.no_cross = h->f16m ? 1 : 0;           // honoured by conv_igemm_f16c_sw (the long-K main convs)
-            }
+            snprintf(k, sizeof k, "gen.rb%d.conv_%d.bias", i, j); const float* cb = need(k);
+            snprintf(k, sizeof k, "gen.rb%d.conv_%d.kernel", i, j);
+            Op cv = conv_op(ab, C, need(k), cb, B, r, f, 1, epi, sf.cv);
+            cv.conv.wexp = wexp(k, sf.cv);
             set_out_dense(cv.conv, y, r, f);
             if (epi == EPI_RES) set_aux_dense(cv.conv, res, res_r, f, res_shift);
             // fused output moments (the tensor feeds a SPADE layer) unless the layer runs split-K
@@ -1189,16 +1195,16 @@ int plan_spade(msr_handle* h) {
             }
         };
         // x1 = conv_1(lrelu(spade_1(x)))                                   blocks.py:29-30
-        rc = spade_then_conv(1, x_prev, r_prev, shift, cin, st_mean, st_std, 1, x1, EPI_BIAS, nullptr, 0, 0, true); if (rc) return rc;
+        rc = spade_then_conv(1, x_prev, r_prev, shift, cin, st_mean, st_std, x1, EPI_BIAS, nullptr, 0, 0, true); if (rc) return rc;
         push_moments(x1, B * r * r, f, m1, s1);
         if (learned) {
             // skip = conv_3(lrelu(spade_3(x)))                             blocks.py:33-34
-            rc = spade_then_conv(3, x_prev, r_prev, shift, cin, st_mean, st_std, 3, skip, EPI_BIAS, nullptr, 0, 0, false); if (rc) return rc;
+            rc = spade_then_conv(3, x_prev, r_prev, shift, cin, st_mean, st_std, skip, EPI_BIAS, nullptr, 0, 0, false); if (rc) return rc;
             // out = skip + conv_2(lrelu(spade_2(x1)))                      blocks.py:31-32,38
-            rc = spade_then_conv(2, x1, r, 0, f, m1, s1, 2, outb, EPI_RES, skip, r, 0, true); if (rc) return rc;
+            rc = spade_then_conv(2, x1, r, 0, f, m1, s1, outb, EPI_RES, skip, r, 0, true); if (rc) return rc;
         } else {
             // out = x + conv_2(lrelu(spade_2(x1))), x read through the folded up-sample
-            rc = spade_then_conv(2, x1, r, 0, f, m1, s1, 2, outb, EPI_RES, x_prev, r_prev, shift, true); if (rc) return rc;
+            rc = spade_then_conv(2, x1, r, 0, f, m1, s1, outb, EPI_RES, x_prev, r_prev, shift, true); if (rc) return rc;
         }
         // moments of the block output == moments of its nearest-2x up-sample (every value is repeated 4x)
         push_moments(outb, B * r * r, f, mo, so);
@@ -1272,9 +1278,10 @@ int plan_pix2pix(msr_handle* h) {
         c.in = in; c.wt = wt; c.bias = shift; c.scale = scale; c.act = act; c.slope = slope;
         c.B = B; c.Hout = rout; c.Wout = rout; c.Cin = cin; c.N = N; c.KH = K; c.KW = K; c.stride = stride;
         c.in_px = in_px; c.in_py = in_py; c.in_pb = in_pb;
-        c.prec = PREC_F32;
-        op.tile = conv_pick_tile(B * rout * rout, N, EPI_AFFINE, PREC_F32);
-        c.ksplit = conv_pick_ksplit(B * rout * rout, N, K * K * (cin / 32), op.tile);
+        const ConvForm f = conv_form(B, rout, N, stride, EPI_AFFINE, PREC_F32, cin, K * K);
+        c.prec = f.prec;
+        op.tile = f.tile;
+        c.ksplit = f.ksplit;
         op.flops = 2.0 * B * rout * rout * (double)cin * N * K * K;
         return op;
     };
@@ -1671,7 +1678,7 @@ static int op_conv_impl(msr_handle* h, const float* in_dev, const float* wt_dev,
         return fail(h, MSR_ERR_INVALID, "msr_op_conv3x3: epilogue %d needs aux / mean / std", epilogue);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     Padded in; in.base = const_cast<float*>(in_dev); in.r = rout * stride; in.C = Cin;
-    Op op = conv_op(in, wt_dev, bias_dev, B, rout, N, stride, epilogue, prec);
+    Op op = conv_op(in, Cin, wt_dev, bias_dev, B, rout, N, stride, epilogue, conv_form(B, rout, N, stride, epilogue, prec, Cin));
     op.conv.out_split = (epilogue == EPI_SPADE && out_split) ? 1 : 0;
     const int Cout = epilogue == EPI_SPADE ? N / 2 : N;
     if (out_padded) { Padded o; o.base = out_dev; o.r = rout; o.C = Cout; set_out_padded(op.conv, o); }
@@ -1728,11 +1735,8 @@ int msr_op_conv3x3_f16c(msr_handle* h, const float* in_dev, const float* wt_dev,
         return fail(h, MSR_ERR_INVALID, "msr_op_conv3x3_f16c: bad epilogue / output mode");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     Padded in; in.base = const_cast<float*>(in_dev); in.r = rout; in.C = Cin;
-    Op op = conv_op(in, wt_dev, bias_dev, B, rout, N, 1, epilogue, PREC_BF16X3);
-    op.tile = TILE_256x128_PP;
-    op.conv.ksplit = 1;
-    op.conv.wt_frag = 0;
-    op.conv.prec = wexp_dev ? PREC_F16C : PREC_F16C6;
+    Op op = conv_op(in, Cin, wt_dev, bias_dev, B, rout, N, 1, epilogue,
+                    make_form(wexp_dev ? PREC_F16C : PREC_F16C6, TILE_256x128_PP, 1));
     op.conv.wexp = wexp_dev;
     op.conv.out_split = epilogue == EPI_SPADE ? out_mode : 0;
     const int Cout = epilogue == EPI_SPADE ? N / 2 : N;
@@ -1832,11 +1836,8 @@ int msr_op_conv3x3_fp8(msr_handle* h, const void* in_dev, const void* wt_dev, co
         return fail(h, MSR_ERR_INVALID, "msr_op_conv3x3_fp8: bad epilogue / output mode");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     Padded in; in.base = const_cast<float*>(static_cast<const float*>(in_dev)); in.r = rout; in.C = Cpad / 4;
-    Op op = conv_op(in, static_cast<const float*>(wt_dev), bias_dev, B, rout, N, 1, epilogue, PREC_BF16X3);
-    op.tile = TILE_256x128_PP;
-    op.conv.ksplit = 1;
-    op.conv.wt_frag = 0;
-    op.conv.prec = PREC_FP8;
+    Op op = conv_op(in, Cpad, static_cast<const float*>(wt_dev), bias_dev, B, rout, N, 1, epilogue,
+                    make_form(PREC_FP8, TILE_256x128_PP, 1));
     op.conv.wexp = wexp_dev;
     op.conv.out_split = epilogue == EPI_SPADE ? out_mode : 0;
     const int Cout = epilogue == EPI_SPADE ? N / 2 : N;

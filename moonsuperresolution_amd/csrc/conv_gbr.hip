@@ -620,7 +620,7 @@ hipError_t conv_gbr_init() {
 // Work decomposition: a work item = one 16 x 16 pixel tile x `nr` channel blocks; the N / 128 blocks of a pixel tile are cut
 // into the fewest ranges (a power of two) that give every CU an item.  Returns 0 if the layer is not one for this kernel.
 int conv_gbr_ranges(int B, int r, int N) {
-    static const bool off = std::getenv("MSR_GBR") && std::atoi(std::getenv("MSR_GBR")) == 0;
+    static const bool off = env_int("MSR_GBR", 1) == 0;
     if (off || r < 16 || (r & (r - 1)) || N % 128) return 0;
     const int tiles_p = B * (r / 16) * (r / 16), tiles_n = N / 128;
     int ranges = 1;

@@ -71,7 +71,7 @@ struct TileGeom {
 };
 
 void conv_walk_pick(int tiles_m, int tiles_n, int* walk_pb, int* walk_nb) {
-    static const bool off = std::getenv("MSR_TILE_WALK") && std::atoi(std::getenv("MSR_TILE_WALK")) == 0;
+    static const bool off = env_int("MSR_TILE_WALK", 1) == 0;
     *walk_pb = 1;
     *walk_nb = tiles_n;
     if (!off && tiles_n > 4 && tiles_n % 4 == 0 && tiles_m % 8 == 0) { *walk_pb = 8; *walk_nb = 4; }
@@ -2056,6 +2056,21 @@ static hipError_t launch_halo(const ConvParams& p, int epi, int sh, hipStream_t 
     return hipGetLastError();
 }
 
+// One launch of the ping-pong kernel's MODE form for a runtime epilogue (the f16c SPADE epilogue assembles its stores in
+// LDS behind the tile buffers: PP_STAGE_LDS more).
+template <int MODE, bool ONE = false>
+static hipError_t launch_pp_epi(const ConvParams& p, const TileGeom& g, int epi, int grid, hipStream_t s) {
+    switch (epi) {
+        case EPI_BIAS: conv_igemm_bf16x3_pp<EPI_BIAS, MODE, ONE><<<grid, 512, PP_LDS, s>>>(p, g); break;
+        case EPI_RES: conv_igemm_bf16x3_pp<EPI_RES, MODE, ONE><<<grid, 512, PP_LDS, s>>>(p, g); break;
+        case EPI_SPADE:
+            conv_igemm_bf16x3_pp<EPI_SPADE, MODE, ONE><<<grid, 512, MODE == PP_F16C ? PP_LDS + PP_STAGE_LDS : PP_LDS, s>>>(p, g);
+            break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
 static hipError_t launch_pp(const ConvParams& p, int epi, hipStream_t s) {
     TileGeom g;
     if (!make_geom(p, 256, 128, 32, g)) return hipErrorInvalidValue;
@@ -2106,44 +2121,17 @@ static hipError_t launch_pp(const ConvParams& p, int epi, hipStream_t s) {
         if (!p.wexp) return hipErrorInvalidValue;
         // conv_sw.hip (one software-pipelined wave per SIMD) takes the long-K main convs; the gamma|beta convs stay here, where
         // a second wave on the SIMD hides their SPADE epilogue.  MSR_F16C_SW = 0: everything here, 2: everything there (A/B).
-        static const int sw_mode = std::getenv("MSR_F16C_SW") ? std::atoi(std::getenv("MSR_F16C_SW")) : 1;
+        static const int sw_mode = env_int("MSR_F16C_SW", 1);
         if (p.Cin % 128 == 0 && !(epi == EPI_SPADE && p.out_split == 5) &&     // (the fp6 image is written by this kernel's epilogue only)
             (sw_mode == 2 || (sw_mode == 1 && epi != EPI_SPADE)))
             return launch_conv_f16c_sw(p, epi, s);
-        switch (epi) {
-            case EPI_BIAS: conv_igemm_bf16x3_pp<EPI_BIAS, PP_F16C><<<grid, 512, PP_LDS, s>>>(p, g); break;
-            case EPI_RES: conv_igemm_bf16x3_pp<EPI_RES, PP_F16C><<<grid, 512, PP_LDS, s>>>(p, g); break;
-            case EPI_SPADE: conv_igemm_bf16x3_pp<EPI_SPADE, PP_F16C><<<grid, 512, PP_LDS + PP_STAGE_LDS, s>>>(p, g); break;
-            default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
+        return launch_pp_epi<PP_F16C>(p, g, epi, grid, s);
     }
     if (p.prec == PREC_FP8) {
         if (!p.wexp) return hipErrorInvalidValue;
-        if (one) {
-            switch (epi) {
-                case EPI_BIAS: conv_igemm_bf16x3_pp<EPI_BIAS, PP_FP8, true><<<grid, 512, PP_LDS, s>>>(p, g); break;
-                case EPI_RES: conv_igemm_bf16x3_pp<EPI_RES, PP_FP8, true><<<grid, 512, PP_LDS, s>>>(p, g); break;
-                case EPI_SPADE: conv_igemm_bf16x3_pp<EPI_SPADE, PP_FP8, true><<<grid, 512, PP_LDS, s>>>(p, g); break;
-                default: return hipErrorInvalidValue;
-            }
-            return hipGetLastError();
-        }
-        switch (epi) {
-            case EPI_BIAS: conv_igemm_bf16x3_pp<EPI_BIAS, PP_FP8><<<grid, 512, PP_LDS, s>>>(p, g); break;
-            case EPI_RES: conv_igemm_bf16x3_pp<EPI_RES, PP_FP8><<<grid, 512, PP_LDS, s>>>(p, g); break;
-            case EPI_SPADE: conv_igemm_bf16x3_pp<EPI_SPADE, PP_FP8><<<grid, 512, PP_LDS, s>>>(p, g); break;
-            default: return hipErrorInvalidValue;
-        }
-        return hipGetLastError();
+        return one ? launch_pp_epi<PP_FP8, true>(p, g, epi, grid, s) : launch_pp_epi<PP_FP8>(p, g, epi, grid, s);
     }
-    switch (epi) {
-        case EPI_BIAS: conv_igemm_bf16x3_pp<EPI_BIAS, PP_BF16X3><<<grid, 512, PP_LDS, s>>>(p, g); break;
-        case EPI_RES: conv_igemm_bf16x3_pp<EPI_RES, PP_BF16X3><<<grid, 512, PP_LDS, s>>>(p, g); break;
-        case EPI_SPADE: conv_igemm_bf16x3_pp<EPI_SPADE, PP_BF16X3><<<grid, 512, PP_LDS, s>>>(p, g); break;
-        default: return hipErrorInvalidValue;
-    }
-    return hipGetLastError();
+    return launch_pp_epi<PP_BF16X3>(p, g, epi, grid, s);
 }
 
 hipError_t launch_conv_igemm(const ConvParams& p, int epilogue, int tile, hipStream_t s) {

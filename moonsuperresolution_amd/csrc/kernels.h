@@ -3,6 +3,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <cstdint>
+#include <cstdlib>
 
 // Diagnostic switches (in-kernel s_memtime stamps; what-if builds that compute WRONG results on purpose to price one
 // cost: SW_NOBAR, SW_NOEPI, MSR_WI_ONESTORE, MSR_WI_NOSTORE) compile only into a library that declares itself a
@@ -16,6 +17,13 @@
 #endif
 
 namespace msr {
+
+// Integer value of an environment switch (std::atoi of its text), `unset` when it is not set.  Callers keep the result in
+// a static const, so every switch is read once per process.
+inline int env_int(const char* name, int unset) {
+    const char* v = std::getenv(name);
+    return v ? std::atoi(v) : unset;
+}
 
 // ---------------------------------------------------------------------------------------------
 // conv_igemm_f32: NHWC implicit-GEMM convolution on v_mfma_f32_32x32x2_f32 (exact fp32).
