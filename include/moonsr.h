@@ -88,7 +88,7 @@ typedef struct {
  *                     conv_igemm_f16c_sw): ONE fp16 product per element on v_mfma_f32_16x16x32_f16, fp32 accumulation,
  *                     per-product error 2^-11.  Tensors, weights and every other layer are exactly F16C's.  It is the usable
  *                     reading of BASELINE.json configs[4] ("fp16 ... conv"): the measured end-to-end error is stated in
- *                     tests/test_gpu_baseline_configs.py::test_f16_mode_declared_tolerance (bound 3e-2 relative L-inf; it is
+ *                     tests/test_gpu_baseline_configs.py::test_f16_mode_declared_tolerance (bound 3e-3 relative L-inf; it is
  *                     NOT inside north_star's 1e-3 and never the default). */
 #define MSR_FLAG_F16_MAIN 16
 
@@ -272,7 +272,14 @@ int msr_op_conv3x3_bf16x3(msr_handle* h, const float* in_dev, const float* wt_de
                           const float* std_dev, int32_t out_padded, int32_t out_split, int32_t tile, void* stream);
 /* Kernel-level entry of the f16c form (MSR_FLAG_F16C) of the persistent ping-pong conv: in_dev / wt_dev hold f16c chunk
  * images (moonsuperresolution_amd.ops.f16c_activation_image / f16c_weight_image restate the format), wexp_dev [N] =
- * (127 + e_lo) | (127 + e_hi) << 8; out_mode (SPADE epilogue) 0 = fp32, 1 = split-bf16 words, 4 = f16c image. */
+ * (127 + e_lo) | (127 + e_hi) << 8; out_mode (SPADE epilogue) 0 = fp32, 1 = split-bf16 words, 4 = f16c image, 5 = f16c6 image,
+ * plus in its high bits:
+ *   + 256 * ksplit   K ranges (ksplit a power of two dividing Cin / 64; 0 or 1 = whole tiles): the ping-pong kernel writes raw
+ *                    accumulators to the handle's split-K workspace and a second pass applies the epilogue (out_mode 0, 1, 4),
+ *                    as the planner launches layers with fewer tiles than CUs
+ *   + 0x10000        no cross terms (MSR_FLAG_F16_MAIN's form: x_hi * w_hi only) on the stream kernel; whole tiles, bias /
+ *                    residual epilogue, Cin % 128 == 0, power-of-two rout only
+ * Anything else is MSR_ERR_INVALID. */
 int msr_op_conv3x3_f16c(msr_handle* h, const float* in_dev, const float* wt_dev, const int32_t* wexp_dev,
                         const float* bias_dev, float* out_dev, int32_t B, int32_t rout, int32_t Cin, int32_t N,
                         int32_t epilogue, const float* aux_dev, int32_t aux_shift, const float* mean_dev,
@@ -287,10 +294,41 @@ int msr_op_conv3x3_f16c(msr_handle* h, const float* in_dev, const float* wt_dev,
  *            re-ordered into [channel block][wave][tap pair][column block][piece][lane] x 16 bytes (csrc/conv_gbr.hip)
  *   bias_dev [N] in column order; aux_dev = x [B, r >> aux_shift, r >> aux_shift, N / 2]; mean_dev / std_dev [N / 2]
  *   out_dev  zero-bordered [B, r + 2, r + 2, N / 2] float slots, the interior is written
- * Needs r >= 32 (a power of two) and N % 128 == 0; MSR_ERR_INVALID otherwise. */
+ * Needs r >= 16 (a power of two) and N % 128 == 0; MSR_ERR_INVALID otherwise. */
 int msr_op_spade_gbr(msr_handle* h, const float* src_dev, int32_t S, const float* we_dev, const float* be_dev,
                      const float* wt_dev, const float* bias_dev, float* out_dev, int32_t B, int32_t r, int32_t N,
                      const float* aux_dev, int32_t aux_shift, const float* mean_dev, const float* std_dev, void* stream);
+/* msr_op_spade_gbr in MSR_FLAG_F16_MAIN's form: the gamma|beta products are the fp16 main term alone (the fp6 cross pieces of
+ * wt_dev are not read); the embedding (phase 1) is computed as in msr_op_spade_gbr.  Same arguments and checks. */
+int msr_op_spade_gbr_f16(msr_handle* h, const float* src_dev, int32_t S, const float* we_dev, const float* be_dev,
+                         const float* wt_dev, const float* bias_dev, float* out_dev, int32_t B, int32_t r, int32_t N,
+                         const float* aux_dev, int32_t aux_shift, const float* mean_dev, const float* std_dev, void* stream);
+/* Kernel-level entry of conv_smallcin (csrc/small_kernels.hip): a 3 x 3 conv of the 2-channel source through an index map, in
+ * the planner's kernel choice (tiled for Hout % 16 == 0 with >= 64 tiles, else 4 or 1 pixels per thread).
+ *   src_dev   [B, S, S, 2];  w_dev HWIO [3, 3, 2, Cout] (Cout 64 | 128);  bias_dev [Cout] or NULL
+ *   map       0 = encoder block 1, stride-2 SAME (S = 2 Hout);  1 = SPADE mask embedding: nearest resize of src to Hout x Hout
+ *             (S a multiple of Hout), then a SAME conv
+ *   act       0 none, 1 relu, 2 leaky_relu(slope)
+ *   out_split 0 fp32 [.., Cout], 1 split-bf16 words, 2 split-fp16 words, 3 bf8 bytes (Cout channels in 128 bytes per pixel:
+ *             32 float slots), 4 f16c chunk image;  out_padded != 0: out_dev is zero-bordered [B, Hout + 2, Hout + 2, slots]
+ * Asynchronous on `stream`. */
+int msr_op_conv_smallcin(msr_handle* h, const float* src_dev, int32_t S, const float* w_dev, const float* bias_dev,
+                         float* out_dev, int32_t B, int32_t Hout, int32_t Cout, int32_t map, int32_t act, float slope,
+                         int32_t out_split, int32_t out_padded, void* stream);
+/* Kernel-level entry of norm_act: out = leaky_relu((x - mean[b]) / std[b] * gamma + beta, slope) (blocks.py:62-65).
+ *   x_dev dense [B, H, W, C] (C % 4 == 0);  mean_dev / std_dev [B, C];  gamma_dev / beta_dev [C]
+ *   out_padded != 0: zero-bordered [B, H + 2, W + 2, C];  out_split 1: split-bf16 words (C % 32 == 0).  Asynchronous. */
+int msr_op_norm_act(msr_handle* h, const float* x_dev, const float* mean_dev, const float* std_dev, const float* gamma_dev,
+                    const float* beta_dev, float* out_dev, int32_t B, int32_t H, int32_t W, int32_t C, float slope,
+                    int32_t out_padded, int32_t out_split, void* stream);
+/* Kernel-level entry of the dense layer, synchronous: y [B, N] = x [B, K] . W [K, N] (+ bias [N], or NULL), 1 <= B <= 16,
+ * N % 4 == 0; K split and final pass as the planner launches them (the entry allocates the split-K workspace). */
+int msr_op_dense(msr_handle* h, const float* x_dev, const float* w_dev, const float* bias_dev, float* y_dev, int32_t B,
+                 int32_t K, int32_t N, void* stream);
+/* Kernel-level entry of the latent sampler: mv_dev [B, 2L] = (mean | variance);  z_dev [B, L] = mean + exp(variance / 2) * eps
+ * (sampler 1, eps_dev [B, L]) or mean + variance (sampler 0, eps_dev ignored).  Asynchronous. */
+int msr_op_latent(msr_handle* h, const float* mv_dev, const float* eps_dev, float* z_dev, int32_t B, int32_t L,
+                  int32_t sampler, void* stream);
 /* Kernel-level entry of the head kernel (csrc/small_kernels.hip head_kernel), synchronous:
  *   variant 0: leaky_relu(slope) -> UpSampling2D(2) -> Conv2D(1, 4, 'same') (networks.py:54-56), kernel_host = HWIO [4,4,C,1];
  *   variant 1: Conv2DTranspose(1, 4, strides 2, 'same') -> tanh (pix2pix.py:53-57; pass slope = 1), kernel_host = [4,4,1,C]

@@ -1722,40 +1722,60 @@ int msr_op_conv3x3_bf16x3(msr_handle* h, const float* in_dev, const float* wt_de
 int msr_op_conv3x3_f16c(msr_handle* h, const float* in_dev, const float* wt_dev, const int32_t* wexp_dev,
                         const float* bias_dev, float* out_dev, int32_t B, int32_t rout, int32_t Cin, int32_t N,
                         int32_t epilogue, const float* aux_dev, int32_t aux_shift, const float* mean_dev,
-                        const float* std_dev, int32_t out_padded, int32_t out_mode, void* stream) {
+                        const float* std_dev, int32_t out_padded, int32_t out_mode_bits, void* stream) {
     if (!h) return MSR_ERR_INVALID;
+    // out_mode_bits = out_mode | 256 * ksplit | 0x10000 (no cross terms)
+    const int out_mode = out_mode_bits & 0xFF, ksplit = (out_mode_bits >> 8) & 0xFF, no_cross = (out_mode_bits >> 16) & 1;
+    if (out_mode_bits < 0 || (out_mode_bits >> 17))
+        return fail(h, MSR_ERR_INVALID, "msr_op_conv3x3_f16c: unknown bits in out_mode 0x%x", out_mode_bits);
     if (!in_dev || !wt_dev || !bias_dev || !out_dev || B < 1 || rout < 16 || Cin % 64 || N % 128)
         return fail(h, MSR_ERR_INVALID, "msr_op_conv3x3_f16c: bad argument (Cin %% 64, N %% 128, rout >= 16)");
     // wexp_dev == nullptr: the operands are f16c6 images (fp6 pieces, scales inside; stream kernel, bias / residual epilogues)
-    if (!wexp_dev && (epilogue == EPI_SPADE || Cin % 128))
-        return fail(h, MSR_ERR_INVALID, "msr_op_conv3x3_f16c: the f16c6 form takes the bias / residual epilogues and Cin %% 128 == 0");
+    if (!wexp_dev && (epilogue == EPI_SPADE || Cin % 128 || ksplit > 1 || no_cross))
+        return fail(h, MSR_ERR_INVALID, "msr_op_conv3x3_f16c: the f16c6 form takes whole-tile bias / residual launches and Cin %% 128 == 0");
     if (epilogue < EPI_BIAS || epilogue > EPI_SPADE || (epilogue != EPI_BIAS && !aux_dev) ||
         (epilogue == EPI_SPADE && (!mean_dev || !std_dev)) || (out_mode != 0 && out_mode != 1 && out_mode != 4 && out_mode != 5) ||
         (out_mode != 0 && epilogue != EPI_SPADE))
         return fail(h, MSR_ERR_INVALID, "msr_op_conv3x3_f16c: bad epilogue / output mode");
+    // K ranges: whole chunk pairs per range (launch_pp); the split-K epilogue writes fp32, split-bf16 or the f16c image
+    if (ksplit > 1 && ((ksplit & (ksplit - 1)) || (Cin / 64) % ksplit || out_mode == 5))
+        return fail(h, MSR_ERR_INVALID, "msr_op_conv3x3_f16c: ksplit %d must be a power of two dividing Cin / 64 = %d (out_mode 0, 1, 4)",
+                    ksplit, Cin / 64);
+    // no cross terms: the stream kernel's form only (whole tiles, bias / residual, Cin % 128 == 0, power-of-two rout)
+    if (no_cross && (ksplit > 1 || epilogue == EPI_SPADE || Cin % 128 || (rout & (rout - 1))))
+        return fail(h, MSR_ERR_INVALID, "msr_op_conv3x3_f16c: no-cross takes whole-tile bias / residual launches with Cin %% 128 == 0");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     Padded in; in.base = const_cast<float*>(in_dev); in.r = rout; in.C = Cin;
     Op op = conv_op(in, Cin, wt_dev, bias_dev, B, rout, N, 1, epilogue,
-                    make_form(wexp_dev ? PREC_F16C : PREC_F16C6, TILE_256x128_PP, 1));
+                    make_form(wexp_dev ? PREC_F16C : PREC_F16C6, TILE_256x128_PP, ksplit > 1 ? ksplit : 1, 0, no_cross));
     op.conv.wexp = wexp_dev;
     op.conv.out_split = epilogue == EPI_SPADE ? out_mode : 0;
+    if (op.conv.ksplit > 1) {
+        int rc = ensure_conv_partial(h, (size_t)op.conv.ksplit * B * rout * rout * N);
+        if (rc) return rc;
+        op.conv.partial = h->conv_partial;
+    }
     const int Cout = epilogue == EPI_SPADE ? N / 2 : N;
     if (out_padded) { Padded o; o.base = out_dev; o.r = rout; o.C = Cout; set_out_padded(op.conv, o); }
     else set_out_dense(op.conv, out_dev, rout, Cout);
     if (epilogue != EPI_BIAS) set_aux_dense(op.conv, aux_dev, rout >> aux_shift, Cout, aux_shift);
     op.conv.mean = mean_dev; op.conv.stdv = std_dev;
-    hipError_t e = launch_conv_igemm(op.conv, epilogue, op.tile, (hipStream_t)stream);
+    // no-cross goes to the stream kernel directly: launch_pp's MSR_F16C_SW = 0 would send it to the ping-pong kernel, which has
+    // no such form and would silently compute the cross terms
+    hipError_t e = no_cross ? launch_conv_f16c_sw(op.conv, epilogue, (hipStream_t)stream)
+                            : launch_conv_igemm(op.conv, epilogue, op.tile, (hipStream_t)stream);
     if (e != hipSuccess) return fail(h, MSR_ERR_INVALID, "f16c conv launch rejected: %s", hipGetErrorString(e));
     return MSR_OK;
 }
 
-int msr_op_spade_gbr(msr_handle* h, const float* src_dev, int32_t S, const float* we_dev, const float* be_dev,
-                     const float* wt_dev, const float* bias_dev, float* out_dev, int32_t B, int32_t r, int32_t N,
-                     const float* aux_dev, int32_t aux_shift, const float* mean_dev, const float* std_dev, void* stream) {
+static int op_spade_gbr_impl(msr_handle* h, const float* src_dev, int32_t S, const float* we_dev, const float* be_dev,
+                             const float* wt_dev, const float* bias_dev, float* out_dev, int32_t B, int32_t r, int32_t N,
+                             const float* aux_dev, int32_t aux_shift, const float* mean_dev, const float* std_dev, int no_cross,
+                             void* stream) {
     if (!h) return MSR_ERR_INVALID;
     if (!src_dev || !we_dev || !be_dev || !wt_dev || !bias_dev || !out_dev || !aux_dev || !mean_dev || !std_dev || B < 1 ||
-        r < 16 || S < r || S % r || N % 128 || aux_shift < 0 || aux_shift > 1)
-        return fail(h, MSR_ERR_INVALID, "msr_op_spade_gbr: bad argument (r >= 16, S a multiple of r, N %% 128 == 0)");
+        r < 16 || (r & (r - 1)) || S < r || S % r || N % 128 || aux_shift < 0 || aux_shift > 1)
+        return fail(h, MSR_ERR_INVALID, "msr_op_spade_gbr: bad argument (r >= 16 a power of two, S a multiple of r, N %% 128 == 0)");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     const int C = N / 2, rx = r >> aux_shift;
     GbrParams q{};
@@ -1765,7 +1785,7 @@ int msr_op_spade_gbr(msr_handle* h, const float* src_dev, int32_t S, const float
     q.mean = mean_dev; q.stdv = std_dev;
     Padded o; o.base = out_dev; o.r = r; o.C = C;
     q.out = o.base; q.out_px = C; q.out_py = o.py(); q.out_pb = o.pb(); q.out_off = o.interior();
-    q.out_split = 4; q.slope = 0.2f; q.B = B; q.r = r; q.N = N;
+    q.out_split = 4; q.slope = 0.2f; q.B = B; q.r = r; q.N = N; q.no_cross = no_cross;
     int ranges = conv_gbr_ranges(B, r, N);       // the planner's split; a layer it would not take runs one item per pixel tile
     if (ranges < 1) ranges = 1;
     // the embedding kernel as fp16 MFMA operands (msr_load_weight builds this image once per layer; this test entry per call)
@@ -1781,6 +1801,93 @@ int msr_op_spade_gbr(msr_handle* h, const float* src_dev, int32_t S, const float
     if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
     hipFree(e16_dev);
     if (e != hipSuccess) return fail(h, MSR_ERR_INVALID, "conv_gb_resident launch rejected: %s", hipGetErrorString(e));
+    return MSR_OK;
+}
+
+int msr_op_spade_gbr(msr_handle* h, const float* src_dev, int32_t S, const float* we_dev, const float* be_dev,
+                     const float* wt_dev, const float* bias_dev, float* out_dev, int32_t B, int32_t r, int32_t N,
+                     const float* aux_dev, int32_t aux_shift, const float* mean_dev, const float* std_dev, void* stream) {
+    return op_spade_gbr_impl(h, src_dev, S, we_dev, be_dev, wt_dev, bias_dev, out_dev, B, r, N, aux_dev, aux_shift, mean_dev,
+                             std_dev, 0, stream);
+}
+
+int msr_op_spade_gbr_f16(msr_handle* h, const float* src_dev, int32_t S, const float* we_dev, const float* be_dev,
+                         const float* wt_dev, const float* bias_dev, float* out_dev, int32_t B, int32_t r, int32_t N,
+                         const float* aux_dev, int32_t aux_shift, const float* mean_dev, const float* std_dev, void* stream) {
+    return op_spade_gbr_impl(h, src_dev, S, we_dev, be_dev, wt_dev, bias_dev, out_dev, B, r, N, aux_dev, aux_shift, mean_dev,
+                             std_dev, 1, stream);
+}
+
+int msr_op_conv_smallcin(msr_handle* h, const float* src_dev, int32_t S, const float* w_dev, const float* bias_dev,
+                         float* out_dev, int32_t B, int32_t Hout, int32_t Cout, int32_t map, int32_t act, float slope,
+                         int32_t out_split, int32_t out_padded, void* stream) {
+    if (!h) return MSR_ERR_INVALID;
+    // the kernel reads any out_split outside 2, 3, 4 as split-bf16: only the five formats the planner writes are accepted
+    if (!src_dev || !w_dev || !out_dev || B < 1 || Hout < 1 || (Cout != 64 && Cout != 128) || map < 0 || map > 1 || act < 0 ||
+        act > 2 || out_split < 0 || out_split > 4 || out_padded < 0 || out_padded > 1 ||
+        (map == 0 && S != 2 * Hout) || (map == 1 && (S < Hout || S % Hout)))
+        return fail(h, MSR_ERR_INVALID, "msr_op_conv_smallcin: bad argument (Cout 64 | 128, map 0: S = 2 Hout, map 1: S a "
+                    "multiple of Hout, act 0..2, out_split 0..4)");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    SmallCinParams p{};
+    p.src = src_dev; p.w = w_dev; p.bias = bias_dev; p.out = out_dev;
+    p.B = B; p.S = S; p.Hout = Hout; p.Cout = Cout;
+    if (map == 0) { p.ay = 2; p.cy = 0; p.lim = S; p.f = 1; p.o = 0; }                       // encoder ds1: stride-2 SAME
+    else { p.ay = 1; p.cy = -1; p.lim = Hout; p.f = S / Hout; p.o = (S / Hout) / 2; }       // SPADE mask embedding
+    const int slots = out_split == 3 ? fp8_pad(Cout) / 4 : Cout;       // bf8: one byte per channel, padded to 128
+    Padded o; o.base = out_dev; o.r = Hout; o.C = slots;
+    p.out_px = slots;
+    if (out_padded) { p.out_py = o.py(); p.out_pb = o.pb(); p.out_off = o.interior(); }
+    else { p.out_py = Hout * slots; p.out_pb = Hout * Hout * slots; p.out_off = 0; }
+    p.act = act; p.slope = slope; p.out_split = out_split;
+    hipError_t e = launch_conv_smallcin(p, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(h, MSR_ERR_INVALID, "conv_smallcin launch rejected: %s", hipGetErrorString(e));
+    return MSR_OK;
+}
+
+int msr_op_norm_act(msr_handle* h, const float* x_dev, const float* mean_dev, const float* std_dev, const float* gamma_dev,
+                    const float* beta_dev, float* out_dev, int32_t B, int32_t H, int32_t W, int32_t C, float slope,
+                    int32_t out_padded, int32_t out_split, void* stream) {
+    if (!h) return MSR_ERR_INVALID;
+    if (!x_dev || !mean_dev || !std_dev || !gamma_dev || !beta_dev || !out_dev || B < 1 || H < 1 || W < 1 || C < 4 || C % 4 ||
+        out_padded < 0 || out_padded > 1 || out_split < 0 || out_split > 1 || (out_split && C % 32))
+        return fail(h, MSR_ERR_INVALID, "msr_op_norm_act: bad argument (C a multiple of 4, of 32 for split output; "
+                    "out_padded, out_split 0 | 1)");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    NormActParams p{};
+    p.x = x_dev; p.mean = mean_dev; p.stdv = std_dev; p.gamma = gamma_dev; p.beta = beta_dev; p.out = out_dev;
+    p.B = B; p.H = H; p.W = W; p.C = C; p.slope = slope; p.out_split = out_split;
+    p.out_px = C;
+    if (out_padded) { p.out_py = (W + 2) * C; p.out_pb = (H + 2) * (W + 2) * C; p.out_off = p.out_py + C; }
+    else { p.out_py = W * C; p.out_pb = H * W * C; p.out_off = 0; }
+    hipError_t e = launch_norm_act(p, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(h, MSR_ERR_INVALID, "norm_act launch rejected: %s", hipGetErrorString(e));
+    return MSR_OK;
+}
+
+int msr_op_dense(msr_handle* h, const float* x_dev, const float* w_dev, const float* bias_dev, float* y_dev, int32_t B,
+                 int32_t K, int32_t N, void* stream) {
+    if (!h) return MSR_ERR_INVALID;
+    if (!x_dev || !w_dev || !y_dev || B < 1 || B > 16 || K < 1 || N < 4 || N % 4 || (long)B * N >= (1L << 31))
+        return fail(h, MSR_ERR_INVALID, "msr_op_dense: bad argument (1 <= B <= 16, K >= 1, N a multiple of 4)");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    float* partial = nullptr;
+    HIPCHK(h, hipMalloc(&partial, dense_partial_floats(B, K, N) * sizeof(float)));
+    hipError_t e = launch_dense(x_dev, w_dev, bias_dev, partial, y_dev, B, K, N, (hipStream_t)stream);
+    if (e == hipSuccess) e = hipStreamSynchronize((hipStream_t)stream);
+    hipFree(partial);
+    if (e != hipSuccess) return fail(h, MSR_ERR_DEVICE, "msr_op_dense failed: %s", hipGetErrorString(e));
+    return MSR_OK;
+}
+
+int msr_op_latent(msr_handle* h, const float* mv_dev, const float* eps_dev, float* z_dev, int32_t B, int32_t L,
+                  int32_t sampler, void* stream) {
+    if (!h) return MSR_ERR_INVALID;
+    if (!mv_dev || !z_dev || B < 1 || L < 1 || sampler < 0 || sampler > 1 || (sampler && !eps_dev) || (long)B * L >= (1L << 31))
+        return fail(h, MSR_ERR_INVALID, "msr_op_latent: bad argument (sampler 0 | 1, eps needed by sampler 1)");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    hipError_t e = launch_latent(mv_dev, eps_dev, z_dev, B, L, sampler, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(h, MSR_ERR_INVALID, "latent launch rejected: %s", hipGetErrorString(e));
     return MSR_OK;
 }
 

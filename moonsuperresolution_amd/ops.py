@@ -320,12 +320,17 @@ def f16c6_decode(img: torch.Tensor):
     return hi, piece(64), piece(96)
 
 
+F16C_NO_CROSS = 0x10000     # msr_op_conv3x3_f16c out_mode bit: MSR_FLAG_F16_MAIN's form (x_hi * w_hi only, stream kernel)
+
+
 def conv3x3_f16c(ctx: OpContext, x_img: torch.Tensor, w_img: torch.Tensor, wexp: torch.Tensor, bias: torch.Tensor, rout: int,
                  epilogue: int = EPI_BIAS, aux: Optional[torch.Tensor] = None, aux_shift: int = 0,
                  mean: Optional[torch.Tensor] = None, std: Optional[torch.Tensor] = None, out_padded: bool = False,
-                 out_mode: int = 0) -> torch.Tensor:
+                 out_mode: int = 0, ksplit: int = 1, no_cross: bool = False) -> torch.Tensor:
     """One launch of the f16c conv (msr_op_conv3x3_f16c; the library sends it to the ping-pong or the stream kernel).
-    ``wexp=None``: the operands are f16c6 images (fp6 pieces, stream kernel)."""
+    ``wexp=None``: the operands are f16c6 images (fp6 pieces, stream kernel).  ``ksplit`` > 1: K ranges of the ping-pong kernel
+    + the split-K epilogue pass (the planner's form for layers with fewer tiles than CUs); ``no_cross``: the cross terms left
+    out (the f16 mode's stream kernel)."""
     B, Cin = x_img.shape[0], x_img.shape[3]
     N = w_img.shape[1]
     Cout = N // 2 if epilogue == EPI_SPADE else N
@@ -334,7 +339,8 @@ def conv3x3_f16c(ctx: OpContext, x_img: torch.Tensor, w_img: torch.Tensor, wexp:
     p = lambda t: t.data_ptr() if t is not None else None   # noqa: E731
     rc = ctx.lib.msr_op_conv3x3_f16c(ctx.h, x_img.data_ptr(), w_img.data_ptr(), p(wexp), bias.data_ptr(),
                                      out.data_ptr(), B, rout, Cin, N, epilogue, p(aux), aux_shift, p(mean), p(std),
-                                     1 if out_padded else 0, out_mode, torch.cuda.current_stream(x_img.device).cuda_stream)
+                                     1 if out_padded else 0, out_mode | 256 * ksplit | (F16C_NO_CROSS if no_cross else 0),
+                                     torch.cuda.current_stream(x_img.device).cuda_stream)
     _lib.raise_for(ctx.lib, ctx.h, rc, "msr_op_conv3x3_f16c")
     return out
 
@@ -365,17 +371,73 @@ def gbr_weight_image(w_kl: torch.Tensor) -> torch.Tensor:
 
 
 def spade_gbr(ctx: OpContext, src: torch.Tensor, we: torch.Tensor, be: torch.Tensor, w_img: torch.Tensor, bias: torch.Tensor,
-              r: int, x: torch.Tensor, aux_shift: int, mean: torch.Tensor, std: torch.Tensor) -> torch.Tensor:
-    """One launch of conv_gb_resident (msr_op_spade_gbr): resize + mask embedding + gamma|beta conv + SPADE epilogue;
-    returns the zero-bordered f16c image [B, r + 2, r + 2, C] (float32 storage; f16c_decode reads it)."""
+              r: int, x: torch.Tensor, aux_shift: int, mean: torch.Tensor, std: torch.Tensor, no_cross: bool = False) -> torch.Tensor:
+    """One launch of conv_gb_resident (msr_op_spade_gbr; ``no_cross``: msr_op_spade_gbr_f16, the f16 mode's form): resize +
+    mask embedding + gamma|beta conv + SPADE epilogue; returns the zero-bordered f16c image [B, r + 2, r + 2, C] (float32
+    storage; f16c_decode reads it)."""
     B, S = src.shape[0], src.shape[1]
     N = w_img.shape[1]
     out = torch.zeros((B, r + 2, r + 2, N // 2), dtype=torch.float32, device=src.device)
-    rc = ctx.lib.msr_op_spade_gbr(ctx.h, src.data_ptr(), S, we.data_ptr(), be.data_ptr(), w_img.data_ptr(), bias.data_ptr(),
-                                  out.data_ptr(), B, r, N, x.data_ptr(), aux_shift, mean.data_ptr(), std.data_ptr(),
-                                  torch.cuda.current_stream(src.device).cuda_stream)
+    fn = ctx.lib.msr_op_spade_gbr_f16 if no_cross else ctx.lib.msr_op_spade_gbr
+    rc = fn(ctx.h, src.data_ptr(), S, we.data_ptr(), be.data_ptr(), w_img.data_ptr(), bias.data_ptr(), out.data_ptr(), B, r, N,
+            x.data_ptr(), aux_shift, mean.data_ptr(), std.data_ptr(), torch.cuda.current_stream(src.device).cuda_stream)
     _lib.raise_for(ctx.lib, ctx.h, rc, "msr_op_spade_gbr")
     return out
+
+
+SMALLCIN_STRIDE2, SMALLCIN_EMBED = 0, 1     # msr_op_conv_smallcin index maps: encoder block 1 / SPADE mask embedding
+
+
+def conv_smallcin(ctx: OpContext, src: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor], hout: int, index_map: int,
+                  act: int = 0, slope: float = 0.0, out_split: int = 0, out_padded: bool = False) -> torch.Tensor:
+    """One launch of conv_smallcin (msr_op_conv_smallcin): src [B, S, S, 2], w HWIO [3, 3, 2, Cout].  Returns float32 storage
+    [B, hout (+2), hout (+2), slots] with slots = Cout, or 32 for bf8 bytes (out_split 3); a padded output starts zeroed."""
+    B, S, Cout = src.shape[0], src.shape[1], w.shape[3]
+    slots = 32 if out_split == 3 else Cout
+    shape = (B, hout + 2, hout + 2, slots) if out_padded else (B, hout, hout, slots)
+    out = torch.zeros(shape, dtype=torch.float32, device=src.device)
+    rc = ctx.lib.msr_op_conv_smallcin(ctx.h, src.contiguous().data_ptr(), S, w.contiguous().data_ptr(),
+                                      bias.data_ptr() if bias is not None else None, out.data_ptr(), B, hout, Cout, index_map,
+                                      act, float(slope), out_split, 1 if out_padded else 0,
+                                      torch.cuda.current_stream(src.device).cuda_stream)
+    _lib.raise_for(ctx.lib, ctx.h, rc, "msr_op_conv_smallcin")
+    return out
+
+
+def norm_act(ctx: OpContext, x: torch.Tensor, mean: torch.Tensor, std: torch.Tensor, gamma: torch.Tensor, beta: torch.Tensor,
+             slope: float = 0.2, out_padded: bool = False, out_split: bool = False) -> torch.Tensor:
+    """One launch of norm_act (msr_op_norm_act): x dense [B, H, W, C], mean / std [B, C], gamma / beta [C]."""
+    B, H, W, Cc = x.shape
+    shape = (B, H + 2, W + 2, Cc) if out_padded else (B, H, W, Cc)
+    out = torch.zeros(shape, dtype=torch.float32, device=x.device)
+    rc = ctx.lib.msr_op_norm_act(ctx.h, x.contiguous().data_ptr(), mean.contiguous().data_ptr(), std.contiguous().data_ptr(),
+                                 gamma.contiguous().data_ptr(), beta.contiguous().data_ptr(), out.data_ptr(), B, H, W, Cc,
+                                 float(slope), 1 if out_padded else 0, 1 if out_split else 0,
+                                 torch.cuda.current_stream(x.device).cuda_stream)
+    _lib.raise_for(ctx.lib, ctx.h, rc, "msr_op_norm_act")
+    return out
+
+
+def dense(ctx: OpContext, x: torch.Tensor, w: torch.Tensor, bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One dense layer (msr_op_dense, synchronous): x [B, K] (B <= 16), w [K, N] -> [B, N]."""
+    B, K = x.shape
+    N = w.shape[1]
+    y = torch.empty((B, N), dtype=torch.float32, device=x.device)
+    rc = ctx.lib.msr_op_dense(ctx.h, x.contiguous().data_ptr(), w.contiguous().data_ptr(),
+                              bias.data_ptr() if bias is not None else None, y.data_ptr(), B, K, N,
+                              torch.cuda.current_stream(x.device).cuda_stream)
+    _lib.raise_for(ctx.lib, ctx.h, rc, "msr_op_dense")
+    return y
+
+
+def latent(ctx: OpContext, mv: torch.Tensor, eps: Optional[torch.Tensor], sampler: int) -> torch.Tensor:
+    """The latent sampler (msr_op_latent): mv [B, 2L] -> z [B, L] = m + exp(v / 2) * eps (sampler 1) or m + v (sampler 0)."""
+    B, L = mv.shape[0], mv.shape[1] // 2
+    z = torch.empty((B, L), dtype=torch.float32, device=mv.device)
+    rc = ctx.lib.msr_op_latent(ctx.h, mv.contiguous().data_ptr(), eps.contiguous().data_ptr() if eps is not None else None,
+                               z.data_ptr(), B, L, sampler, torch.cuda.current_stream(mv.device).cuda_stream)
+    _lib.raise_for(ctx.lib, ctx.h, rc, "msr_op_latent")
+    return z
 
 
 def f16c_decode(img: torch.Tensor):

@@ -39,3 +39,25 @@ def synthetic_raster(h, w, seed=0, hole=None, no_value=-32768.0):
         y0, y1, x0, x1 = hole
         dem[y0:y1, x0:x1] = no_value
     return img, dem
+
+
+def smallcin_ref(src, w, bias, hout, index_map, act=0, slope=0.0):
+    """float64 CPU restatement of conv_smallcin: src [B,S,S,2] -> [B,hout,hout,Cout].  index_map 0: Conv2D(3, strides=2,
+    'same') on S = 2 hout (TF pads 0 before, 1 after); 1: tf.image.resize(nearest, half-pixel centres) to hout x hout, then
+    Conv2D(3, 'same'); act 1 relu, 2 leaky_relu(slope)."""
+    import torch
+    import torch.nn.functional as F
+    x = src.double().cpu()
+    S = x.shape[1]
+    if index_map == 1:
+        f = S // hout
+        x = x[:, f // 2::f, f // 2::f][:, :hout, :hout]
+    xn = x.permute(0, 3, 1, 2)
+    xn = F.pad(xn, (0, 1, 0, 1)) if index_map == 0 else F.pad(xn, (1, 1, 1, 1))
+    b = bias.double().cpu() if bias is not None else None
+    y = F.conv2d(xn, w.double().cpu().permute(3, 2, 0, 1), b, stride=2 if index_map == 0 else 1).permute(0, 2, 3, 1)
+    if act == 1:
+        y = torch.relu(y)
+    elif act == 2:
+        y = torch.where(y >= 0, y, slope * y)
+    return y

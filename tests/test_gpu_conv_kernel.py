@@ -304,32 +304,118 @@ def _ref_f16c(xparts, wparts, bias, cin, cout):
     return (ref_conv(xh, hwio(wh), bias, 1) + ref_conv(x8, hwio(wl), zero, 1) + ref_conv(xl, hwio(w8), zero, 1))
 
 
-@pytest.mark.parametrize("B,r,cin,cout", [(2, 16, 64, 128), (1, 32, 256, 256), (3, 64, 128, 128), (9, 32, 128, 512)])
-def test_conv_f16c(ctx, B, r, cin, cout):
+@pytest.mark.parametrize("B,r,cin,cout,ks,res", [
+    pytest.param(2, 16, 64, 128, 1, None, id="2-16-64-128"), pytest.param(1, 32, 256, 256, 1, None, id="1-32-256-256"),
+    pytest.param(3, 64, 128, 128, 1, None, id="3-64-128-128"), pytest.param(9, 32, 128, 512, 1, None, id="9-32-128-512"),
+    (8, 16, 1024, 1024, 4, None),     # K ranges: the planner's pick for rb2 conv_1 at S = 512, B = 8 (32 tiles x 4 ranges)
+    (8, 16, 1024, 1024, 4, 1),        # ... rb2 conv_2: residual read through the folded 2x up-sample
+    (1, 16, 512, 256, 8, 0),          # eight ranges of one chunk pair each, residual at full resolution
+    (3, 16, 256, 128, 2, None)])      # two ranges, odd batch
+def test_conv_f16c(ctx, B, r, cin, cout, ks, res):
     """fp16 main term + fp8 cross terms (MSR_FLAG_F16C): against the float64 evaluation of exactly those three terms on the
     de-quantised operands the kernel is exact up to accumulation (<= 5e-5: pins the chunk image, the pairing of the
     pieces of two taps in one 128-deep MFMA and the per-lane scales); against the float64 conv of the ORIGINAL operands it
-    holds 2e-4 at kernel level (per-product error ~2^-15; weights spanning three decades)."""
+    holds 2e-4 at kernel level (per-product error ~2^-15; weights spanning three decades).  ks > 1: the K-range form of the
+    ping-pong kernel (conv_igemm_bf16x3_pp<EPI_PARTIAL, PP_F16C>, whole chunk pairs per range) + the split-K epilogue pass,
+    which the planner launches for every f16c layer with fewer 16 x 16 x 128 tiles than CUs; same bounds.  res = the residual
+    epilogue's aux_shift (None: bias)."""
     from moonsuperresolution_amd import ops
-    g = torch.Generator(device="cpu").manual_seed(51 + B + r)
+    g = torch.Generator(device="cpu").manual_seed(51 + B + r + (7 * ks if ks > 1 else 0))
     x = torch.randn((B, r, r, cin), generator=g).cuda()
     w = (torch.randn((3, 3, cin, cout), generator=g) / np.sqrt(9 * cin) * torch.logspace(-2, 1, cout)).cuda()
     b = torch.randn(cout, generator=g).cuda()
+    skip = torch.randn((B, r >> res, r >> res, cout), generator=g).cuda() if res is not None else None
     ximg, xparts = ops.f16c_activation_image(ops.pad_nhwc(x))
     wimg, wexp, wparts = ops.f16c_weight_image(ops.kernel_layout(w))
-    y = ops.conv3x3_f16c(ctx, ximg, wimg, wexp, b, r).cpu().numpy()
+    y = ops.conv3x3_f16c(ctx, ximg, wimg, wexp, b, r, epilogue=ops.EPI_BIAS if res is None else ops.EPI_RES, aux=skip,
+                         aux_shift=res or 0, ksplit=ks).cpu().numpy()
+    torch.set_num_threads(16)
     xin = tuple(t[:, 1:-1, 1:-1].cpu() for t in xparts)
-    emu = _ref_f16c(xin, tuple(t.cpu() for t in wparts), b, cin, cout).numpy()
-    e_emu, e_true = rel_linf(y, emu), rel_linf(y, ref_conv(x, w, b, 1).numpy())
-    print("f16c conv: vs its own three terms in fp64", e_emu, " vs the fp64 conv", e_true)
+    emu = _ref_f16c(xin, tuple(t.cpu() for t in wparts), b, cin, cout)
+    true = ref_conv(x, w, b, 1)
+    if res is not None:
+        up = skip.double().cpu().repeat_interleave(1 << res, 1).repeat_interleave(1 << res, 2)
+        emu, true = emu + up, true + up
+    e_emu, e_true = rel_linf(y, emu.numpy()), rel_linf(y, true.numpy())
+    print(f"f16c conv ks={ks} res={res}: vs its own three terms in fp64 {e_emu:.3e}, vs the fp64 conv {e_true:.3e}")
     assert e_emu <= 5e-5, e_emu
     assert e_true <= 2e-4, e_true
 
 
-def test_conv_f16c_spade_epilogue_writes_the_chunk_image(ctx):
+def test_f16c_entry_rejects_forms_without_a_kernel(ctx):
+    """msr_op_conv3x3_f16c's K-range and no-cross bits are validated before anything runs: a K split must be a power of two
+    that divides Cin / 64 (whole chunk pairs per range); no-cross exists on the stream kernel only (whole tiles, bias /
+    residual, Cin % 128 == 0) and is refused elsewhere instead of silently computing the cross terms."""
     from moonsuperresolution_amd import ops
-    g = torch.Generator(device="cpu").manual_seed(53)
-    B, r, C, shift = 3, 32, 128, 1
+    x = torch.zeros((1, 18, 18, 256), device="cuda")
+    w = torch.zeros((9, 128, 256), device="cuda")
+    wexp = torch.full((128,), 127 | (127 << 8), dtype=torch.int32, device="cuda")
+    b = torch.zeros(128, device="cuda")
+    for ks in (3, 8, 16):            # 256 / 64 = 4 chunk pairs: 3 is not a power of two, 8 and 16 do not divide 4
+        with pytest.raises(ValueError):
+            ops.conv3x3_f16c(ctx, x, w, wexp, b, 16, ksplit=ks)
+    with pytest.raises(ValueError):  # no cross terms with K ranges
+        ops.conv3x3_f16c(ctx, x, w, wexp, b, 16, ksplit=2, no_cross=True)
+    xs = torch.zeros((1, 18, 18, 64), device="cuda")
+    with pytest.raises(ValueError):  # Cin % 128 != 0: not a stream-kernel shape
+        ops.conv3x3_f16c(ctx, xs, torch.zeros((9, 128, 64), device="cuda"), wexp, b, 16, no_cross=True)
+    m = torch.zeros(64, device="cuda")
+    with pytest.raises(ValueError):  # the SPADE epilogue has no no-cross form
+        ops.conv3x3_f16c(ctx, x, w, wexp, b, 16, epilogue=ops.EPI_SPADE, aux=torch.zeros((1, 16, 16, 64), device="cuda"),
+                         mean=m, std=m + 1, out_padded=True, no_cross=True)
+    with pytest.raises(ValueError):  # the split-K epilogue does not write the fp6 image
+        ops.conv3x3_f16c(ctx, x, w, wexp, b, 16, epilogue=ops.EPI_SPADE, aux=torch.zeros((1, 16, 16, 64), device="cuda"),
+                         mean=m, std=m + 1, out_padded=True, out_mode=5, ksplit=2)
+
+
+@pytest.mark.parametrize("B,r,cin,cout,res", [(2, 32, 128, 128, None), (1, 32, 256, 256, 0), (3, 16, 128, 128, 1)])
+def test_conv_f16c_no_cross(ctx, B, r, cin, cout, res):
+    """The f16 mode's stream kernel (conv_igemm_f16c_sw<EPI, false, true>, MSR_FLAG_F16_MAIN): one fp16 product per element.
+    Against the float64 conv of the fp16 parts alone (x_hi * w_hi, + bias / residual) it is exact up to accumulation
+    (<= 5e-5); against the true conv it holds 2e-3 (per-product error 2^-11) and is WORSE than the f16c kernel on the same
+    operands: the cross terms are really left out, as the mode declares."""
+    from moonsuperresolution_amd import ops
+    g = torch.Generator(device="cpu").manual_seed(71 + B + r + cin)
+    x = torch.randn((B, r, r, cin), generator=g).cuda()
+    w = (torch.randn((3, 3, cin, cout), generator=g) / np.sqrt(9 * cin) * torch.logspace(-2, 1, cout)).cuda()
+    b = torch.randn(cout, generator=g).cuda()
+    skip = torch.randn((B, r >> res, r >> res, cout), generator=g).cuda() if res is not None else None
+    ximg, (xh, _, _) = ops.f16c_activation_image(ops.pad_nhwc(x))
+    wimg, wexp, (wh, _, _) = ops.f16c_weight_image(ops.kernel_layout(w))
+    kw = dict(epilogue=ops.EPI_BIAS if res is None else ops.EPI_RES, aux=skip, aux_shift=res or 0)
+    y16 = ops.conv3x3_f16c(ctx, ximg, wimg, wexp, b, r, no_cross=True, **kw).cpu().numpy()
+    yc = ops.conv3x3_f16c(ctx, ximg, wimg, wexp, b, r, **kw).cpu().numpy()
+    hi_only = ref_conv(xh[:, 1:-1, 1:-1].cpu(), wh.cpu().permute(0, 2, 1).reshape(3, 3, cin, cout), b, 1)
+    true = ref_conv(x, w, b, 1)
+    if res is not None:
+        up = skip.double().cpu().repeat_interleave(1 << res, 1).repeat_interleave(1 << res, 2)
+        hi_only, true = hi_only + up, true + up
+    e_hi, e_true, e_f16c = rel_linf(y16, hi_only.numpy()), rel_linf(y16, true.numpy()), rel_linf(yc, true.numpy())
+    print(f"f16 no-cross conv res={res}: vs fp64 x_hi*w_hi {e_hi:.3e}, vs the fp64 conv {e_true:.3e} (f16c: {e_f16c:.3e})")
+    assert e_hi <= 5e-5, e_hi
+    assert e_true <= 2e-3, e_true
+    assert e_true > e_f16c, (e_true, e_f16c)
+
+
+def test_conv_f16c_spade_epilogue_writes_the_chunk_image(ctx):
+    _check_f16c_spade(ctx, 3, 32, 128, 1, 1, 53)
+
+
+@pytest.mark.parametrize("B,r,C,shift,ks", [
+    (8, 16, 1024, 1, 2),      # the gamma|beta conv of rb2 at S = 512, B = 8 (N = 2048, Cin = 128: 2 ranges of one chunk pair)
+    (2, 16, 256, 0, 2)])      # ... with x at full resolution
+def test_conv_f16c_spade_epilogue_k_ranges(ctx, B, r, C, shift, ks):
+    """The planner's K-range form of an f16c gamma|beta conv: ping-pong K ranges + the split-K SPADE pass, same checks."""
+    _check_f16c_spade(ctx, B, r, C, shift, ks, 53 + B + C)
+
+
+def _check_f16c_spade(ctx, B, r, C, shift, ks, seed):
+    """The f16c gamma|beta conv with its SPADE epilogue, whole tiles (ks = 1) or K ranges + the split-K SPADE pass (ks > 1).
+    out_mode 0 (fp32): <= 5e-5 against the float64 SPADE of the kernel's own three terms, <= 2e-4 against the exact float64
+    chain; out_mode 1 (split-bf16 words): hi + lo <= 5e-5 against the own-terms chain; out_mode 4 (f16c image): hi = fp16 of
+    the value, hi + lo8 ~ 15 bits, h8 = e4m3 of it; the borders stay zero."""
+    from moonsuperresolution_amd import ops
+    g = torch.Generator(device="cpu").manual_seed(seed)
     h = torch.relu(torch.randn((B, r, r, 128), generator=g)).cuda()
     wg = (torch.randn((3, 3, 128, C), generator=g) / 34).cuda()
     wb_ = (torch.randn((3, 3, 128, C), generator=g) / 34).cuda()
@@ -338,16 +424,30 @@ def test_conv_f16c_spade_epilogue_writes_the_chunk_image(ctx):
     mean = x.mean((0, 1, 2)).contiguous()
     std = torch.sqrt(x.var((0, 1, 2), unbiased=False) + 1e-5).contiguous()
     w, bias = ops.spade_layout(wg, wb_, bg, bb)
-    himg, _ = ops.f16c_activation_image(ops.pad_nhwc(h))
-    wimg, wexp, _ = ops.f16c_weight_image(w)
-    xr = x.double().cpu().repeat_interleave(2, 1).repeat_interleave(2, 2)
-    v = ref_conv(h, wg, bg, 1) * ((xr - mean.double().cpu()) / std.double().cpu()) + ref_conv(h, wb_, bb, 1)
+    himg, hparts = ops.f16c_activation_image(ops.pad_nhwc(h))
+    wimg, wexp, wparts = ops.f16c_weight_image(w)
+    torch.set_num_threads(16)
+    xr = x.double().cpu().repeat_interleave(1 << shift, 1).repeat_interleave(1 << shift, 2)
+    xn = (xr - mean.double().cpu()) / std.double().cpu()
+    v = ref_conv(h, wg, bg, 1) * xn + ref_conv(h, wb_, bb, 1)
     v = torch.where(v >= 0, v, 0.2 * v)
-    y32 = ops.conv3x3_f16c(ctx, himg, wimg, wexp, bias, r, epilogue=ops.EPI_SPADE, aux=x, aux_shift=shift, mean=mean, std=std,
-                           out_padded=True, out_mode=0)
-    assert rel_linf(y32.cpu()[:, 1:-1, 1:-1].numpy(), v.numpy()) <= 2e-4
-    yc = ops.conv3x3_f16c(ctx, himg, wimg, wexp, bias, r, epilogue=ops.EPI_SPADE, aux=x, aux_shift=shift, mean=mean, std=std,
-                          out_padded=True, out_mode=4)
+    gb = _ref_f16c(tuple(t[:, 1:-1, 1:-1].cpu() for t in hparts), tuple(t.cpu() for t in wparts), bias.cpu(), 128, 2 * C)
+    c = torch.arange(C)
+    rows_g = (c // 32) * 64 + (c % 32)
+    ve = gb[..., rows_g] * xn + gb[..., rows_g + 32]
+    ve = torch.where(ve >= 0, ve, 0.2 * ve)
+    kw = dict(epilogue=ops.EPI_SPADE, aux=x, aux_shift=shift, mean=mean, std=std, out_padded=True, ksplit=ks)
+    y32 = ops.conv3x3_f16c(ctx, himg, wimg, wexp, bias, r, out_mode=0, **kw)
+    e_emu, e_true = rel_linf(y32.cpu()[:, 1:-1, 1:-1].numpy(), ve.numpy()), rel_linf(y32.cpu()[:, 1:-1, 1:-1].numpy(), v.numpy())
+    ys = ops.conv3x3_f16c(ctx, himg, wimg, wexp, bias, r, out_mode=1, **kw)
+    shi, slo = unsplit(ys)
+    e_split = rel_linf((shi + slo).cpu()[:, 1:-1, 1:-1].numpy(), ve.numpy())
+    print(f"f16c SPADE ks={ks} C={C}: fp32 out vs own three terms {e_emu:.3e}, vs fp64 {e_true:.3e}; split-bf16 out vs own "
+          f"three terms {e_split:.3e}")
+    assert e_emu <= 5e-5 and e_split <= 5e-5, (e_emu, e_split)
+    assert e_true <= 2e-4, e_true
+    assert float((shi + slo).cpu()[:, 0].abs().max()) == 0 and float((shi + slo).cpu()[:, :, -1].abs().max()) == 0
+    yc = ops.conv3x3_f16c(ctx, himg, wimg, wexp, bias, r, out_mode=4, **kw)
     hi, h8, lo8 = (t.cpu()[:, 1:-1, 1:-1] for t in ops.f16c_decode(yc))
     want = y32.cpu()[:, 1:-1, 1:-1].double()
     scale = float(want.abs().max())
@@ -481,6 +581,67 @@ def test_spade_layer_resident_kernel(ctx, B, S, r, C, shift):
         float(full[0][:, -1].abs().max()) == 0 and float(full[2][:, :, 0].abs().max()) == 0        # the border stays zero
 
 
+@pytest.mark.parametrize("B,S,r,C,shift", [(8, 128, 32, 1024, 1), (2, 256, 64, 128, 0), (8, 64, 64, 64, 1), (3, 512, 128, 64, 1),
+                                           (8, 512, 16, 1024, 1)])
+def test_spade_layer_resident_kernel_f16(ctx, B, S, r, C, shift):
+    """conv_gb_resident<true> (msr_op_spade_gbr_f16, the f16 mode's SPADE layer): the gamma|beta products are the fp16 main
+    term alone.  Against the float64 chain in which the embedding and the gamma|beta weights are rounded to fp16 the kernel
+    holds 1e-4 (measured 1.0-2.5e-5 at these shapes; the bound is 4x the largest.  What is left is the output image's own
+    hi + lo8 rounding, ~2^-15, and the embedding, computed in fp32 by phase 1, rounding to the fp16 neighbour of the float64
+    embedding's rounding for the few values that sit next to a rounding boundary: one fp16 ulp of one K term, which a
+    bound at the kernel's accumulation level, 5e-5, would not always cover); against the exact chain 2e-3 (per-product
+    error 2^-11; measured 0.9-1.1e-4), and worse than the f16c6 form on the same operands."""
+    from moonsuperresolution_amd import ops
+    g = torch.Generator(device="cpu").manual_seed(1000 * B + r + C + 1)
+    src = (torch.rand((B, S, S, 2), generator=g) - 0.5).cuda()
+    we = (torch.randn((3, 3, 2, 128), generator=g) / 3).cuda()
+    be = (0.1 * torch.randn(128, generator=g)).cuda()
+    wg = (torch.randn((3, 3, 128, C), generator=g) / 34).cuda()
+    wb_ = (torch.randn((3, 3, 128, C), generator=g) / 34).cuda()
+    bg, bb = torch.randn(C, generator=g).cuda(), torch.randn(C, generator=g).cuda()
+    x = (3 + 2 * torch.randn((B, r >> shift, r >> shift, C), generator=g)).cuda()
+    mean = x.mean((0, 1, 2)).contiguous()
+    std = torch.sqrt(x.var((0, 1, 2), unbiased=False) + 1e-5).contiguous()
+    w, bias = ops.spade_layout(wg, wb_, bg, bb)
+    wimg = ops.gbr_weight_image(w)
+    torch.set_num_threads(16)
+    f = S // r
+    e = torch.relu(ref_conv(src[:, f // 2::f, f // 2::f][:, :r, :r], we, be, 1))
+    xr = x.double().cpu().repeat_interleave(1 << shift, 1).repeat_interleave(1 << shift, 2)
+    xn = (xr - mean.double().cpu()) / std.double().cpu()
+
+    def chain(e_, wg_, wb_r):
+        v = ref_conv(e_, wg_, bg, 1) * xn + ref_conv(e_, wb_r, bb, 1)
+        return torch.where(v >= 0, v, 0.2 * v).numpy()
+    exact = chain(e, wg, wb_)
+    rounded = chain(e.half().double(), wg.half().float(), wb_.half().float())
+    val = {}
+    for nox in (True, False):
+        hi, _, lo8 = (t.cpu()[:, 1:-1, 1:-1] for t in ops.f16c_decode(ops.spade_gbr(ctx, src, we, be, wimg, bias, r, x, shift,
+                                                                                       mean, std, no_cross=nox)))
+        val[nox] = (hi + lo8).numpy()
+    e_round, e_exact, e_full = rel_linf(val[True], rounded), rel_linf(val[True], exact), rel_linf(val[False], exact)
+    print(f"spade layer f16 (no cross) B={B} S={S} r={r} C={C}: vs fp16-rounded fp64 chain {e_round:.3e}, vs exact "
+          f"{e_exact:.3e} (f16c6 form {e_full:.3e})")
+    assert e_round <= 1e-4, e_round
+    assert e_exact <= 2e-3, e_exact
+    assert e_exact > e_full, (e_exact, e_full)
+
+
+def _check_saturated_f16c_image(what, hi, h8, lo8, want):
+    """The f16c producer contract beyond the pieces' ranges (kernels.h msr_store_f16c4_dev): finite, clamped to +-65504 with
+    the sign kept, h8 = +-448 in the middle band, hi + lo8 accurate to fp16's 11 bits there."""
+    assert float(want.abs().max()) > 65504, what
+    assert torch.isfinite(hi).all() and torch.isfinite(h8).all() and torch.isfinite(lo8).all(), what
+    over = want.abs() > 65504
+    assert over.any() and float((hi[over].abs() - 65504).abs().max()) == 0, what
+    assert bool((torch.sign(hi[over]) == torch.sign(want[over])).all()), what
+    mid = (want.abs() > 448) & (want.abs() < 6.0e4)
+    assert mid.any() and float((h8[mid].abs() - 448).abs().max()) == 0, what
+    assert bool((torch.sign(h8[mid]) == torch.sign(want[mid])).all()), what
+    assert float(((hi + lo8)[mid] - want[mid]).abs().max() / 6.0e4) <= 2.0 ** -11, what
+
+
 def test_f16c_saturation_regimes(ctx):
     """What the f16c path does with activations outside the pieces' ranges (kernels.h msr_store_f16c4_dev):
       |a| <= 448            all three terms live: per-product error ~2^-15 (the parity regime; every activation of the
@@ -532,6 +693,23 @@ def test_f16c_saturation_regimes(ctx):
     mid = (want.abs() > 448) & (want.abs() < 6.0e4)
     assert float((h8[mid].abs() - 448).abs().max()) == 0                        # the e4m3 piece saturates at 448
     assert float(((hi + lo8)[mid] - want[mid]).abs().max() / 6.0e4) <= 2.0 ** -11   # hi alone: fp16's 11 bits
+    # every other f16c producer, same contract: the ping-pong SPADE epilogue (whole tiles) and the split-K SPADE pass (K ranges)
+    # on host-built operands, with the same gamma bias ...
+    himg, _ = ops.f16c_activation_image(ops.pad_nhwc(e.float().cuda()))
+    wimg2, wexp2, _ = ops.f16c_weight_image(wl)
+    for ks in (1, 2):
+        yc = ops.conv3x3_f16c(ctx, himg, wimg2, wexp2, bias, rr, epilogue=ops.EPI_SPADE, aux=xx, aux_shift=0, mean=mean, std=std,
+                              out_padded=True, out_mode=4, ksplit=ks)
+        _check_saturated_f16c_image(f"f16c SPADE epilogue ks={ks}", *(t.cpu()[:, 1:-1, 1:-1] for t in ops.f16c_decode(yc)), want)
+    # ... and the mask embedding / encoder conv (conv_smallcin), tiled and untiled, with biases across +-9e4
+    from tests.helpers import smallcin_ref
+    for (Bs, S2, ho, imap) in ((1, 256, 128, ops.SMALLCIN_EMBED), (2, 64, 32, ops.SMALLCIN_STRIDE2)):    # tiled, untiled PX = 4
+        s2 = (torch.rand((Bs, S2, S2, 2), generator=g) - 0.5).cuda()
+        ws = (3.0e3 * torch.randn((3, 3, 2, 128), generator=g)).cuda()
+        bs = torch.linspace(-9.0e4, 9.0e4, 128).cuda()
+        yc = ops.conv_smallcin(ctx, s2, ws, bs, ho, imap, out_split=4)
+        _check_saturated_f16c_image(f"conv_smallcin map={imap} Hout={ho}", *(t.cpu() for t in ops.f16c_decode(yc)),
+                                    smallcin_ref(s2, ws, bs, ho, imap))
 
 
 def test_head_kernel_known_answers(ctx):

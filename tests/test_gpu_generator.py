@@ -17,6 +17,9 @@ from tests.helpers import rel_linf
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 TOL = 1e-3
+# pix2pix runs every layer on the fp32 MFMA (api.hip plan_pix2pix): an fp32-class bound, like MODE_TOL["fp32"] of
+# tests/test_gpu_baseline_configs.py.  Measured 7.4e-7 (B = 1) and 5.4e-7 (B = 3) against the float64 oracle; 2.5e-6 = 3.4x.
+P2P_TOL = 2.5e-6
 
 
 @pytest.fixture(scope="module")
@@ -279,7 +282,9 @@ def test_pix2pix_against_oracle(Generator):
     y = gen(x)
     ref = generator_ref.pix2pix_call(x, w, dtype=torch.float64)
     assert y.shape == (1, 256, 256, 1) and np.abs(y).max() < 1.0
-    assert rel_linf(y, ref) <= TOL
+    err = rel_linf(y, ref)
+    print(f"pix2pix S=256 B=1 rel Linf vs fp64 oracle {err:.3e}")
+    assert err <= P2P_TOL, err
     assert np.allclose(y[0, 16::32, 16::32, 0], g["probe"], atol=TOL * g["absmax"])
     assert abs(gen.forward_flops() / 1e9 - 11.929) < 1e-3
     gen.close()
@@ -295,7 +300,9 @@ def test_pix2pix_batched_and_repeatable(Generator):
     y1 = gen(x)
     y2 = gen(x)
     ref = generator_ref.pix2pix_call(x, w, dtype=torch.float64)
-    assert rel_linf(y1, ref) <= TOL
+    err = rel_linf(y1, ref)
+    print(f"pix2pix S=256 B=3 rel Linf vs fp64 oracle {err:.3e}")
+    assert err <= P2P_TOL, err
     assert np.array_equal(y1, y2)
     gen.close()
 
