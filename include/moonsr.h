@@ -365,6 +365,14 @@ int msr_debug_tensor(msr_handle* h, const char* name, float* host_out, int64_t c
  * kernels over the tensor), B (split-K epilogue), E1 | E2 (one- | two-stage finalize of conv slabs) followed by /C (slabs of
  * the conv_igemm epilogue) or /D (ping-pong / stream kernels).  NUL-terminated; MSR_ERR_INVALID when cap is too small. */
 int msr_debug_moment_forms(msr_handle* h, char* out, int64_t cap);
+/* Debug, read-only: one line per planned op of the network, in plan order, as "key=value" words.  kind = conv | gbr
+ * (conv_gb_resident) | smallcin | norm_act | dense | latent | head | moments | moments_slabs | direct; in / wt / wexp / bias / aux
+ * / mean / std / out name the op's tensors as msr_debug_tensor knows them ("input", "eps", "output": the call's own tensors,
+ * "-": none); conv and gbr lines carry prec, tile, ksplit, wt_frag, no_cross, epi, out_split, ranges (work items per pixel tile
+ * of the resident kernel, else 0) and img, the weight image msr_load_weight built (F32, BF16, BF16_FRAG, F16, FP8, F16C, F16C6,
+ * GBR); smallcin and norm_act lines carry out_split.  Needs a plan (after the first msr_forward or msr_forward_flops).
+ * NUL-terminated; MSR_ERR_INVALID when cap is too small. */
+int msr_debug_conv_forms(msr_handle* h, char* out, int64_t cap);
 /* Bytes of device memory held by the handle (weights + workspace). */
 int msr_device_bytes(const msr_handle* h, int64_t* bytes);
 

@@ -90,6 +90,7 @@ SYMBOLS = [
     ("msr_op_split_bf16", C.c_int, [_P, _P, _P, C.c_int64, _P]),
     ("msr_debug_tensor", C.c_int, [_P, C.c_char_p, _P, C.c_int64]),
     ("msr_debug_moment_forms", C.c_int, [_P, _P, C.c_int64]),
+    ("msr_debug_conv_forms", C.c_int, [_P, _P, C.c_int64]),
     ("msr_device_bytes", C.c_int, [_P, C.POINTER(C.c_int64)]),
 ]
 

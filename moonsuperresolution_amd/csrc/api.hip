@@ -101,6 +101,7 @@ struct msr_handle {
     std::map<std::string, int> spec_index;
     std::map<std::string, float*> dev;          // device tensors: weights (re-laid-out) and workspace
     std::map<std::string, size_t> dev_bytes;
+    std::map<std::string, int> dev_img;          // WeightImage of every conv weight uploaded by upload_conv_weight
     std::map<std::string, std::vector<float>> host_small;   // small host copies needed at plan time (BN, head)
     size_t total_bytes = 0;
     bool planned = false;
@@ -373,8 +374,10 @@ std::vector<float> build_f16c6_image(const float* host, int taps, int N, int Cin
     auto pow2exp = [](float amax) {
         if (!(amax > 0.f)) return 0;
         int fe;
-        const float m = std::frexp(amax / 7.5f, &fe);       // amax / 7.5 = m * 2^fe, m in [0.5, 1)
-        return std::max(-100, std::min(100, m == 0.5f ? fe - 1 : fe));
+        // in double: amax / 7.5f rounded to float can land ON a power of two from just above it, and 2^E would then be
+        // smaller than amax / 7.5 (kernels.h PREC_F16C6: 2^E >= max / 7.5)
+        const double m = std::frexp((double)amax / 7.5, &fe);       // amax / 7.5 = m * 2^fe, m in [0.5, 1)
+        return std::max(-100, std::min(100, m == 0.5 ? fe - 1 : fe));
     };
     for (int n = 0; n < N; ++n) {
         float ah = 0.f, al = 0.f;
@@ -523,6 +526,7 @@ int upload_conv_weight_fp8(msr_handle* h, const std::string& key, const float* h
 // Uploads the [taps][N][Cin] weights `host` of a conv as the image its form reads, under `key` (+ key.wexp: the per-channel
 // scales of the fp8 / f16c images).
 int upload_conv_weight(msr_handle* h, const std::string& key, const float* host, int taps, int N, int Cin, WeightImage img) {
+    h->dev_img[key] = img;
     switch (img) {
         case IMG_F32: return upload(h, key, host, (size_t)taps * N * Cin);
         case IMG_FP8: return upload_conv_weight_fp8(h, key, host, taps, N, Cin);
@@ -651,7 +655,12 @@ SpadeForm spade_form(const msr_handle* h, int r, int C, int cout, int epi) {
     }
     if (cv8) s.cv = make_form(PREC_FP8, TILE_256x128_PP, 1);
     else if (cv6) s.cv = make_form(PREC_F16C6, TILE_256x128_PP, 1);
-    else if (cvc) s.cv = make_form(PREC_F16C, TILE_256x128_PP, pp_ksplit(B, r, cout, 1, C), 0, h->f16m);
+    else if (cvc) {
+        // the f16 mode leaves the cross terms out on the stream kernel (whole tiles) only: a K-range launch runs the
+        // ping-pong kernel, which has no such form and computes them
+        const int ks = pp_ksplit(B, r, cout, 1, C);
+        s.cv = make_form(PREC_F16C, TILE_256x128_PP, ks, 0, h->f16m && ks == 1);
+    }
     else s.cv = conv_form(B, r, cout, 1, epi, h->prec, C);
     s.h_split = split_for(s.gb.prec);
     s.hslots = gb8 ? fp8_pad(128) / 4 : 128;
@@ -859,11 +868,13 @@ int msr_load_weight(msr_handle* h, const char* name_c, const float* host, const 
                             std::copy(src, src + co * ci, t4.data() + ((size_t)(py * 2 + px) * 4 + t * 2 + u) * co * ci);
                         }
             rc = upload(h, name, t4.data(), count);
+            h->dev_img[name] = IMG_F32;
         } else if (ends_with(name, ".kernel")) {
             // down2..8: HWIO -> [tap][Cout][Cin]
             std::vector<float> t(count);
             hwio_to_tap_oc_ic(host, t.data(), 16, (int)s[2], (int)s[3], (int)s[3], nullptr);
             rc = upload(h, name, t.data(), count);
+            h->dev_img[name] = IMG_F32;
         } else {
             h->host_small[name].assign(host, host + count);   // BN statistics / bias: folded at plan time
         }
@@ -2001,6 +2012,95 @@ int msr_debug_moment_forms(msr_handle* h, char* out, int64_t cap) {
         }
     }
     if ((int64_t)txt.size() + 1 > cap) return fail(h, MSR_ERR_INVALID, "msr_debug_moment_forms: %zu bytes needed", txt.size() + 1);
+    memcpy(out, txt.c_str(), txt.size() + 1);
+    return MSR_OK;
+}
+
+int msr_debug_conv_forms(msr_handle* h, char* out, int64_t cap) {
+    if (!h || !out || cap < 1) return MSR_ERR_INVALID;
+    // one line of "key=value" words per planned op, in plan order (moonsr.h).  Tensors are named by the reverse lookup in
+    // h->dev; a pointer into a buffer (a stride-2 conv reads from the interior of its padded input) names the buffer.
+    auto name_of = [&](const void* ptr) -> std::string {
+        if (!ptr) return "-";
+        const char* q = static_cast<const char*>(ptr);
+        for (const auto& kv : h->dev) {
+            const char* b = reinterpret_cast<const char*>(kv.second);
+            const auto sz = h->dev_bytes.find(kv.first);
+            if (q >= b && q < b + std::max<size_t>(sz == h->dev_bytes.end() ? 0 : sz->second, 16)) return kv.first;
+        }
+        return "?";
+    };
+    static const char* kImg[] = {"F32", "BF16", "BF16_FRAG", "F16", "FP8", "F16C", "F16C6", "GBR"};
+    auto img_of = [&](const std::string& key) -> const char* {
+        auto it = h->dev_img.find(key);
+        return it == h->dev_img.end() ? "?" : kImg[it->second];
+    };
+    std::string txt;
+    char b[1024];
+    for (const Op& op : h->ops) {
+        switch (op.type) {
+            case OP_CONV: {
+                const ConvParams& c = op.conv;
+                const std::string wt = name_of(c.wt);
+                snprintf(b, sizeof b, "kind=conv in=%s wt=%s wexp=%s bias=%s aux=%s mean=%s std=%s out=%s prec=%d tile=%d ksplit=%d "
+                         "wt_frag=%d no_cross=%d epi=%d out_split=%d ranges=0 img=%s B=%d r=%d cin=%d N=%d stride=%d aux_shift=%d "
+                         "stat_slabs=%d mom=%s\n", name_of(c.in).c_str(), wt.c_str(), name_of(c.wexp).c_str(),
+                         name_of(c.bias).c_str(), name_of(c.aux).c_str(), name_of(c.mean).c_str(), name_of(c.stdv).c_str(),
+                         name_of(c.out).c_str(), c.prec, op.tile, c.ksplit, c.wt_frag, c.no_cross, op.epi, c.out_split,
+                         img_of(wt), c.B, c.Hout, c.Cin, c.N, c.stride, c.aux_shift, op.stat_slabs, name_of(c.mom_mean).c_str());
+                break;
+            }
+            case OP_GBR: {
+                const GbrParams& q = op.gbr;
+                const std::string wt = name_of(q.wt);
+                snprintf(b, sizeof b, "kind=gbr in=input wt=%s embed=%s embed16=%s embed_bias=%s bias=%s aux=%s mean=%s std=%s out=%s "
+                         "prec=%d tile=%d ksplit=1 wt_frag=0 no_cross=%d epi=%d out_split=%d ranges=%d img=%s B=%d r=%d cin=128 N=%d "
+                         "stride=1 aux_shift=%d\n", wt.c_str(), name_of(q.we).c_str(), name_of(q.we16).c_str(),
+                         name_of(q.be).c_str(), name_of(q.bias).c_str(), name_of(q.aux).c_str(), name_of(q.mean).c_str(),
+                         name_of(q.stdv).c_str(), name_of(q.out).c_str(), (int)PREC_F16C6, (int)TILE_256x128_PP, q.no_cross,
+                         (int)EPI_SPADE, q.out_split, conv_gbr_ranges(q.B, q.r, q.N), img_of(wt), q.B, q.r, q.N, q.aux_shift);
+                break;
+            }
+            case OP_SMALLCIN: {
+                const SmallCinParams& p = op.sc;
+                snprintf(b, sizeof b, "kind=smallcin in=input wt=%s bias=%s out=%s out_split=%d B=%d r=%d N=%d stride=%d act=%d "
+                         "on_aux=%d\n", name_of(p.w).c_str(), name_of(p.bias).c_str(), name_of(p.out).c_str(), p.out_split, p.B,
+                         p.Hout, p.Cout, p.ay, p.act, op.on_aux ? 1 : 0);
+                break;
+            }
+            case OP_MOMENTS:
+            case OP_MOMENTS_SLABS:
+                snprintf(b, sizeof b, "kind=%s in=%s mean=%s std=%s\n", op.type == OP_MOMENTS ? "moments" : "moments_slabs",
+                         name_of(op.mom.x).c_str(), name_of(op.mom.mean).c_str(), name_of(op.mom.stdv).c_str());
+                break;
+            case OP_NORMACT:
+                snprintf(b, sizeof b, "kind=norm_act in=%s mean=%s std=%s gamma=%s beta=%s out=%s out_split=%d B=%d r=%d N=%d\n",
+                         name_of(op.na.x).c_str(), name_of(op.na.mean).c_str(), name_of(op.na.stdv).c_str(),
+                         name_of(op.na.gamma).c_str(), name_of(op.na.beta).c_str(), name_of(op.na.out).c_str(), op.na.out_split,
+                         op.na.B, op.na.H, op.na.C);
+                break;
+            case OP_DENSE:
+                snprintf(b, sizeof b, "kind=dense in=%s wt=%s bias=%s out=%s B=%d cin=%d N=%d\n", name_of(op.dense.x).c_str(),
+                         name_of(op.dense.W).c_str(), name_of(op.dense.bias).c_str(), name_of(op.dense.y).c_str(), op.dense.B,
+                         op.dense.K, op.dense.N);
+                break;
+            case OP_LATENT:
+                snprintf(b, sizeof b, "kind=latent in=%s aux=eps out=%s B=%d N=%d sampler=%d\n", name_of(op.lat.mv).c_str(),
+                         name_of(op.lat.z).c_str(), op.lat.B, op.lat.L, op.lat.sampler);
+                break;
+            case OP_HEAD:
+                snprintf(b, sizeof b, "kind=head in=%s wt=%s out=output B=%d r=%d cin=%d tanh=%d\n", name_of(op.head.x).c_str(),
+                         name_of(op.head.weff).c_str(), op.head.B, op.head.r, op.head.C, op.head.tanh_out);
+                break;
+            case OP_DIRECT:
+                snprintf(b, sizeof b, "kind=direct in=%s wt=%s out=%s B=%d r=%d N=%d\n", op.src_is_input ? "input" : name_of(op.dc.in0).c_str(),
+                         name_of(op.dc.w).c_str(), op.out_is_output ? "output" : name_of(op.dc.out).c_str(), op.dc.B, op.dc.Hout,
+                         op.dc.Cout);
+                break;
+        }
+        txt += b;
+    }
+    if ((int64_t)txt.size() + 1 > cap) return fail(h, MSR_ERR_INVALID, "msr_debug_conv_forms: %zu bytes needed", txt.size() + 1);
     memcpy(out, txt.c_str(), txt.size() + 1);
     return MSR_OK;
 }

@@ -21,6 +21,15 @@ from . import _lib
 from .weights import VARIANTS, make_latent_noise, make_weights, weight_shapes
 
 
+def parse_conv_forms(text: str) -> list:
+    """The text of msr_debug_conv_forms -> one dict per line; values that read as integers become ints."""
+    ops = []
+    for line in text.splitlines():
+        d = dict(word.split("=", 1) for word in line.split())
+        ops.append({k: int(v) if v.lstrip("-").isdigit() else v for k, v in d.items()})
+    return ops
+
+
 class Generator:
     """MI355X generator(call).
 
@@ -184,6 +193,15 @@ class Generator:
         rc = self._lib.msr_debug_moment_forms(self._h, buf, len(buf))
         _lib.raise_for(self._lib, self._h, rc, "msr_debug_moment_forms")
         return dict(line.split(" ") for line in buf.value.decode().splitlines())
+
+    def conv_forms(self) -> list:
+        """One dict per planned op, in plan order (msr_debug_conv_forms): kind, tensor names, and for the convs prec, tile,
+        ksplit, wt_frag, no_cross, epi, out_split, ranges and img (the weight image built at upload).  Integers are ints."""
+        self.prepare()
+        buf = C.create_string_buffer(1 << 18)
+        rc = self._lib.msr_debug_conv_forms(self._h, buf, len(buf))
+        _lib.raise_for(self._lib, self._h, rc, "msr_debug_conv_forms")
+        return parse_conv_forms(buf.value.decode())
 
     # -- measurement ---------------------------------------------------------------------------------
     def forward_flops(self) -> float:

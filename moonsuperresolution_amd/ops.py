@@ -86,6 +86,16 @@ def split_f16(x: torch.Tensor) -> torch.Tensor:
     return hl.view(torch.int16).reshape(-1).view(torch.float32).reshape(x.shape)
 
 
+def split_bf16_host(x: torch.Tensor) -> torch.Tensor:
+    """Host restatement of the split-bf16 chunk image (kernels.h msr_store_split4): every aligned group of 32 values becomes
+    [32 x hi bf16 | 32 x lo bf16] with hi = bf16_rn(v), lo = bf16_rn(v - hi); float32 storage, same shape."""
+    x = x.contiguous()
+    hi = x.to(torch.bfloat16)
+    lo = (x - hi.float()).to(torch.bfloat16)
+    hl = torch.stack([hi.reshape(-1, 32), lo.reshape(-1, 32)], 1).contiguous()
+    return hl.view(torch.int16).reshape(-1).view(torch.float32).reshape(x.shape)
+
+
 def weights_bf16x3(w_kl: torch.Tensor) -> torch.Tensor:
     """Kernel-layout weights [taps][N][Cin] (fp32) -> the MFMA-fragment order conv_igemm_bf16x3 reads:
     [tap][chunk][n-tile][kg][hi|lo][lane = 32*h + j][8 bf16], returned as float32 storage of the same size."""
@@ -261,6 +271,12 @@ def _f16c6_pack(hi: torch.Tensor, first: torch.Tensor, e_first: torch.Tensor, se
     return out.reshape(shp[:-1] + (n * 128,)).view(torch.float32).reshape(shp)
 
 
+def _pow2(E: torch.Tensor) -> torch.Tensor:
+    """2^E as float64, built from the exponent bits: exact on every device (a device pow(2.0, E) may be an ulp off, which moves
+    quotients that sit on a rounding tie to the other code)."""
+    return ((E.to(torch.int64) + 1023) << 52).view(torch.float64)
+
+
 def _ceil_log2_over(amax: torch.Tensor, top: float) -> torch.Tensor:
     """E = ceil(log2(amax / top)) as int64 (0 where amax == 0)"""
     m, e = torch.frexp((amax.double() / top))
@@ -277,7 +293,7 @@ def f16c6_activation_image(x: torch.Tensor):
     lo = (x - hi.float()).double()
     xb = x.double().reshape(shp[:-1] + (n, 32))
     E = _ceil_log2_over(xb.abs().amax(-1), 7.5).clamp(-100, 120)
-    s = torch.pow(2.0, E.double())[..., None]
+    s = _pow2(E)[..., None]
     ch = _e2m3_codes(xb / s)
     cl = _e2m3_codes(lo.reshape(xb.shape) / (s / 2048.0))
     dec = lambda c: torch.where(c >= 32, -_E2M3.to(c.device)[(c & 31).long()], _E2M3.to(c.device)[(c & 31).long()])   # noqa: E731
@@ -292,8 +308,8 @@ def f16c6_weight_image(w_kl: torch.Tensor):
     lo = (w_kl - hi.float()).double()
     Eh = _ceil_log2_over(w_kl.abs().amax(dim=(0, 2)), 7.5).clamp(-100, 100)
     El = _ceil_log2_over(lo.abs().amax(dim=(0, 2)), 7.5).clamp(-100, 100)
-    sh = torch.pow(2.0, Eh.double())[None, :, None]
-    sl = torch.pow(2.0, El.double())[None, :, None]
+    sh = _pow2(Eh)[None, :, None]
+    sl = _pow2(El)[None, :, None]
     ch, cl = _e2m3_codes(w_kl.double() / sh), _e2m3_codes(lo / sl)
     n = w_kl.shape[-1] // 32
     eb = lambda E: (127 + E)[None, :, None].expand(w_kl.shape[0], -1, n)   # noqa: E731
@@ -315,7 +331,7 @@ def f16c6_decode(img: torch.Tensor):
         c = torch.stack([(w >> (6 * k)) & 63 for k in range(4)], dim=-1).reshape(shp[:-1] + (n, 32))
         grid = _E2M3.to(img.device)
         v = torch.where(c >= 32, -grid[c & 31], grid[c & 31])
-        s = torch.pow(2.0, (b[..., off + 24] - 127).double())[..., None]
+        s = _pow2(b[..., off + 24] - 127)[..., None]
         return (v * s).reshape(shp)
     return hi, piece(64), piece(96)
 
@@ -383,6 +399,46 @@ def spade_gbr(ctx: OpContext, src: torch.Tensor, we: torch.Tensor, be: torch.Ten
             x.data_ptr(), aux_shift, mean.data_ptr(), std.data_ptr(), torch.cuda.current_stream(src.device).cuda_stream)
     _lib.raise_for(ctx.lib, ctx.h, rc, "msr_op_spade_gbr")
     return out
+
+
+def gbr_embed_image(we_hwio: torch.Tensor) -> torch.Tensor:
+    """Mask-embedding kernel HWIO [3, 3, 2, 128] -> the fp16 A operands of conv_gb_resident's phase 1 (conv_gbr.hip
+    conv_gbr_embed_image, uploaded as <kernel>.e16): [channel quarter 4][instruction 4][lane 64] x 8 fp16.  K slot pair
+    P = 8 j + 4 (lane >> 5) + u carries term P // 9 (0, 1: w_hi, 2: w_lo = f16_rn(w - w_hi)) of tap P % 9 for both mask
+    channels, output channel 32 wq + (lane & 31); P >= 27 is zero.  Returned as float32 storage [4096]."""
+    w = we_hwio.reshape(9, 2, 128).float().cpu()
+    hi = w.to(torch.float16)
+    lo = (w - hi.float()).to(torch.float16)
+    wq, j, lane, u, c = torch.meshgrid(torch.arange(4), torch.arange(4), torch.arange(64), torch.arange(4), torch.arange(2),
+                                       indexing="ij")
+    P = 8 * j + 4 * (lane >> 5) + u
+    ch = 32 * wq + (lane & 31)
+    tap = (P % 9).clamp(max=8)
+    v = torch.where(P // 9 == 2, lo[tap, c, ch], hi[tap, c, ch])
+    v = torch.where(P < 27, v, torch.zeros_like(v))
+    return v.contiguous().view(torch.int16).reshape(-1).view(torch.float32).clone()
+
+
+def head_taps_upconv(k44c: torch.Tensor) -> torch.Tensor:
+    """Head kernel [4, 4, C] (Conv2D(1, 4, 'same') after UpSampling2D(2), networks.py:54-56) -> the effective per-parity taps
+    weff[py][px][dy + 1][dx + 1][C] the head kernel reads (api.hip head_weff_upconv, uploaded as gen.head.weff): TF SAME for
+    k = 4 pads 1 before / 2 after, so output parity p reads half-resolution offsets {-1, 0, 0, +1} (p = 0) or {0, 0, +1, +1}
+    (p = 1) for kh = 0..3; taps that land on the same pixel are added in fp32, in kh, kw order."""
+    k = k44c.float().cpu()
+    dmap = lambda parity, t: (0 if t == 0 else 2 if t == 3 else 1) if parity == 0 else (1 if t < 2 else 2)   # noqa: E731
+    weff = torch.zeros((2, 2, 3, 3, k.shape[2]), dtype=torch.float32)
+    for py in range(2):
+        for px in range(2):
+            for kh in range(4):
+                for kw in range(4):
+                    weff[py, px, dmap(py, kh), dmap(px, kw)] += k[kh, kw]
+    return weff
+
+
+def heads_concat(mean: torch.Tensor, variance: torch.Tensor) -> torch.Tensor:
+    """The encoder's two heads as msr_load_weight stores them (enc.heads.kernel [K, 2L], enc.heads.bias [2L]): mean | variance
+    side by side along the last axis, so that the flattened encoder output is streamed once."""
+    return torch.cat([mean, variance], dim=-1).contiguous()
 
 
 SMALLCIN_STRIDE2, SMALLCIN_EMBED = 0, 1     # msr_op_conv_smallcin index maps: encoder block 1 / SPADE mask embedding

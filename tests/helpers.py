@@ -41,12 +41,15 @@ def synthetic_raster(h, w, seed=0, hole=None, no_value=-32768.0):
     return img, dem
 
 
-def smallcin_ref(src, w, bias, hout, index_map, act=0, slope=0.0):
-    """float64 CPU restatement of conv_smallcin: src [B,S,S,2] -> [B,hout,hout,Cout].  index_map 0: Conv2D(3, strides=2,
+def smallcin_ref(src, w, bias, hout, index_map, act=0, slope=0.0, device=None):
+    """float64 CPU restatement of conv_smallcin (``device``: the same arithmetic as tap matmuls on that device, for the
+    network-sized tensors of tests/test_gpu_network_sites.py): src [B,S,S,2] -> [B,hout,hout,Cout].  index_map 0: Conv2D(3, strides=2,
     'same') on S = 2 hout (TF pads 0 before, 1 after); 1: tf.image.resize(nearest, half-pixel centres) to hout x hout, then
     Conv2D(3, 'same'); act 1 relu, 2 leaky_relu(slope)."""
     import torch
     import torch.nn.functional as F
+    if device is not None:
+        return _smallcin_ref_taps(src, w, bias, hout, index_map, act, slope, device)
     x = src.double().cpu()
     S = x.shape[1]
     if index_map == 1:
@@ -61,3 +64,87 @@ def smallcin_ref(src, w, bias, hout, index_map, act=0, slope=0.0):
     elif act == 2:
         y = torch.where(y >= 0, y, slope * y)
     return y
+
+
+def ref_conv(x, w, b, stride):
+    """TF SAME conv on NHWC in float64 on the CPU."""
+    import torch
+    import torch.nn.functional as F
+    x, w, b = x.double().cpu(), w.double().cpu(), b.double().cpu()
+    xn = x.permute(0, 3, 1, 2)
+    xn = F.pad(xn, (1, 1, 1, 1)) if stride == 1 else F.pad(xn, (0, 1, 0, 1))
+    return F.conv2d(xn, w.permute(3, 2, 0, 1), b, stride=stride).permute(0, 2, 3, 1)
+
+
+def unsplit(t):
+    """split-bf16 chunk image -> (hi + lo) float32 values, same shape (innermost dim % 32 == 0)."""
+    import torch
+    u = t.contiguous().view(torch.int16).reshape(-1, 2, 32).to(torch.int32) & 0xFFFF
+    hi = (u[:, 0] << 16).view(torch.float32)
+    lo = (u[:, 1] << 16).view(torch.float32)
+    return hi.reshape(t.shape), lo.reshape(t.shape)
+
+
+def _ref_f16c(xparts, wparts, bias, cin, cout):
+    """What the f16c kernel computes, in float64: x_hi*w_hi + x_h8*w_lo8 + x_lo8*w_h8 (+ bias)."""
+    import torch
+    (xh, x8, xl), (wh, w8, wl) = xparts, wparts
+    hwio = lambda t: t.permute(0, 2, 1).reshape(3, 3, cin, cout)   # noqa: E731
+    zero = torch.zeros(cout, dtype=torch.float64)
+    return (ref_conv(xh, hwio(wh), bias, 1) + ref_conv(x8, hwio(wl), zero, 1) + ref_conv(xl, hwio(w8), zero, 1))
+
+
+def conv_taps(xpad, w_tnk, r, stride=1, dtype=None):
+    """3x3 conv as nine matmuls, on whatever device the operands live: xpad [B, r * stride + 2, ., C] zero-bordered NHWC (what
+    the conv kernels read: tap (kh, kw) of output (y, x) is xpad[b, y * stride + kh, x * stride + kw] at stride 1 and
+    xpad[b, 1 + y * stride + kh, 1 + x * stride + kw] at stride 2, TF SAME), w_tnk [9][N][C] -> [B, r, r, N].  float64 unless
+    ``dtype`` says otherwise (float32: the plain fp32 accumulation the K-length allowance is measured with)."""
+    import torch
+    dtype = dtype or torch.float64
+    B, C = xpad.shape[0], xpad.shape[3]
+    N = w_tnk.shape[1]
+    off = 0 if stride == 1 else 1
+    w = w_tnk.to(dtype)
+    out = torch.empty((B, r, r, N), dtype=dtype, device=xpad.device)
+    for b in range(B):                       # per sample: bounds the temporaries at the S = 512 shapes
+        xb = xpad[b].to(dtype)
+        acc = torch.zeros((r * r, N), dtype=dtype, device=xpad.device)
+        for kh in range(3):
+            for kw in range(3):
+                sl = xb[off + kh: off + kh + stride * r: stride, off + kw: off + kw + stride * r: stride]
+                acc += sl.reshape(r * r, C) @ w[kh * 3 + kw].T
+        out[b] = acc.reshape(r, r, N)
+    return out
+
+
+def pad_hw(x):
+    """[B, r, r, C] -> zero-bordered [B, r + 2, r + 2, C], same dtype and device."""
+    import torch.nn.functional as F
+    return F.pad(x, (0, 0, 1, 1, 1, 1))
+
+
+def _smallcin_ref_taps(src, w, bias, hout, index_map, act, slope, device):
+    import torch
+    x = src.double().to(device)
+    S = x.shape[1]
+    if index_map == 1:
+        f = S // hout
+        x = x[:, f // 2::f, f // 2::f][:, :hout, :hout]
+    w_tnk = w.double().to(device).reshape(9, 2, -1).permute(0, 2, 1).contiguous()
+    y = conv_taps(pad_hw(x), w_tnk, hout, stride=2 if index_map == 0 else 1)
+    if bias is not None:
+        y = y + bias.double().to(device)
+    if act == 1:
+        y = torch.relu(y)
+    elif act == 2:
+        y = torch.where(y >= 0, y, slope * y)
+    return y
+
+
+def dense_kch(K, N):
+    """small_kernels.hip dense_kch: K chunk per workgroup (power of two, 16..256) for >= 1024 workgroups."""
+    gx = (N // 4 + 127) // 128
+    kch = 256
+    while kch > 16 and gx * ((K + kch - 1) // kch) < 1024:
+        kch >>= 1
+    return kch

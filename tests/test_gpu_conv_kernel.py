@@ -5,7 +5,7 @@ import pytest
 import torch
 import torch.nn.functional as F
 
-from tests.helpers import rel_linf
+from tests.helpers import _ref_f16c, ref_conv, rel_linf, unsplit
 
 pytestmark = pytest.mark.gpu
 
@@ -17,14 +17,6 @@ def ctx(hip_lib):
     c = ops.OpContext()
     yield c
     c.close()
-
-
-def ref_conv(x, w, b, stride):
-    """TF SAME conv on NHWC in float64 on the CPU."""
-    x, w, b = x.double().cpu(), w.double().cpu(), b.double().cpu()
-    xn = x.permute(0, 3, 1, 2)
-    xn = F.pad(xn, (1, 1, 1, 1)) if stride == 1 else F.pad(xn, (0, 1, 0, 1))
-    return F.conv2d(xn, w.permute(3, 2, 0, 1), b, stride=stride).permute(0, 2, 3, 1)
 
 
 @pytest.mark.parametrize("B,r,cin,cout,stride,tile", [
@@ -134,14 +126,6 @@ def test_conv_bf16x3(ctx, B, r, cin, cout, stride, tile, frag):
     y = ops.conv3x3(ctx, xs, ws, b, r, stride=stride, tile=tile | frag, precision="bf16x3")
     err = rel_linf(y.cpu().numpy(), ref_conv(x, w, b, stride).numpy())
     assert err <= 5e-5, err
-
-
-def unsplit(t):
-    """split-bf16 chunk image -> (hi + lo) float32 values, same shape (innermost dim % 32 == 0)."""
-    u = t.contiguous().view(torch.int16).reshape(-1, 2, 32).to(torch.int32) & 0xFFFF
-    hi = (u[:, 0] << 16).view(torch.float32)
-    lo = (u[:, 1] << 16).view(torch.float32)
-    return hi.reshape(t.shape), lo.reshape(t.shape)
 
 
 def test_split_bf16_words(ctx):
@@ -294,14 +278,6 @@ def test_conv_fp8_spade_epilogue_bf8_output(ctx):
     ulp = torch.maximum(want.abs() * 0.25, torch.tensor(2.0 ** -16))               # one bf8 step (2 mantissa bits; subnormal floor)
     assert bool(((got - want).abs() <= ulp * 1.001)[mism].all())
     assert int(y8[:, 0].max()) == 0 and int(y8[:, :, -1].max()) == 0     # the border stays zero
-
-
-def _ref_f16c(xparts, wparts, bias, cin, cout):
-    """What the f16c kernel computes, in float64: x_hi*w_hi + x_h8*w_lo8 + x_lo8*w_h8 (+ bias)."""
-    (xh, x8, xl), (wh, w8, wl) = xparts, wparts
-    hwio = lambda t: t.permute(0, 2, 1).reshape(3, 3, cin, cout)   # noqa: E731
-    zero = torch.zeros(cout, dtype=torch.float64)
-    return (ref_conv(xh, hwio(wh), bias, 1) + ref_conv(x8, hwio(wl), zero, 1) + ref_conv(xl, hwio(w8), zero, 1))
 
 
 @pytest.mark.parametrize("B,r,cin,cout,ks,res", [

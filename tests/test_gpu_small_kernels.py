@@ -10,7 +10,7 @@ import numpy as np
 import pytest
 import torch
 
-from tests.helpers import smallcin_ref
+from tests.helpers import dense_kch as _dense_kch, smallcin_ref
 
 pytestmark = pytest.mark.gpu
 
@@ -184,15 +184,6 @@ def test_norm_act(ctx, B, H, C, out_padded, out_split):
     if out_split:
         ys = ops.norm_act(ctx, *args, slope=slope, out_padded=out_padded, out_split=True).cpu()
         assert torch.equal(_bytes(ys), _bytes(_split_bf16_host(y)))
-
-
-def _dense_kch(K, N):
-    """small_kernels.hip dense_kch: K chunk per workgroup (power of two, 16..256) for >= 1024 workgroups."""
-    gx = (N // 4 + 127) // 128
-    kch = 256
-    while kch > 16 and gx * ((K + kch - 1) // kch) < 1024:
-        kch >>= 1
-    return kch
 
 
 @pytest.mark.parametrize("B,K,N,bias", [(1, 1000, 100, True), (2, 7, 1024, False), (3, 1000, 2052, True), (5, 13, 516, True),
