@@ -373,6 +373,52 @@ int msr_debug_moment_forms(msr_handle* h, char* out, int64_t cap);
  * GBR); smallcin and norm_act lines carry out_split.  Needs a plan (after the first msr_forward or msr_forward_flops).
  * NUL-terminated; MSR_ERR_INVALID when cap is too small. */
 int msr_debug_conv_forms(msr_handle* h, char* out, int64_t cap);
+/* ---- activation-range scan ------------------------------------------------------------------------ */
+/* The f16c family (MSR_FLAG_F16C, _F16_MAIN, _FP8, _GB_F16X2) stores the inputs of the big convs in narrow pieces with finite
+ * ranges; tests/test_gpu_conv_kernel.py::test_f16c_saturation_regimes states the three regimes of one activation a:
+ *   |a| <= 448            every piece is live: the parity regime (every stated parity figure is taken here)
+ *   448 < |a| <= 65504    the e4m3 cross piece clips and the conv drops to one fp16 product (2.5e-4 in that test)
+ *   |a| > 65504           the producer clamps: finite and wrong
+ * Keras-default weights stay near 40; trained gamma / beta need not.  The scan tells at run time which regime a call was in.
+ * A record per narrow activation tensor of the plan (out_split 2 split-fp16, 3 bf8 bytes, 4 f16c, 5 f16c6; split-bf16 and fp32
+ * tensors have fp32's range and are not scanned), taken on the tensor's MAIN piece hi over the interior (zero borders and zero
+ * padding channels are not counted):
+ *   max_abs          largest finite |hi|
+ *   n_total          interior elements
+ *   n_cross_clipped  format 4 only: |hi| > 464.  The boundary is 464 and not 448 because e4m3's grid around its largest value
+ *                    is 416, 448, (480): under round-to-nearest-even everything up to the midpoint 464 — the tie included, 448
+ *                    has the even mantissa — rounds to 448 whether or not the converter saturates; above it the saturation
+ *                    changes the value.  A clipped low piece needs |hi| >= 512, so counting on hi covers it.  Format 5's block
+ *                    scale follows the data: always 0
+ *   n_clamped        |hi| equals the format's largest finite value (65504; bf8: 57344)
+ *   n_nonfinite      hi is an infinity or a NaN */
+typedef struct {
+    char    tensor[48];      /* name as msr_debug_tensor knows it, e.g. "ws.gen.rb5.a1" */
+    int32_t format;          /* the planner's out_split of that tensor, or MSR_RANGE_FORMAT_EMBED */
+    int32_t producer;        /* index of the producing op in msr_debug_conv_forms order */
+    float   max_abs;
+    int64_t n_total, n_cross_clipped, n_clamped, n_nonfinite;
+} msr_range_stat;
+#define MSR_RANGE_FORMAT_EMBED 100
+/* Asynchronous: enqueues on `stream` the zeroing of the records, ONE scan launch over every narrow activation tensor of the
+ * plan (csrc/range_scan.hip) and the copy of the records to pinned host memory.  Meant to follow an msr_forward on the same
+ * stream, so that it sees that call's workspace before the next call overwrites it; it is a call of its own and never part
+ * of the forward's HIP graph.  One scan is outstanding per handle: a new one replaces the last.  MSR_ERR_STATE before the
+ * first msr_forward.  The first scan allocates the table and the records (40 + 40 bytes per tensor). */
+int msr_range_scan(msr_handle* h, void* stream);
+/* Waits for the last msr_range_scan and fills up to cap records in plan order; *n = number of scanned tensors (0 for plans
+ * without narrow tensors: fp32, bf16x3).  MSR_ERR_STATE if no scan was enqueued. */
+int msr_range_read(msr_handle* h, msr_range_stat* out, int32_t cap, int32_t* n);
+/* The embedding of a conv_gb_resident layer (kind=gbr) exists only in LDS, as fp16, and cannot be scanned.  For every gbr op,
+ * in plan order: a record with format = MSR_RANGE_FORMAT_EMBED, tensor = the embedding kernel's weight name, producer = the op
+ * and max_abs = max over channels c of 0.5 * sum |w[., ., ., c]| + |b_c|, from the fp32 weights the handle received — a bound
+ * on |embedding| for inputs in [-0.5, 0.5] (the contract of msr_forward's in_dev); counts are 0.  Host only; needs a plan. */
+int msr_range_embed_bounds(msr_handle* h, msr_range_stat* out, int32_t cap, int32_t* n);
+/* Kernel-level entry of the scan, synchronous: one image in `format` (2, 3, 4, 5) holding [B, r, r, C] (C % 32 == 0),
+ * zero-bordered [B, r + 2, r + 2, .] when padded != 0; chunk formats have 4 * C bytes per pixel, bf8 has C bytes padded to 128
+ * or a multiple of 256.  Fills *out_stat (tensor empty, producer -1).  Bad arguments: MSR_ERR_INVALID before any allocation. */
+int msr_op_range_scan(msr_handle* h, const void* img_dev, int32_t format, int32_t B, int32_t r, int32_t C, int32_t padded,
+                      msr_range_stat* out_stat, void* stream);
 /* Bytes of device memory held by the handle (weights + workspace). */
 int msr_device_bytes(const msr_handle* h, int64_t* bytes);
 

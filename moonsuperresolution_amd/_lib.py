@@ -34,6 +34,15 @@ class MsrKernelStat(C.Structure):
                 ("flops", C.c_double), ("bytes", C.c_double)]
 
 
+class MsrRangeStat(C.Structure):
+    """msr_range_stat: one record of the activation-range scan (include/moonsr.h)."""
+    _fields_ = [("tensor", C.c_char * 48), ("format", C.c_int32), ("producer", C.c_int32), ("max_abs", C.c_float),
+                ("n_total", C.c_int64), ("n_cross_clipped", C.c_int64), ("n_clamped", C.c_int64),
+                ("n_nonfinite", C.c_int64)]
+
+
+RANGE_FORMAT_EMBED = 100    # MSR_RANGE_FORMAT_EMBED: a host-side bound on a conv_gb_resident embedding, not a scanned tensor
+
 # every symbol include/moonsr.h declares: (name, restype, argtypes)
 _P = C.c_void_p
 SYMBOLS = [
@@ -92,6 +101,10 @@ SYMBOLS = [
     ("msr_debug_moment_forms", C.c_int, [_P, _P, C.c_int64]),
     ("msr_debug_conv_forms", C.c_int, [_P, _P, C.c_int64]),
     ("msr_device_bytes", C.c_int, [_P, C.POINTER(C.c_int64)]),
+    ("msr_range_scan", C.c_int, [_P, _P]),
+    ("msr_range_read", C.c_int, [_P, C.POINTER(MsrRangeStat), C.c_int32, C.POINTER(C.c_int32)]),
+    ("msr_range_embed_bounds", C.c_int, [_P, C.POINTER(MsrRangeStat), C.c_int32, C.POINTER(C.c_int32)]),
+    ("msr_op_range_scan", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.POINTER(MsrRangeStat), _P]),
 ]
 
 _lib: Optional[C.CDLL] = None
@@ -162,14 +175,24 @@ def load() -> C.CDLL:
         import torch  # noqa: F401
     except ImportError:
         pass
-    lib = C.CDLL(path)
-    for name, restype, argtypes in SYMBOLS:
-        fn = getattr(lib, name)   # AttributeError if the ABI lost a symbol
-        fn.restype = restype
-        fn.argtypes = argtypes
+    lib = bind(C.CDLL(path), path)
     if lib.msr_abi_version() != 1:
         raise RuntimeError("libmoonsr_hip.so ABI version mismatch")
     _lib = lib
+    return lib
+
+
+def bind(lib, path: str):
+    """Set the prototypes of every symbol of SYMBOLS on ``lib``.  A library that lacks one (an older build of the same ABI
+    version: entries are only ever added) is an error that names the symbols, never a partial binding."""
+    missing = [name for name, _, _ in SYMBOLS if not hasattr(lib, name)]
+    if missing:
+        raise RuntimeError(f"{path} lacks {', '.join(missing)}: it was built from older sources than this package; rebuild "
+                           "it with `python -c 'import __graft_entry__ as g; g.build()'`")
+    for name, restype, argtypes in SYMBOLS:
+        fn = getattr(lib, name)
+        fn.restype = restype
+        fn.argtypes = argtypes
     return lib
 
 

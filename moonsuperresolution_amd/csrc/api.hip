@@ -135,6 +135,20 @@ struct msr_handle {
     std::vector<ProfRec> prof;
     std::vector<hipEvent_t> ev_pool;
     size_t ev_used = 0;
+    // activation-range scan (msr_range_scan): the narrow activation tensors of the plan, in plan order.  Nothing here is
+    // allocated on the device before the first scan.
+    struct RangeEntry { std::string tensor; int producer; RangeScanItem item; };
+    struct EmbedEntry { std::string kernel; int producer; };
+    std::vector<RangeEntry> range_plan;
+    std::vector<EmbedEntry> range_embeds;        // the gbr ops, whose embedding exists only in LDS (msr_range_embed_bounds)
+    RangeScanItem* range_table_dev = nullptr;
+    RangeScanRecord* range_rec_dev = nullptr;
+    RangeScanRecord* range_rec_host = nullptr;   // pinned
+    size_t range_cap = 0;                        // entries the three buffers hold
+    bool range_table_stale = true;
+    hipEvent_t range_done = nullptr;
+    bool range_enqueued = false;
+    bool forward_seen = false;
 };
 
 namespace {
@@ -799,6 +813,10 @@ int msr_destroy(msr_handle* h) {
         if (op.done) hipEventDestroy(op.done);
     if (h->ev_fork) hipEventDestroy(h->ev_fork);
     if (h->aux) hipStreamDestroy(h->aux);
+    if (h->range_table_dev) hipFree(h->range_table_dev);
+    if (h->range_rec_dev) hipFree(h->range_rec_dev);
+    if (h->range_rec_host) hipHostFree(h->range_rec_host);
+    if (h->range_done) hipEventDestroy(h->range_done);
     delete h;
     return MSR_OK;
 }
@@ -883,6 +901,8 @@ int msr_load_weight(msr_handle* h, const char* name_c, const float* host, const 
                name == "gen.dense.bias" || (name.find(".conv_") != std::string::npos && ends_with(name, ".bias") &&
                                             name.find("spade") == std::string::npos)) {
         rc = upload(h, name, host, count);   // used in the reference layout
+        if (name.find(".spade_") != std::string::npos && (ends_with(name, ".conv.kernel") || ends_with(name, ".conv.bias")))
+            h->host_small[name].assign(host, host + count);   // msr_range_embed_bounds reads the fp32 embedding weights
         if (!rc && ends_with(name, ".conv.kernel") && name.find(".spade_") != std::string::npos) {
             // conv_gb_resident multiplies the mask embedding on the fp16 MFMA: its A operands (three fp16 terms per product)
             std::vector<float> e16(4096);
@@ -1385,6 +1405,41 @@ int ensure_conv_partial(msr_handle* h, size_t floats) {
     return MSR_OK;
 }
 
+// The tensors msr_range_scan reads: every planned activation image written in a format whose pieces have a finite range
+// (out_split 2, 3, 4, 5), once each, in plan order; and the gbr ops, whose embedding is bounded on the host instead.
+void build_range_plan(msr_handle* h) {
+    h->range_plan.clear();
+    h->range_embeds.clear();
+    h->range_table_stale = true;
+    auto name_of = [&](const void* ptr) -> std::string {
+        for (const auto& kv : h->dev) if (kv.second == ptr) return kv.first;
+        return "";
+    };
+    auto add = [&](int producer, const float* out, int out_off, int split, int B, int r, int C, int px_floats) {
+        if (split < 2 || split > 5 || !out || C % 32) return;
+        const std::string nm = name_of(out);
+        if (nm.empty() || nm.size() >= 48) return;
+        if (split != 3 && px_floats != C) return;                       // chunk formats: one float slot per channel
+        for (const auto& e : h->range_plan) if (e.tensor == nm) return;
+        RangeScanItem it{out, split, B, r, C, px_floats * 4, out_off != 0, (int)h->range_plan.size()};
+        h->range_plan.push_back({nm, producer, it});
+    };
+    for (size_t k = 0; k < h->ops.size(); ++k) {
+        const Op& op = h->ops[k];
+        if (op.type == OP_CONV) {
+            const ConvParams& c = op.conv;
+            add((int)k, c.out, c.out_off, c.out_split, c.B, c.Hout, op.epi == EPI_SPADE ? c.N / 2 : c.N, c.out_px);
+        } else if (op.type == OP_GBR) {
+            const GbrParams& q = op.gbr;
+            add((int)k, q.out, q.out_off, q.out_split, q.B, q.r, q.N / 2, q.out_px);
+            h->range_embeds.push_back({name_of(q.we), (int)k});
+        } else if (op.type == OP_SMALLCIN) {
+            const SmallCinParams& p = op.sc;
+            add((int)k, p.out, p.out_off, p.out_split, p.B, p.Hout, p.Cout, p.out_px);
+        }
+    }
+}
+
 int ensure_plan(msr_handle* h) {
     if (h->planned) return MSR_OK;
     for (auto& s : h->specs)
@@ -1431,6 +1486,7 @@ int ensure_plan(msr_handle* h) {
         h->stat_ws_floats = stat_need;
     }
     HIPCHK(h, hipDeviceSynchronize());
+    build_range_plan(h);
     h->planned = true;
     return MSR_OK;
 }
@@ -1591,6 +1647,7 @@ int msr_forward(msr_handle* h, const float* in_dev, const float* eps_dev, float*
     HIPCHK(h, hipSetDevice(h->cfg.device));
     int rc = ensure_plan(h);
     if (rc) return rc;
+    h->forward_seen = true;
     hipStream_t s = (hipStream_t)stream_v;
     if (!h->graph_on || h->prof_on) return launch_all(h, in_dev, eps_dev, out_dev, s);
     // Graph mode: the ~100 launches, the fork to the auxiliary stream and its joins are captured once per pointer
@@ -1650,6 +1707,7 @@ int msr_forward_gated(msr_handle* h, const float* in_dev, const float* eps_dev, 
     HIPCHK(h, hipSetDevice(h->cfg.device));
     int rc = ensure_plan(h);
     if (rc) return rc;
+    h->forward_seen = true;
     return launch_all(h, in_dev, eps_dev, out_dev, (hipStream_t)stream_v, (hipEvent_t)gate_event);
 }
 
@@ -2102,6 +2160,123 @@ int msr_debug_conv_forms(msr_handle* h, char* out, int64_t cap) {
     }
     if ((int64_t)txt.size() + 1 > cap) return fail(h, MSR_ERR_INVALID, "msr_debug_conv_forms: %zu bytes needed", txt.size() + 1);
     memcpy(out, txt.c_str(), txt.size() + 1);
+    return MSR_OK;
+}
+
+// ---- activation-range scan ---------------------------------------------------------------------------------------------
+static void range_fill(msr_range_stat* o, const std::string& tensor, int format, int producer, const RangeScanRecord& r) {
+    std::memset(o, 0, sizeof *o);
+    snprintf(o->tensor, sizeof o->tensor, "%s", tensor.c_str());
+    o->format = format;
+    o->producer = producer;
+    std::memcpy(&o->max_abs, &r.max_abs_bits, sizeof(float));
+    o->n_total = (int64_t)r.n_total;
+    o->n_cross_clipped = (int64_t)r.n_cross_clipped;
+    o->n_clamped = (int64_t)r.n_clamped;
+    o->n_nonfinite = (int64_t)r.n_nonfinite;
+}
+
+int msr_range_scan(msr_handle* h, void* stream) {
+    if (!h) return MSR_ERR_INVALID;
+    if (!h->forward_seen) return fail(h, MSR_ERR_STATE, "msr_range_scan: no msr_forward has run on this handle yet");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t n = h->range_plan.size();
+    h->range_enqueued = true;
+    if (n == 0) return MSR_OK;                       // fp32 / bf16x3 plans hold no narrow tensor
+    if (!h->range_done) HIPCHK(h, hipEventCreateWithFlags(&h->range_done, hipEventDisableTiming));
+    if (h->range_cap < n) {
+        // table (device), records (device, pinned host), and a pinned staging copy of the table behind the records
+        if (h->range_table_dev) { HIPCHK(h, hipFree(h->range_table_dev)); h->range_table_dev = nullptr; }
+        if (h->range_rec_dev) { HIPCHK(h, hipFree(h->range_rec_dev)); h->range_rec_dev = nullptr; }
+        if (h->range_rec_host) { HIPCHK(h, hipHostFree(h->range_rec_host)); h->range_rec_host = nullptr; }
+        h->total_bytes -= h->range_cap * (sizeof(RangeScanItem) + sizeof(RangeScanRecord));
+        h->range_cap = 0;
+        HIPCHK(h, hipMalloc(&h->range_table_dev, n * sizeof(RangeScanItem)));
+        HIPCHK(h, hipMalloc(&h->range_rec_dev, n * sizeof(RangeScanRecord)));
+        HIPCHK(h, hipHostMalloc(&h->range_rec_host, n * (sizeof(RangeScanRecord) + sizeof(RangeScanItem)), hipHostMallocDefault));
+        h->range_cap = n;
+        h->total_bytes += n * (sizeof(RangeScanItem) + sizeof(RangeScanRecord));
+        h->range_table_stale = true;
+    }
+    int max_rows = 1;
+    for (const auto& e : h->range_plan) max_rows = std::max(max_rows, e.item.B * e.item.r);
+    if (h->range_table_stale) {
+        RangeScanItem* stage = reinterpret_cast<RangeScanItem*>(h->range_rec_host + h->range_cap);
+        for (size_t k = 0; k < n; ++k) stage[k] = h->range_plan[k].item;
+        HIPCHK(h, hipMemcpyAsync(h->range_table_dev, stage, n * sizeof(RangeScanItem), hipMemcpyHostToDevice, s));
+        h->range_table_stale = false;
+    }
+    HIPCHK(h, hipMemsetAsync(h->range_rec_dev, 0, n * sizeof(RangeScanRecord), s));
+    HIPCHK(h, launch_range_scan(h->range_table_dev, (int)n, h->range_rec_dev, max_rows, s));
+    HIPCHK(h, hipMemcpyAsync(h->range_rec_host, h->range_rec_dev, n * sizeof(RangeScanRecord), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipEventRecord(h->range_done, s));
+    return MSR_OK;
+}
+
+int msr_range_read(msr_handle* h, msr_range_stat* out, int32_t cap, int32_t* n) {
+    if (!h || !n || cap < 0 || (cap > 0 && !out)) return MSR_ERR_INVALID;
+    if (!h->range_enqueued) return fail(h, MSR_ERR_STATE, "msr_range_read: no msr_range_scan was enqueued");
+    const size_t cnt = h->range_plan.size();
+    if (cnt && h->range_done) HIPCHK(h, hipEventSynchronize(h->range_done));
+    *n = (int32_t)cnt;
+    for (size_t k = 0; k < cnt && (int32_t)k < cap; ++k) {
+        const auto& e = h->range_plan[k];
+        range_fill(out + k, e.tensor, e.item.format, e.producer, h->range_rec_host[k]);
+    }
+    return MSR_OK;
+}
+
+int msr_range_embed_bounds(msr_handle* h, msr_range_stat* out, int32_t cap, int32_t* n) {
+    if (!h || !n || cap < 0 || (cap > 0 && !out)) return MSR_ERR_INVALID;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    int rc = ensure_plan(h);
+    if (rc) return rc;
+    *n = (int32_t)h->range_embeds.size();
+    for (size_t k = 0; k < h->range_embeds.size() && (int32_t)k < cap; ++k) {
+        const auto& e = h->range_embeds[k];
+        const auto w = h->host_small.find(e.kernel);
+        const auto b = h->host_small.find(e.kernel.substr(0, e.kernel.size() - 6) + "bias");
+        if (w == h->host_small.end() || b == h->host_small.end() || w->second.size() != 18 * 128 || b->second.size() != 128)
+            return fail(h, MSR_ERR_STATE, "msr_range_embed_bounds: no host copy of %s", e.kernel.c_str());
+        // HWIO [3, 3, 2, 128]: |embedding_c| <= 0.5 * sum |w[., ., ., c]| + |b_c| for inputs in [-0.5, 0.5]
+        double worst = 0.0;
+        for (int c = 0; c < 128; ++c) {
+            double sum = 0.0;
+            for (int t = 0; t < 18; ++t) sum += std::fabs((double)w->second[(size_t)t * 128 + c]);
+            worst = std::max(worst, 0.5 * sum + std::fabs((double)b->second[c]));
+        }
+        RangeScanRecord r{};
+        const float bound = (float)worst;
+        std::memcpy(&r.max_abs_bits, &bound, sizeof(float));
+        range_fill(out + k, e.kernel, MSR_RANGE_FORMAT_EMBED, e.producer, r);
+    }
+    return MSR_OK;
+}
+
+int msr_op_range_scan(msr_handle* h, const void* img_dev, int32_t format, int32_t B, int32_t r, int32_t C, int32_t padded,
+                      msr_range_stat* out_stat, void* stream) {
+    if (!h) return MSR_ERR_INVALID;
+    if (!img_dev || !out_stat) return fail(h, MSR_ERR_INVALID, "msr_op_range_scan: null argument");
+    if (format < 2 || format > 5) return fail(h, MSR_ERR_INVALID, "msr_op_range_scan: format %d is not 2, 3, 4 or 5", format);
+    if (B < 1 || r < 1 || C < 32 || C % 32 || (int64_t)B * r > (1 << 24) || (int64_t)r * C > (1 << 24))
+        return fail(h, MSR_ERR_INVALID, "msr_op_range_scan: bad shape B=%d r=%d C=%d (C a multiple of 32)", B, r, C);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    const RangeScanItem item{img_dev, format, B, r, C, format == 3 ? fp8_pad(C) : 4 * C, padded != 0, 0};
+    char* buf = nullptr;     // [record | item]
+    HIPCHK(h, hipMalloc(&buf, sizeof(RangeScanRecord) + sizeof(RangeScanItem)));
+    RangeScanRecord rec{};
+    hipError_t e = hipMemsetAsync(buf, 0, sizeof(RangeScanRecord), s);
+    if (e == hipSuccess) e = hipMemcpyAsync(buf + sizeof(RangeScanRecord), &item, sizeof item, hipMemcpyHostToDevice, s);
+    if (e == hipSuccess)
+        e = launch_range_scan(reinterpret_cast<const RangeScanItem*>(buf + sizeof(RangeScanRecord)), 1,
+                              reinterpret_cast<RangeScanRecord*>(buf), B * r, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    if (e == hipSuccess) e = hipMemcpy(&rec, buf, sizeof rec, hipMemcpyDeviceToHost);
+    hipFree(buf);
+    if (e != hipSuccess) return fail(h, MSR_ERR_DEVICE, "msr_op_range_scan failed: %s", hipGetErrorString(e));
+    range_fill(out_stat, "", format, -1, rec);
     return MSR_OK;
 }
 

@@ -447,4 +447,24 @@ hipError_t launch_halo_merge(const float* wa, const float* ma, const float* sa, 
 hipError_t launch_resize_area(const float* src, int h, int w, float* dst, int dh, int dw, int factor, hipStream_t s);
 hipError_t launch_resize_cubic(const float* src, int h, int w, float* dst, int dh, int dw, hipStream_t s);
 
+// ---------------------------------------------------------------------------------------------
+// Activation-range scan (range_scan.hip): one launch over a device table of narrow activation images
+// ---------------------------------------------------------------------------------------------
+struct RangeScanItem {
+    const void* base;      // first byte of the tensor (of its zero border when padded)
+    int format;            // the planner's out_split: 2 split-fp16, 3 bf8 bytes, 4 f16c, 5 f16c6
+    int B, r, C;           // [B, r, r, C] interior, C % 32 == 0
+    int px_bytes;          // bytes per pixel: 4 * C for the chunk formats, the padded channel count for bf8
+    int padded;            // != 0: zero-bordered [B, r + 2, r + 2, .]
+    int record;            // index of the tensor's record
+};
+struct RangeScanRecord {   // zeroed before a scan
+    unsigned max_abs_bits;             // bits of the fp32 value of the largest finite |main piece|
+    unsigned pad_;
+    unsigned long long n_total, n_cross_clipped, n_clamped, n_nonfinite;
+};
+// max_rows = the largest B * r of the table (the grid is CUs * 4 workgroups, at most that).
+hipError_t launch_range_scan(const RangeScanItem* table_dev, int n_items, RangeScanRecord* rec_dev, int max_rows,
+                             hipStream_t s);
+
 }  // namespace msr

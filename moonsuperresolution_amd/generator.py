@@ -30,6 +30,67 @@ def parse_conv_forms(text: str) -> list:
     return ops
 
 
+F16_MAX = 65504.0
+
+
+class RangeReport:
+    """Result of an activation-range scan (msr_range_scan): ``records`` — one dict per narrow activation tensor of the plan, in
+    plan order (tensor, format, producer, max_abs, n_total, n_cross_clipped, n_clamped, n_nonfinite); ``embed_bounds`` — one dict
+    per conv_gb_resident op, whose embedding cannot be scanned (max_abs holds the host-side bound); ``layers`` — producer index
+    -> the producing layer's weight name, for the text.
+
+    ``regime`` follows tests/test_gpu_conv_kernel.py::test_f16c_saturation_regimes: "clamped" if any tensor holds a clamped or
+    non-finite element or an embed bound exceeds 65504 (finite and wrong), else "degraded" if any e4m3 cross piece is clipped
+    (the conv drops to one fp16 product), else "parity".  An empty report (fp32, bf16x3: no narrow tensor) is "parity"."""
+
+    def __init__(self, records=(), embed_bounds=(), layers=None):
+        self.records = [dict(r) for r in records]
+        self.embed_bounds = [dict(r) for r in embed_bounds]
+        self.layers = dict(layers or {})
+
+    @property
+    def regime(self) -> str:
+        if any(r["n_clamped"] + r["n_nonfinite"] > 0 for r in self.records) or \
+                any(not (e["max_abs"] <= F16_MAX) for e in self.embed_bounds):
+            return "clamped"
+        if any(r["n_cross_clipped"] > 0 for r in self.records):
+            return "degraded"
+        return "parity"
+
+    @property
+    def worst(self) -> Optional[dict]:
+        """The record that decides the regime: most clamped + non-finite elements, then most clipped cross pieces, then the
+        largest max_abs; the first in plan order among equals.  None for an empty report."""
+        if not self.records:
+            return None
+        key = lambda r: (r["n_clamped"] + r["n_nonfinite"], r["n_cross_clipped"], float(r["max_abs"]))   # noqa: E731
+        best = self.records[0]
+        for r in self.records[1:]:
+            if key(r) > key(best):
+                best = r
+        return best
+
+    def flagged(self) -> list:
+        """Names of the tensors with any clipped, clamped or non-finite element, in plan order."""
+        return [r["tensor"] for r in self.records if r["n_cross_clipped"] + r["n_clamped"] + r["n_nonfinite"] > 0]
+
+    def __str__(self) -> str:
+        w = self.worst
+        if w is None:
+            return "activation range: parity (no narrow activation tensor in this plan)"
+        layer = self.layers.get(w["producer"], "?")
+        text = (f"activation range: {self.regime}; worst tensor {w['tensor']} (format {w['format']}, written by op "
+                f"{w['producer']}, {layer}): max |a| = {float(w['max_abs']):.6g}, {w['n_cross_clipped']} cross-clipped (|a| > 464), "
+                f"{w['n_clamped']} clamped, {w['n_nonfinite']} non-finite of {w['n_total']} elements; "
+                f"{len(self.flagged())} of {len(self.records)} tensors flagged")
+        over = [e for e in self.embed_bounds if not (e["max_abs"] <= F16_MAX)]
+        if over:
+            text += f"; embedding bound of {over[0]['tensor']} is {float(over[0]['max_abs']):.6g} > 65504"
+        return text
+
+    __repr__ = __str__
+
+
 class Generator:
     """MI355X generator(call).
 
@@ -53,16 +114,38 @@ class Generator:
             mode of round 3: the f16c data path with the cross terms left out of the two big kernels (one fp16 product
             per element; error stated in tests/test_gpu_baseline_configs.py).  Inputs, outputs, weights and
             every non-conv op (moments, normalisation, epilogues, dense, head) are fp32 in every mode.
+            "auto" builds "f16c", runs one call on ``calibrate`` and scans the activation ranges (``range_report``); it keeps
+            f16c when the regime is "parity" and rebuilds as "bf16x3" from the same weights otherwise.  ``.precision`` then
+            reads the mode chosen and ``.range`` the report that decided it; ``clone()`` clones the chosen mode.
+        calibrate: the batch [batch_size, S, S, 2] "auto" calibrates on; None = ``synthetic_patches(batch_size, S, seed=0)``.
+            Calibration holds for the data it saw: ``DEMSuperResolution(range_check=...)`` checks real tiles.
     """
 
     def __init__(self, image_size: int, batch_size: int, latent_dim: int = 256, variant: str = "gaugan",
                  weights: Union[int, Mapping[str, np.ndarray]] = 1234, eps: Union[None, int, np.ndarray] = None,
-                 device: int = 0, precision: str = "f16c"):
+                 device: int = 0, precision: str = "f16c", calibrate=None):
         if variant not in VARIANTS:
             raise ValueError(f"unknown variant {variant!r}; expected one of {VARIANTS}")
+        if precision == "auto":
+            # resolved here, above the flag table: try the fast default, keep it only in the parity regime
+            if isinstance(weights, (int, np.integer)):
+                weights = make_weights(variant, image_size, latent_dim, seed=int(weights))
+            self.__init__(image_size, batch_size, latent_dim, variant, weights, eps, device, "f16c")
+            if calibrate is None:
+                from .weights import synthetic_patches
+                calibrate = synthetic_patches(batch_size, image_size, seed=0)
+            # the sampler noise of the calibration call: the fixed one if the caller gave one, else a seeded draw (repeatable)
+            noise = None if self._eps_fixed is not None else make_latent_noise(batch_size, latent_dim)
+            report = self.range_report(calibrate, eps=noise)
+            if report.regime != "parity":
+                self.close()
+                self.__init__(image_size, batch_size, latent_dim, variant, weights, eps, device, "bf16x3")
+            self.range = report
+            return
         if precision not in _lib.PRECISION_FLAGS:
-            raise ValueError(f"unknown precision {precision!r}; expected one of {tuple(_lib.PRECISION_FLAGS)}")
+            raise ValueError(f"unknown precision {precision!r}; expected one of {tuple(_lib.PRECISION_FLAGS) + ('auto',)}")
         self.precision = precision
+        self.range: Optional[RangeReport] = None
         self.image_size, self.batch_size, self.latent_dim, self.variant = image_size, batch_size, latent_dim, variant
         self._lib = _lib.load()
         if not torch.cuda.is_available():
@@ -97,6 +180,7 @@ class Generator:
         the matrix-bound tail of the other."""
         twin = Generator(weights=self._weights, **self._ctor)
         twin.weights_version = self.weights_version
+        twin.range = self.range                  # an "auto" generator's clone is the chosen mode, not calibrated again
         return twin
 
     # -- weights -----------------------------------------------------------------------------------
@@ -202,6 +286,44 @@ class Generator:
         rc = self._lib.msr_debug_conv_forms(self._h, buf, len(buf))
         _lib.raise_for(self._lib, self._h, rc, "msr_debug_conv_forms")
         return parse_conv_forms(buf.value.decode())
+
+    # -- activation ranges -----------------------------------------------------------------------------
+    def range_scan_async(self) -> None:
+        """Enqueue a scan of the last call's narrow activation tensors on torch's current stream (msr_range_scan); it must
+        be the stream of that call, ahead of the handle's next call.  ``range_read`` collects it."""
+        rc = self._lib.msr_range_scan(self._h, torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.raise_for(self._lib, self._h, rc, "msr_range_scan")
+
+    def _range_records(self, fn, what: str) -> list:
+        from .ops import range_stat_dict
+        cap = 256
+        arr = (_lib.MsrRangeStat * cap)()
+        n = C.c_int32()
+        _lib.raise_for(self._lib, self._h, fn(self._h, arr, cap, C.byref(n)), what)
+        return [range_stat_dict(arr[i]) for i in range(min(n.value, cap))]
+
+    def range_read(self) -> RangeReport:
+        """Wait for the last ``range_scan_async`` and return its RangeReport (with the embed bounds of the gbr ops)."""
+        records = self._range_records(self._lib.msr_range_read, "msr_range_read")
+        bounds = self._range_records(self._lib.msr_range_embed_bounds, "msr_range_embed_bounds") if records else []
+        layers = {}
+        if records:
+            forms = self.conv_forms()
+            for r in records:
+                layers[r["producer"]] = forms[r["producer"]].get("wt", "?")
+        return RangeReport(records, bounds, layers)
+
+    def range_report(self, batch=None, eps=None) -> RangeReport:
+        """Which regime of the narrow formats the last call ran in (RangeReport).  With ``batch`` [B, S, S, 2] (``eps`` as the
+        constructor's array form, for "gaugan"), one call is run on it first.  Modes without narrow tensors ("fp32", "bf16x3")
+        return an empty report whose regime is "parity"."""
+        with torch.cuda.device(self.device):
+            if batch is not None:
+                x = torch.from_numpy(np.ascontiguousarray(np.asarray(batch), dtype=np.float32)).to(self.device)
+                e = None if eps is None else torch.from_numpy(np.ascontiguousarray(eps, dtype=np.float32)).to(self.device)
+                self.forward_device(x, eps=e)
+            self.range_scan_async()
+            return self.range_read()
 
     # -- measurement ---------------------------------------------------------------------------------
     def forward_flops(self) -> float:

@@ -83,6 +83,7 @@ class HaloShardedSuperResolution(DEMSuperResolution):
                                          dmm.data_ptr(), meta.data_ptr(), stream)
             _lib.raise_for(lib, h, rc, "msr_compact_patches")
             nv, ncall = (int(v) for v in meta.cpu().tolist())
+            self._range_retire()                      # range_check: the previous band's scan, read with this band's counts
             preds = torch.empty((max(ncall * B, 1), S, S), dtype=torch.float32, device=dev)
             if self._gen is not None:
                 if self._gens is None:
@@ -98,6 +99,8 @@ class HaloShardedSuperResolution(DEMSuperResolution):
                                                      mm_sel[c * B:].data_ptr(), B, batches[k].data_ptr(), self._stream())
                         _lib.raise_for(lib, h, rc, "msr_extract_patches")
                         self._gens[k].forward_device(batches[k], out=preds[c * B:(c + 1) * B].unsqueeze(-1))
+                        if c == 0:
+                            self._range_enqueue(self._gens[k])
                 for ps in self._pstreams:
                     cur.wait_stream(ps)
                     for t in batches + [preds, sx, sy, mm_sel]:
@@ -199,6 +202,7 @@ class HaloShardedSuperResolution(DEMSuperResolution):
                 done += len(band)
                 del preds, keys, dmm                     # the band's predictions are not needed again
             acc = slab[:, lo - y_b0:hi - y_b0, :wp]
+        self._range_retire()                          # the last band's scan
         self.last_counts_halo = (nv_tot, nc_tot)
         self.last_band_rows = band_rows
         st = dict(rank=rank, world=world, acc=acc, lo=lo, hi=hi, own_lo=own_lo, own_hi=own_hi, wp=wp,

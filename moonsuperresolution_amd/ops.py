@@ -533,3 +533,63 @@ def head(ctx: OpContext, x: torch.Tensor, kernel: "np.ndarray", bias: float, slo
                              float(slope), 1 if transpose_tanh else 0, torch.cuda.current_stream(x.device).cuda_stream)
     _lib.raise_for(ctx.lib, ctx.h, rc, "msr_op_head")
     return out
+
+
+# ---- activation-range scan (csrc/range_scan.hip, include/moonsr.h msr_range_scan) ---------------------------------------------
+RANGE_FORMATS = (2, 3, 4, 5)        # out_split values with a finite range: split-fp16, bf8 bytes, f16c, f16c6
+F16_MAX, BF8_MAX = 65504.0, 57344.0
+
+
+def e4m3_cross_limit() -> float:
+    """The largest fp16 value whose e4m3 piece is not changed by the saturation at 448: the largest fp16 that
+    round-to-nearest-even takes to 448 (``torch.float8_e4m3fn`` has no 480: above the midpoint the conversion overflows).
+    It is 464, the midpoint of 448 and the 480 the grid would continue with; the tie goes to 448, whose mantissa is even."""
+    v = torch.arange(448, 513, 0.25, dtype=torch.float32).to(torch.float16)          # every fp16 of [448, 512]: spacing 0.25
+    ok = v.float().to(torch.float8_e4m3fn).float() == 448.0
+    return float(v[ok].max())
+
+
+def range_stats(img: torch.Tensor, fmt: int, padded: bool, channels: Optional[int] = None) -> dict:
+    """Host twin of the range scan, from the DECODED image: the record msr_op_range_scan / msr_range_scan give for one
+    activation image [B, r (+2), r (+2), .] in format ``fmt`` (2 split-fp16, 4 f16c, 5 f16c6: float32 storage, one slot per
+    channel; 3: bf8 bytes, ``channels`` real channels in a pixel padded with zero bytes).  The zero border of a padded image and
+    the padding channels are left out.  Returns max_abs (np.float32, the largest finite \\|main piece\\|) and the four counts."""
+    import numpy as np
+    if fmt not in RANGE_FORMATS:
+        raise ValueError(f"format {fmt} has fp32's range and is not scanned; expected one of {RANGE_FORMATS}")
+    img = img.detach().cpu().contiguous()
+    if padded:
+        img = img[:, 1:-1, 1:-1].contiguous()
+    if fmt == 3:
+        b = img.view(torch.uint8) if img.dtype != torch.uint8 else img
+        hi = b[..., :channels if channels is not None else b.shape[-1]].contiguous().view(torch.float8_e5m2).double()
+        top = BF8_MAX
+    elif fmt == 4:
+        hi, top = f16c_decode(img)[0], F16_MAX
+    elif fmt == 5:
+        hi, top = f16c6_decode(img)[0], F16_MAX
+    else:
+        words = img.view(torch.int16).reshape(-1, 2, 32)                       # [chunk][hi | lo][32]
+        hi, top = words[:, 0].contiguous().view(torch.float16).double(), F16_MAX
+    mag = hi.abs()
+    finite = torch.isfinite(mag)
+    cross = int((~(mag <= e4m3_cross_limit())).sum()) if fmt == 4 else 0       # a NaN piece is clipped as well
+    return dict(max_abs=np.float32(mag[finite].max()) if bool(finite.any()) else np.float32(0.0), n_total=int(mag.numel()),
+                n_cross_clipped=cross, n_clamped=int((mag == top).sum()), n_nonfinite=int((~finite).sum()))
+
+
+def range_stat_dict(rec) -> dict:
+    """An msr_range_stat (``_lib.MsrRangeStat``) as a dict; max_abs stays an np.float32 (compared bit for bit in the tests)."""
+    import numpy as np
+    return dict(tensor=rec.tensor.decode(), format=int(rec.format), producer=int(rec.producer), max_abs=np.float32(rec.max_abs),
+                n_total=int(rec.n_total), n_cross_clipped=int(rec.n_cross_clipped), n_clamped=int(rec.n_clamped),
+                n_nonfinite=int(rec.n_nonfinite))
+
+
+def range_scan(ctx: OpContext, img: torch.Tensor, fmt: int, B: int, r: int, channels: int, padded: bool) -> dict:
+    """One synchronous scan of a device image (msr_op_range_scan); the layout is what ``range_stats`` takes."""
+    rec = _lib.MsrRangeStat()
+    rc = ctx.lib.msr_op_range_scan(ctx.h, img.contiguous().data_ptr(), fmt, B, r, channels, 1 if padded else 0, C.byref(rec),
+                                   torch.cuda.current_stream(img.device).cuda_stream)
+    _lib.raise_for(ctx.lib, ctx.h, rc, "msr_op_range_scan")
+    return range_stat_dict(rec)

@@ -73,10 +73,21 @@ class DEMSuperResolution:
             reference's identity self-check (process_full_tiles.py:143).
         device: HIP device ordinal.
         as_implemented: keep the reference's aliased variance update; False = textbook West.
+        range_check: "off" (default: no call is added), "warn" or "raise" — with a ``Generator`` model, scan the activation
+            ranges of the FIRST generator call of every tile (``Generator.range_scan_async`` on that call's stream and handle)
+            and read the records where the next tile's two counts are read (after the last tile: when the run ends), so
+            the loop gains no host wait of its own.  A regime other than "parity" is kept in ``self.range_report`` and
+            warned about once per run ("warn"), or raises RuntimeError when that tile's records are read ("raise").
     """
 
     def __init__(self, config: DSRConfig, model: Callable = lambda x, training=False: x, device: int = 0,
-                 as_implemented: bool = True, pipeline: int = 2) -> None:
+                 as_implemented: bool = True, pipeline: int = 2, range_check: str = "off") -> None:
+        if range_check not in ("off", "warn", "raise"):
+            raise ValueError(f"range_check must be 'off', 'warn' or 'raise', got {range_check!r}")
+        self.range_check = range_check
+        self.range_report = None                     # the first non-parity RangeReport of a run (else the last one read)
+        self._range_pending = None                   # the handle whose scan has not been read yet
+        self._range_warned = False
         self.map_name = config.map_name
         self.save_path = config.save_path
         self.folder_path = config.source_folder_path
@@ -327,6 +338,7 @@ class DEMSuperResolution:
         lib, h, dev = self._lib, self._h, self.device
         rows, cols = self.dem_padded_shape
         st["event"].synchronize()                     # 8 bytes; the GPU keeps working on what is already queued
+        self._range_retire()                          # the previous tile's scan (range_check), read at the same point
         nv, ncall = (int(v) for v in st["meta_host"].tolist())
         total = ncall * B
         sx, sy, mm_sel = st["sx"], st["sy"], st["mm_sel"]
@@ -367,6 +379,8 @@ class DEMSuperResolution:
                         _lib.raise_for(lib, h, rc, "msr_extract_patches")
                         self._gens[k].forward_device(batches[k], out=preds[c * B:(c + 1) * B].unsqueeze(-1),
                                                      gate=self._gate if gated else None)
+                        if c == 0:
+                            self._range_enqueue(self._gens[k])
                         if gated:
                             self._gate_ring = (self._gate_ring + 1) % len(self._gate_events)
                             self._gate = self._gate_events[self._gate_ring]
@@ -389,6 +403,32 @@ class DEMSuperResolution:
                 out = np.array(self.model(batch.cpu().numpy(), training=False))[:, :, :, -1]
                 preds[c * B:(c + 1) * B] = torch.from_numpy(np.ascontiguousarray(out, dtype=np.float32)).to(dev)
             return self.rebuildTile(preds, st["keys"], st["dmm"], nv)
+
+    # -- range_check: one scan per tile, read one tile late -------------------------------------------------------------
+    def _range_enqueue(self, gen) -> None:
+        """After the first generator call of a tile, on that call's stream (the current one): scan its activations."""
+        if self.range_check == "off":
+            return
+        gen.range_scan_async()
+        self._range_pending = gen
+
+    def _range_retire(self) -> None:
+        """Read the outstanding scan, if any, and act on its regime."""
+        gen, self._range_pending = self._range_pending, None
+        if gen is None:
+            return
+        report = gen.range_read()
+        if self.range_report is None or self.range_report.regime == "parity":
+            self.range_report = report
+        if report.regime == "parity":
+            return
+        if self.range_check == "raise":
+            raise RuntimeError(f"range_check: {report}")
+        if not self._range_warned:
+            import warnings
+            self._range_warned = True
+            warnings.warn(f"range_check: {report}; the f16c family is outside its parity regime for these weights: use "
+                          "precision='bf16x3' or precision='auto'", RuntimeWarning, stacklevel=2)
 
     def _tile_buffers(self, cap: int):
         """Two persistent prediction buffers [cap, S, S] used by alternate tiles, and one input batch per handle."""
@@ -446,11 +486,13 @@ class DEMSuperResolution:
         tiles = list(tiles)
         if not tiles:
             return
+        self._range_warned = False                    # one warning per run
         nxt = self._prepare_tile(*tiles[0])
         for i, (xx, yy) in enumerate(tiles):
             st = nxt
             nxt = self._prepare_tile(*tiles[i + 1]) if i + 1 < len(tiles) else None
             yield (xx, yy), self._generate_tile(st)
+        self._range_retire()                          # the last tile's scan
 
     def processTiles(self, tiles: Sequence[Tuple[int, int]]):
         """Process a list of tiles (this rank's shard); returns {(xx,yy): (mean, std, good)} of host arrays.
