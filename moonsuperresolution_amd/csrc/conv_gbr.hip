@@ -116,7 +116,7 @@ conv_gb_resident(const GbrParams p, const GbrGeom g) {
     const char* const SLd[3] = {SL + (cg < 2 ? 0 : 16), SL + (cg < 2 ? 0 : (4 * 2 * 18 - 2) * 16),
                                 SL + (cg < 2 ? 0 : (2 * 18 - 2 * 4 * 2 * 18 - 2) * 16)};
     char* const stage = smem + GB_STAGE_OFF + wq * GB_STAGE_WAVE;
-    // Weight stream (GbrParams.wt, built by the host: api.hip gbr_weight_stream / ops.gbr_weight_image): for channel block nt,
+    // Weight stream (GbrParams.wt, built by the host: weight_images.hip gbr_weight_stream / ops.gbr_weight_image): for channel block nt,
     // wave q and tap pair P (K-steps 2P, 2P + 1 of the 36-step chunk-major sequence) 8 KB = [column block j][piece][lane] x 16 B
     // with piece 0 / 1 = the fp16 fragments of the even / odd tap, 2 / 3 = the two halves of the lane's fp6 piece: every load
     // instruction reads 1 KB of consecutive bytes (8 whole cache lines; the [tap][row][chunk] image made the fp6 loads touch

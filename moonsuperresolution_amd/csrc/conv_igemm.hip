@@ -1966,23 +1966,32 @@ int conv_pick_ksplit(int M, int N, int ksteps, int tile, int prec) {
     return ks;
 }
 
+// The finishing pass of every split-K launch: sums the K ranges of p.partial and applies epilogue `epi` (bias, residual,
+// SPADE or affine), with the output's moments in the same launch when the plan asked for them (p.mom_mean).
+static hipError_t finish_splitk(const ConvParams& p, int epi, hipStream_t s) {
+    if (p.mom_mean) return launch_splitk_epilogue_mom(p, epi, s);      // epilogue + the output's moments, one launch
+    const int Cout = epi == EPI_SPADE ? p.N / 2 : p.N;
+    long eb = ((long)p.B * p.Hout * p.Wout * (Cout / 4) + 255) / 256;
+    if (eb > 4096) eb = 4096;
+    switch (epi) {
+        case EPI_BIAS: splitk_epilogue_kernel<EPI_BIAS><<<(int)eb, 256, 0, s>>>(p); break;
+        case EPI_RES: splitk_epilogue_kernel<EPI_RES><<<(int)eb, 256, 0, s>>>(p); break;
+        case EPI_SPADE: splitk_epilogue_kernel<EPI_SPADE><<<(int)eb, 256, 0, s>>>(p); break;
+        case EPI_AFFINE: splitk_epilogue_kernel<EPI_AFFINE><<<(int)eb, 256, 0, s>>>(p); break;
+        default: return hipErrorInvalidValue;
+    }
+    return hipGetLastError();
+}
+
 template <int WM, int WN, int MT, int NT, int BKC, int PREC>
 static hipError_t launch_cfg(const ConvParams& p, int epi, hipStream_t s) {
     using C = TileCfg<WM, WN, MT, NT, BKC>;
     TileGeom g;
     if (!make_geom(p, C::BM, C::BN, BKC, g)) return hipErrorInvalidValue;
     if (p.ksplit > 1) {
-        if (!p.partial || epi == EPI_PARTIAL) return hipErrorInvalidValue;
+        if (!p.partial || (epi != EPI_BIAS && epi != EPI_RES && epi != EPI_SPADE && epi != EPI_AFFINE)) return hipErrorInvalidValue;
         conv_igemm<WM, WN, MT, NT, BKC, EPI_PARTIAL, PREC><<<g.tiles_mn * p.ksplit, C::NTHR, C::LDS, s>>>(p, g);
-        if (p.mom_mean) return launch_splitk_epilogue_mom(p, epi, s);      // epilogue + the output's moments, one launch
-        const int Cout = epi == EPI_SPADE ? p.N / 2 : p.N;
-        long eb = ((long)p.B * p.Hout * p.Wout * (Cout / 4) + 255) / 256;
-        if (eb > 4096) eb = 4096;
-        if (epi == EPI_BIAS) splitk_epilogue_kernel<EPI_BIAS><<<(int)eb, 256, 0, s>>>(p);
-        else if (epi == EPI_RES) splitk_epilogue_kernel<EPI_RES><<<(int)eb, 256, 0, s>>>(p);
-        else if (epi == EPI_AFFINE) splitk_epilogue_kernel<EPI_AFFINE><<<(int)eb, 256, 0, s>>>(p);
-        else splitk_epilogue_kernel<EPI_SPADE><<<(int)eb, 256, 0, s>>>(p);
-        return hipGetLastError();
+        return finish_splitk(p, epi, s);
     }
     const int grid = g.tiles_mn;
     switch (epi) {
@@ -2011,16 +2020,9 @@ static hipError_t launch_bf16x3(const ConvParams& p, int epi, hipStream_t s) {
     if (!make_geom(p, C::BM, C::BN, 32, g)) return hipErrorInvalidValue;
     const int grid = g.tiles_mn * (p.ksplit > 1 ? p.ksplit : 1);
     if (p.ksplit > 1) {
-        if (!p.partial || epi == EPI_PARTIAL) return hipErrorInvalidValue;
+        if (!p.partial || (epi != EPI_BIAS && epi != EPI_RES && epi != EPI_SPADE)) return hipErrorInvalidValue;   // no affine form
         conv_igemm_bf16x3<WM, WN, MT, NT, EPI_PARTIAL><<<grid, C::NTHR, C::LDS, s>>>(p, g);
-        if (p.mom_mean) return launch_splitk_epilogue_mom(p, epi, s);      // epilogue + the output's moments, one launch
-        const int Cout = epi == EPI_SPADE ? p.N / 2 : p.N;
-        long eb = ((long)p.B * p.Hout * p.Wout * (Cout / 4) + 255) / 256;
-        if (eb > 4096) eb = 4096;
-        if (epi == EPI_BIAS) splitk_epilogue_kernel<EPI_BIAS><<<(int)eb, 256, 0, s>>>(p);
-        else if (epi == EPI_RES) splitk_epilogue_kernel<EPI_RES><<<(int)eb, 256, 0, s>>>(p);
-        else splitk_epilogue_kernel<EPI_SPADE><<<(int)eb, 256, 0, s>>>(p);
-        return hipGetLastError();
+        return finish_splitk(p, epi, s);
     }
     switch (epi) {
         case EPI_BIAS: conv_igemm_bf16x3<WM, WN, MT, NT, EPI_BIAS><<<grid, C::NTHR, C::LDS, s>>>(p, g); break;
@@ -2096,21 +2098,14 @@ static hipError_t launch_pp(const ConvParams& p, int epi, hipStream_t s) {
     if (ksn > 1) {
         // few tiles: K ranges fill the chip, raw accumulators go to the split-K workspace, one more pass finishes
         if (!p.partial || (p.prec != PREC_BF16X3 && p.prec != PREC_F16C)) return hipErrorInvalidValue;     // K ranges: 3-term and f16c forms
+        if (epi != EPI_BIAS && epi != EPI_RES && epi != EPI_SPADE) return hipErrorInvalidValue;            // no affine form
         if (p.prec == PREC_F16C) {
             if (!p.wexp) return hipErrorInvalidValue;
             conv_igemm_bf16x3_pp<EPI_PARTIAL, PP_F16C><<<grid, 512, PP_LDS, s>>>(p, g);
         } else {
             conv_igemm_bf16x3_pp<EPI_PARTIAL, PP_BF16X3><<<grid, 512, PP_LDS, s>>>(p, g);
         }
-        if (p.mom_mean) return launch_splitk_epilogue_mom(p, epi, s);      // epilogue + the output's moments, one launch
-        const int Cout = epi == EPI_SPADE ? p.N / 2 : p.N;
-        long eb = ((long)p.B * p.Hout * p.Wout * (Cout / 4) + 255) / 256;
-        if (eb > 4096) eb = 4096;
-        if (epi == EPI_BIAS) splitk_epilogue_kernel<EPI_BIAS><<<(int)eb, 256, 0, s>>>(p);
-        else if (epi == EPI_RES) splitk_epilogue_kernel<EPI_RES><<<(int)eb, 256, 0, s>>>(p);
-        else if (epi == EPI_SPADE) splitk_epilogue_kernel<EPI_SPADE><<<(int)eb, 256, 0, s>>>(p);
-        else return hipErrorInvalidValue;
-        return hipGetLastError();
+        return finish_splitk(p, epi, s);
     }
     if (p.prec == PREC_F16X2) {
         if (epi != EPI_SPADE) return hipErrorInvalidValue;     // the 2-term form exists for the gamma|beta convs only

@@ -1,0 +1,228 @@
+// debug_entries.hip — what a test or a tool reads back from a handle: device tensors by name, the planned forms as text
+// (msr_debug_*), the activation-range scan (msr_range_*) and the device-memory total.
+#include "host.h"
+
+using namespace msr;
+
+void msr::range_fill(msr_range_stat* o, const std::string& tensor, int format, int producer, const RangeScanRecord& r) {
+    std::memset(o, 0, sizeof *o);
+    snprintf(o->tensor, sizeof o->tensor, "%s", tensor.c_str());
+    o->format = format;
+    o->producer = producer;
+    std::memcpy(&o->max_abs, &r.max_abs_bits, sizeof(float));
+    o->n_total = (int64_t)r.n_total;
+    o->n_cross_clipped = (int64_t)r.n_cross_clipped;
+    o->n_clamped = (int64_t)r.n_clamped;
+    o->n_nonfinite = (int64_t)r.n_nonfinite;
+}
+
+extern "C" {
+
+int msr_debug_tensor(msr_handle* h, const char* name, float* host_out, int64_t count) {
+    if (!h || !name || !host_out) return MSR_ERR_INVALID;
+    auto it = h->dev.find(name);
+    if (it == h->dev.end()) return fail(h, MSR_ERR_INVALID, "no tensor named '%s'", name);
+    if (count < 0 || (size_t)count * sizeof(float) > h->dev_bytes[name])
+        return fail(h, MSR_ERR_INVALID, "%s holds %zu floats, %lld requested", name, h->dev_bytes[name] / sizeof(float),
+                    (long long)count);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, hipDeviceSynchronize());
+    HIPCHK(h, hipMemcpy(host_out, it->second, (size_t)count * sizeof(float), hipMemcpyDeviceToHost));
+    return MSR_OK;
+}
+
+int msr_debug_moment_forms(msr_handle* h, char* out, int64_t cap) {
+    if (!h || !out || cap < 1) return MSR_ERR_INVALID;
+    // one line "<mean tensor> <form>" per planned moments site, in plan order.  Forms: A moments kernels over the tensor,
+    // B split-K epilogue, E1 / E2 one- / two-stage slab finalize after the slabs of the conv_igemm epilogue (/C) or of
+    // the ping-pong / stream kernels (/D)
+    auto tensor_of = [&](const float* ptr) -> std::string {
+        const char* nm = name_of(h, ptr);
+        return nm ? nm : "?";
+    };
+    std::string txt;
+    for (size_t i = 0; i < h->ops.size(); ++i) {
+        const Op& op = h->ops[i];
+        if (op.type == OP_MOMENTS) {
+            txt += tensor_of(op.mom.mean) + " A\n";
+        } else if (op.type == OP_CONV && op.conv.mom_mean) {
+            txt += tensor_of(op.conv.mom_mean) + " B\n";
+        } else if (op.type == OP_MOMENTS_SLABS && i > 0) {
+            const bool two = op.mom.P >= 512;
+            txt += tensor_of(op.mom.mean) + (two ? " E2/" : " E1/") + (h->ops[i - 1].tile == TILE_256x128_PP ? "D\n" : "C\n");
+        }
+    }
+    if ((int64_t)txt.size() + 1 > cap) return fail(h, MSR_ERR_INVALID, "msr_debug_moment_forms: %zu bytes needed", txt.size() + 1);
+    memcpy(out, txt.c_str(), txt.size() + 1);
+    return MSR_OK;
+}
+
+int msr_debug_conv_forms(msr_handle* h, char* out, int64_t cap) {
+    if (!h || !out || cap < 1) return MSR_ERR_INVALID;
+    // one line of "key=value" words per planned op, in plan order (moonsr.h).  Tensors are named by the handle's reverse
+    // lookup; a pointer into a buffer (a stride-2 conv reads from the interior of its padded input) names the buffer.
+    auto tensor_of = [&](const void* ptr) -> std::string {
+        if (!ptr) return "-";
+        const char* nm = name_of(h, ptr);
+        return nm ? nm : "?";
+    };
+    static const char* kImg[] = {"F32", "BF16", "BF16_FRAG", "F16", "FP8", "F16C", "F16C6", "GBR"};
+    auto img_of = [&](const std::string& key) -> const char* {
+        auto it = h->dev_img.find(key);
+        return it == h->dev_img.end() ? "?" : kImg[it->second];
+    };
+    std::string txt;
+    char b[1024];
+    for (const Op& op : h->ops) {
+        switch (op.type) {
+            case OP_CONV: {
+                const ConvParams& c = op.conv;
+                const std::string wt = tensor_of(c.wt);
+                snprintf(b, sizeof b, "kind=conv in=%s wt=%s wexp=%s bias=%s aux=%s mean=%s std=%s out=%s prec=%d tile=%d ksplit=%d "
+                         "wt_frag=%d no_cross=%d epi=%d out_split=%d ranges=0 img=%s B=%d r=%d cin=%d N=%d stride=%d aux_shift=%d "
+                         "stat_slabs=%d mom=%s\n", tensor_of(c.in).c_str(), wt.c_str(), tensor_of(c.wexp).c_str(),
+                         tensor_of(c.bias).c_str(), tensor_of(c.aux).c_str(), tensor_of(c.mean).c_str(), tensor_of(c.stdv).c_str(),
+                         tensor_of(c.out).c_str(), c.prec, op.tile, c.ksplit, c.wt_frag, c.no_cross, op.epi, c.out_split,
+                         img_of(wt), c.B, c.Hout, c.Cin, c.N, c.stride, c.aux_shift, op.stat_slabs, tensor_of(c.mom_mean).c_str());
+                break;
+            }
+            case OP_GBR: {
+                const GbrParams& q = op.gbr;
+                const std::string wt = tensor_of(q.wt);
+                snprintf(b, sizeof b, "kind=gbr in=input wt=%s embed=%s embed16=%s embed_bias=%s bias=%s aux=%s mean=%s std=%s out=%s "
+                         "prec=%d tile=%d ksplit=1 wt_frag=0 no_cross=%d epi=%d out_split=%d ranges=%d img=%s B=%d r=%d cin=128 N=%d "
+                         "stride=1 aux_shift=%d\n", wt.c_str(), tensor_of(q.we).c_str(), tensor_of(q.we16).c_str(),
+                         tensor_of(q.be).c_str(), tensor_of(q.bias).c_str(), tensor_of(q.aux).c_str(), tensor_of(q.mean).c_str(),
+                         tensor_of(q.stdv).c_str(), tensor_of(q.out).c_str(), (int)PREC_F16C6, (int)TILE_256x128_PP, q.no_cross,
+                         (int)EPI_SPADE, q.out_split, conv_gbr_ranges(q.B, q.r, q.N), img_of(wt), q.B, q.r, q.N, q.aux_shift);
+                break;
+            }
+            case OP_SMALLCIN: {
+                const SmallCinParams& p = op.sc;
+                snprintf(b, sizeof b, "kind=smallcin in=input wt=%s bias=%s out=%s out_split=%d B=%d r=%d N=%d stride=%d act=%d "
+                         "on_aux=%d\n", tensor_of(p.w).c_str(), tensor_of(p.bias).c_str(), tensor_of(p.out).c_str(), p.out_split, p.B,
+                         p.Hout, p.Cout, p.ay, p.act, op.on_aux ? 1 : 0);
+                break;
+            }
+            case OP_MOMENTS:
+            case OP_MOMENTS_SLABS:
+                snprintf(b, sizeof b, "kind=%s in=%s mean=%s std=%s\n", op.type == OP_MOMENTS ? "moments" : "moments_slabs",
+                         tensor_of(op.mom.x).c_str(), tensor_of(op.mom.mean).c_str(), tensor_of(op.mom.stdv).c_str());
+                break;
+            case OP_NORMACT:
+                snprintf(b, sizeof b, "kind=norm_act in=%s mean=%s std=%s gamma=%s beta=%s out=%s out_split=%d B=%d r=%d N=%d\n",
+                         tensor_of(op.na.x).c_str(), tensor_of(op.na.mean).c_str(), tensor_of(op.na.stdv).c_str(),
+                         tensor_of(op.na.gamma).c_str(), tensor_of(op.na.beta).c_str(), tensor_of(op.na.out).c_str(), op.na.out_split,
+                         op.na.B, op.na.H, op.na.C);
+                break;
+            case OP_DENSE:
+                snprintf(b, sizeof b, "kind=dense in=%s wt=%s bias=%s out=%s B=%d cin=%d N=%d\n", tensor_of(op.dense.x).c_str(),
+                         tensor_of(op.dense.W).c_str(), tensor_of(op.dense.bias).c_str(), tensor_of(op.dense.y).c_str(), op.dense.B,
+                         op.dense.K, op.dense.N);
+                break;
+            case OP_LATENT:
+                snprintf(b, sizeof b, "kind=latent in=%s aux=eps out=%s B=%d N=%d sampler=%d\n", tensor_of(op.lat.mv).c_str(),
+                         tensor_of(op.lat.z).c_str(), op.lat.B, op.lat.L, op.lat.sampler);
+                break;
+            case OP_HEAD:
+                snprintf(b, sizeof b, "kind=head in=%s wt=%s out=output B=%d r=%d cin=%d tanh=%d\n", tensor_of(op.head.x).c_str(),
+                         tensor_of(op.head.weff).c_str(), op.head.B, op.head.r, op.head.C, op.head.tanh_out);
+                break;
+            case OP_DIRECT:
+                snprintf(b, sizeof b, "kind=direct in=%s wt=%s out=%s B=%d r=%d N=%d\n", op.src_is_input ? "input" : tensor_of(op.dc.in0).c_str(),
+                         tensor_of(op.dc.w).c_str(), op.out_is_output ? "output" : tensor_of(op.dc.out).c_str(), op.dc.B, op.dc.Hout,
+                         op.dc.Cout);
+                break;
+        }
+        txt += b;
+    }
+    if ((int64_t)txt.size() + 1 > cap) return fail(h, MSR_ERR_INVALID, "msr_debug_conv_forms: %zu bytes needed", txt.size() + 1);
+    memcpy(out, txt.c_str(), txt.size() + 1);
+    return MSR_OK;
+}
+
+int msr_range_scan(msr_handle* h, void* stream) {
+    if (!h) return MSR_ERR_INVALID;
+    if (!h->forward_seen) return fail(h, MSR_ERR_STATE, "msr_range_scan: no msr_forward has run on this handle yet");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    const size_t n = h->range_plan.size();
+    h->range_enqueued = true;
+    if (n == 0) return MSR_OK;                       // fp32 / bf16x3 plans hold no narrow tensor
+    if (!h->range_done) HIPCHK(h, hipEventCreateWithFlags(&h->range_done, hipEventDisableTiming));
+    if (h->range_cap < n) {
+        // table (device), records (device, pinned host), and a pinned staging copy of the table behind the records
+        if (h->range_table_dev) { HIPCHK(h, hipFree(h->range_table_dev)); h->range_table_dev = nullptr; }
+        if (h->range_rec_dev) { HIPCHK(h, hipFree(h->range_rec_dev)); h->range_rec_dev = nullptr; }
+        if (h->range_rec_host) { HIPCHK(h, hipHostFree(h->range_rec_host)); h->range_rec_host = nullptr; }
+        h->total_bytes -= h->range_cap * (sizeof(RangeScanItem) + sizeof(RangeScanRecord));
+        h->range_cap = 0;
+        HIPCHK(h, hipMalloc(&h->range_table_dev, n * sizeof(RangeScanItem)));
+        HIPCHK(h, hipMalloc(&h->range_rec_dev, n * sizeof(RangeScanRecord)));
+        HIPCHK(h, hipHostMalloc(&h->range_rec_host, n * (sizeof(RangeScanRecord) + sizeof(RangeScanItem)), hipHostMallocDefault));
+        h->range_cap = n;
+        h->total_bytes += n * (sizeof(RangeScanItem) + sizeof(RangeScanRecord));
+        h->range_table_stale = true;
+    }
+    int max_rows = 1;
+    for (const auto& e : h->range_plan) max_rows = std::max(max_rows, e.item.B * e.item.r);
+    if (h->range_table_stale) {
+        RangeScanItem* stage = reinterpret_cast<RangeScanItem*>(h->range_rec_host + h->range_cap);
+        for (size_t k = 0; k < n; ++k) stage[k] = h->range_plan[k].item;
+        HIPCHK(h, hipMemcpyAsync(h->range_table_dev, stage, n * sizeof(RangeScanItem), hipMemcpyHostToDevice, s));
+        h->range_table_stale = false;
+    }
+    HIPCHK(h, hipMemsetAsync(h->range_rec_dev, 0, n * sizeof(RangeScanRecord), s));
+    HIPCHK(h, launch_range_scan(h->range_table_dev, (int)n, h->range_rec_dev, max_rows, s));
+    HIPCHK(h, hipMemcpyAsync(h->range_rec_host, h->range_rec_dev, n * sizeof(RangeScanRecord), hipMemcpyDeviceToHost, s));
+    HIPCHK(h, hipEventRecord(h->range_done, s));
+    return MSR_OK;
+}
+
+int msr_range_read(msr_handle* h, msr_range_stat* out, int32_t cap, int32_t* n) {
+    if (!h || !n || cap < 0 || (cap > 0 && !out)) return MSR_ERR_INVALID;
+    if (!h->range_enqueued) return fail(h, MSR_ERR_STATE, "msr_range_read: no msr_range_scan was enqueued");
+    const size_t cnt = h->range_plan.size();
+    if (cnt && h->range_done) HIPCHK(h, hipEventSynchronize(h->range_done));
+    *n = (int32_t)cnt;
+    for (size_t k = 0; k < cnt && (int32_t)k < cap; ++k) {
+        const auto& e = h->range_plan[k];
+        range_fill(out + k, e.tensor, e.item.format, e.producer, h->range_rec_host[k]);
+    }
+    return MSR_OK;
+}
+
+int msr_range_embed_bounds(msr_handle* h, msr_range_stat* out, int32_t cap, int32_t* n) {
+    if (!h || !n || cap < 0 || (cap > 0 && !out)) return MSR_ERR_INVALID;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    int rc = ensure_plan(h);
+    if (rc) return rc;
+    *n = (int32_t)h->range_embeds.size();
+    for (size_t k = 0; k < h->range_embeds.size() && (int32_t)k < cap; ++k) {
+        const auto& e = h->range_embeds[k];
+        const auto w = h->host_small.find(e.kernel);
+        const auto b = h->host_small.find(e.kernel.substr(0, e.kernel.size() - 6) + "bias");
+        if (w == h->host_small.end() || b == h->host_small.end() || w->second.size() != 18 * 128 || b->second.size() != 128)
+            return fail(h, MSR_ERR_STATE, "msr_range_embed_bounds: no host copy of %s", e.kernel.c_str());
+        // HWIO [3, 3, 2, 128]: |embedding_c| <= 0.5 * sum |w[., ., ., c]| + |b_c| for inputs in [-0.5, 0.5]
+        double worst = 0.0;
+        for (int c = 0; c < 128; ++c) {
+            double sum = 0.0;
+            for (int t = 0; t < 18; ++t) sum += std::fabs((double)w->second[(size_t)t * 128 + c]);
+            worst = std::max(worst, 0.5 * sum + std::fabs((double)b->second[c]));
+        }
+        RangeScanRecord r{};
+        const float bound = (float)worst;
+        std::memcpy(&r.max_abs_bits, &bound, sizeof(float));
+        range_fill(out + k, e.kernel, MSR_RANGE_FORMAT_EMBED, e.producer, r);
+    }
+    return MSR_OK;
+}
+
+int msr_device_bytes(const msr_handle* h, int64_t* bytes) {
+    if (!h || !bytes) return MSR_ERR_INVALID;
+    *bytes = (int64_t)h->total_bytes;
+    return MSR_OK;
+}
+
+}  // extern "C"

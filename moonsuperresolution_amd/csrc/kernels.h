@@ -1,4 +1,4 @@
-// Internal launch interface between the C-ABI layer (api.hip) and the gfx950 kernels.
+// Internal launch interface between the C-ABI layer (the host units of host.h) and the gfx950 kernels.
 // Everything here is MI355X-only HIP; there is no other backend.
 #pragma once
 #include <hip/hip_runtime.h>

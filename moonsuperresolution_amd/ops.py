@@ -367,7 +367,7 @@ GBR_PERM = [8 * (e >> 3) + 4 * (e & 1) + ((e >> 1) & 3) for e in range(32)]   # 
 def gbr_weight_image(w_kl: torch.Tensor) -> torch.Tensor:
     """gamma|beta weights [9][N][128] (kernel layout, spade_layout rows) -> the weight STREAM conv_gb_resident reads: the f16c6
     image with the input channels of every 32-chunk in the kernel's position order, re-ordered into the order its waves load
-    it: [channel block nt][wave q][tap pair P][column block j][piece][lane] x 16 bytes (csrc/conv_gbr.hip, api.hip
+    it: [channel block nt][wave q][tap pair P][column block j][piece][lane] x 16 bytes (csrc/conv_gbr.hip, weight_images.hip
     gbr_weight_stream).  Returned as float32 storage [9][N][128] (same byte count)."""
     N = w_kl.shape[1]
     idx = torch.tensor([32 * c + GBR_PERM[e] for c in range(w_kl.shape[2] // 32) for e in range(32)], device=w_kl.device)
@@ -421,7 +421,7 @@ def gbr_embed_image(we_hwio: torch.Tensor) -> torch.Tensor:
 
 def head_taps_upconv(k44c: torch.Tensor) -> torch.Tensor:
     """Head kernel [4, 4, C] (Conv2D(1, 4, 'same') after UpSampling2D(2), networks.py:54-56) -> the effective per-parity taps
-    weff[py][px][dy + 1][dx + 1][C] the head kernel reads (api.hip head_weff_upconv, uploaded as gen.head.weff): TF SAME for
+    weff[py][px][dy + 1][dx + 1][C] the head kernel reads (weight_images.hip head_weff_upconv, uploaded as gen.head.weff): TF SAME for
     k = 4 pads 1 before / 2 after, so output parity p reads half-resolution offsets {-1, 0, 0, +1} (p = 0) or {0, 0, +1, +1}
     (p = 1) for kh = 0..3; taps that land on the same pixel are added in fp32, in kh, kw order."""
     k = k44c.float().cpu()

@@ -1,7 +1,7 @@
 """GPU (-m gpu): oracle parity on the exact BASELINE.json configurations, in every conv arithmetic the library offers.
 
 The conv kernel a layer runs on is chosen from its shape (conv_igemm.hip: conv_pick_tile / conv_pick_ksplit on
-M = B * r^2; api.hip: conv_form / spade_form), so the B = 2 end-to-end tests of test_gpu_generator.py run other kernels
+M = B * r^2; forms.hip: conv_form / spade_form), so the B = 2 end-to-end tests of test_gpu_generator.py run other kernels
 for rb3-rb5 than bench.py does (split-K small tiles instead of the persistent ping-pong kernel with fused output
 moments).  These tests run the bench shapes themselves — GauGAN(256, 16), GauGAN(512, 8) and the production
 setting GauGAN(512, 12) of run_GAN.sh:24-26 — against the CPU restatement of GauGAN.call

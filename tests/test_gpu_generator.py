@@ -17,7 +17,7 @@ from tests.helpers import rel_linf
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 TOL = 1e-3
-# pix2pix runs every layer on the fp32 MFMA (api.hip plan_pix2pix): an fp32-class bound, like MODE_TOL["fp32"] of
+# pix2pix runs every layer on the fp32 MFMA (plan.hip plan_pix2pix): an fp32-class bound, like MODE_TOL["fp32"] of
 # tests/test_gpu_baseline_configs.py.  Measured 7.4e-7 (B = 1) and 5.4e-7 (B = 3) against the float64 oracle; 2.5e-6 = 3.4x.
 P2P_TOL = 2.5e-6
 

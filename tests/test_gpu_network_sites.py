@@ -73,7 +73,7 @@ CONFIGS = [(256, 16, "f16c", 0), (512, 8, "f16c", 0), (256, 16, "bf16x3", 0), (2
                                       # configurations above, and leaves rb5 / rb6 here (conv_gbr_ranges = 0: too few work items)
 
 # (kind, prec, tile, ksplit > 1, wt_frag, no_cross, out_split) the configurations must send to a checked site, from reading
-# api.hip conv_form / spade_form (kinds without a field carry 0):
+# forms.hip conv_form / spade_form (kinds without a field carry 0):
 REQUIRED_FORMS = {
     # f16c (spade_form, gbc && cvc): conv_gb_resident writes the f16c image; its consumer runs the stream kernel on whole tiles
     # (conv_sw.hip, Cin % 128 == 0) or K ranges of the ping-pong kernel + split-K pass where tiles < CUs (pp_ksplit > 1)
