@@ -91,6 +91,13 @@ typedef struct {
  *                     tests/test_gpu_baseline_configs.py::test_f16_mode_declared_tolerance (bound 3e-3 relative L-inf; it is
  *                     NOT inside north_star's 1e-3 and never the default). */
 #define MSR_FLAG_F16_MAIN 16
+/*   MSR_FLAG_BF16X3 | MSR_FLAG_F16C | MSR_FLAG_CROSS_FP6   opt-in: F16C with the cross terms of the main convs in fp6 e2m3
+ *                     with a power-of-two scale per pixel and 32 channels (1.5 MFMA-equivalents per product instead of 2; e2m3
+ *                     keeps e4m3's three mantissa bits, so it is the same parity grade).  It covers the consumers that run
+ *                     the stream kernel on whole tiles (Cin % 128 == 0); their SPADE layers keep conv_gb_resident, whose
+ *                     epilogue writes the fp6 image.  Not valid with MSR_FLAG_F16_MAIN (no cross terms to move); ignored for
+ *                     MSR_PIX2PIX.  Not the default: the measured A/B is in DESIGN.md. */
+#define MSR_FLAG_CROSS_FP6 32
 
 typedef struct msr_handle msr_handle;
 
@@ -300,6 +307,11 @@ int msr_op_spade_gbr(msr_handle* h, const float* src_dev, int32_t S, const float
                      const float* aux_dev, int32_t aux_shift, const float* mean_dev, const float* std_dev, void* stream);
 /* msr_op_spade_gbr in MSR_FLAG_F16_MAIN's form: the gamma|beta products are the fp16 main term alone (the fp6 cross pieces of
  * wt_dev are not read); the embedding (phase 1) is computed as in msr_op_spade_gbr.  Same arguments and checks. */
+/* msr_op_spade_gbr writing the f16c6 chunk image (MSR_FLAG_CROSS_FP6's form: fp16 | fp6 e2m3 pieces with one block scale per
+ * pixel and 32 channels, the input of msr_op_conv3x3_f16c with wexp_dev == NULL) into out_dev.  Same arguments and checks. */
+int msr_op_spade_gbr_f16c6(msr_handle* h, const float* src_dev, int32_t S, const float* we_dev, const float* be_dev,
+                           const float* wt_dev, const float* bias_dev, float* out_dev, int32_t B, int32_t r, int32_t N,
+                           const float* aux_dev, int32_t aux_shift, const float* mean_dev, const float* std_dev, void* stream);
 int msr_op_spade_gbr_f16(msr_handle* h, const float* src_dev, int32_t S, const float* we_dev, const float* be_dev,
                          const float* wt_dev, const float* bias_dev, float* out_dev, int32_t B, int32_t r, int32_t N,
                          const float* aux_dev, int32_t aux_shift, const float* mean_dev, const float* std_dev, void* stream);

@@ -22,6 +22,9 @@ VARIANT_IDS = {"gaugan": 0, "gaugan_no_kl": 1, "cnn": 2, "pix2pix": 3}
 # MSR_FLAG_F16C = 8: fp16 main term + fp8 cross terms in the chip-filling convs (parity-grade, 2 MFMA-equivalents per product)
 # MSR_FLAG_F16_MAIN = 16 (with F16C): the cross terms left out of the stream / resident kernels ("f16": declared tolerance)
 PRECISION_FLAGS = {"fp32": 0, "bf16x3": 1, "bf16x3_gbf16": 3, "fp8": 5, "f16c": 9, "f16": 25}
+# MSR_FLAG_CROSS_FP6 = 32 (with F16C, not F16_MAIN): the format of the cross terms in the stream-kernel consumers, or-ed into
+# the precision's flags (Generator(cross=...)); "fp8" is the f16c mode as it always was
+CROSS_FLAGS = {"fp8": 0, "fp6": 32}
 
 
 class MsrConfig(C.Structure):
@@ -85,6 +88,8 @@ SYMBOLS = [
     ("msr_op_spade_gbr", C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P]),
     ("msr_op_spade_gbr_f16", C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P,
                                        _P]),
+    ("msr_op_spade_gbr_f16c6", C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P,
+                                         _P]),
     ("msr_op_conv_smallcin", C.c_int, [_P, _P, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                        C.c_float, C.c_int32, C.c_int32, _P]),
     ("msr_op_norm_act", C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32,

@@ -270,6 +270,9 @@ int msr_create(const msr_config* cfg, msr_handle** out) {
     if ((cfg->flags & MSR_FLAG_F16_MAIN) && !(cfg->flags & MSR_FLAG_F16C))
         return fail(nullptr, MSR_ERR_INVALID, "MSR_FLAG_F16_MAIN modifies MSR_FLAG_F16C");
     h->f16m = h->f16c && (cfg->flags & MSR_FLAG_F16_MAIN);
+    if ((cfg->flags & MSR_FLAG_CROSS_FP6) && (!(cfg->flags & MSR_FLAG_F16C) || (cfg->flags & MSR_FLAG_F16_MAIN)))
+        return fail(nullptr, MSR_ERR_INVALID, "MSR_FLAG_CROSS_FP6 modifies MSR_FLAG_F16C and does not go with MSR_FLAG_F16_MAIN (which computes no cross terms)");
+    h->cross6 = h->f16c && (cfg->flags & MSR_FLAG_CROSS_FP6);
     if (cfg->variant == MSR_PIX2PIX) { h->prec = PREC_F32; h->gb_f16x2 = false; }   // the parity config runs on the fp32 MFMA
     build_specs(h.get());
     fill_forms(h.get());

@@ -78,9 +78,13 @@ struct GbrGeom {
 // NOX = true (GbrParams.no_cross, the "f16" mode): the fp6 cross terms are left out of the sweep — one fp16 product per
 // element (per-product error 2^-11; declared tolerance, include/moonsr.h MSR_FLAG_F16_MAIN).  Phase 1 and the weight
 // stream are unchanged; the cross pieces are not read.
-template <bool NOX>
+// F6OUT = true (GbrParams.out_split == 5): the SPADE epilogue writes the consumer's f16c6 chunk image (kernels.h PREC_F16C6)
+// instead of the f16c one.  A pixel's block scale spans the two waves that hold a chunk's 2 x 16 channels: they exchange
+// their per-pixel exponents once per channel block (below).  Everything else is the <false, false> kernel.
+template <bool NOX, bool F6OUT = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 conv_gb_resident(const GbrParams p, const GbrGeom g) {
+    static_assert(!(NOX && F6OUT), "the f16 mode's consumer reads no cross pieces");
     MSR_SATURATING_CONVERSIONS();
     constexpr int PH = GB_PH, HW = 18, HP = 324;
     constexpr int PD = GB_PD, PDC = GB_PDC;
@@ -505,6 +509,112 @@ conv_gb_resident(const GbrParams p, const GbrGeom g) {
             }
             // ---- SPADE epilogue: acc[i][0] = gamma, acc[i][1] = beta of channels ch .. ch + 3 at pixel (ty0 + i, x) ----
             GB_STAMP2()
+            if constexpr (F6OUT) {
+                // ---- the f16c6 image: per pixel and 32-channel chunk 32 x fp16 | 32 x h6 + scale | 32 x l6 + scale ----
+                // The block scale 2^E >= max|v| / 7.5 is taken over the chunk's 32 channels: 4 lanes (px + 16 cg) of this wave
+                // and 4 of its partner wq ^ 1.  e8m0(max) is monotonic in the maximum, so the exponent BYTES are exchanged:
+                //   pass 1  the 16 rows' values v (they replace x in its registers) and, per row, the exponent of the wave's 16
+                //           channels (two cross-lane steps); the lane's 16 exponent bytes go to the wave's exchange buffer
+                //   one workgroup barrier, then the partner's 16 bytes are read: exponent = the larger of the two
+                //   pass 2  the row pipeline of the f16c form with the scale known
+                // The reader of block n's bytes and the writer of block n + 1's sit between the same two barriers, so the
+                // buffer alternates with the block's parity: the 16 pad bytes of the 16 staged lines (even blocks), and 8
+                // bytes of the stage area's slack + the two dwords that the row pipeline leaves free in every line (odd).
+                typedef _Float16 h2 __attribute__((ext_vector_type(2)));
+                typedef unsigned u32x4a __attribute__((ext_vector_type(4), aligned(4)));
+                typedef unsigned u32x3a __attribute__((ext_vector_type(3), aligned(4)));
+                const float A[4] = {1.f / sq4.x, 1.f / sq4.y, 1.f / sq4.z, 1.f / sq4.w};
+                const float Bc[4] = {-mq4.x * A[0], -mq4.y * A[1], -mq4.z * A[2], -mq4.w * A[3]};
+                const int half = wq & 1;
+                const int par = (nt - nt0) & 1;
+                char* const line = stage + px * GB_LINE;
+                char* const pline = smem + GB_STAGE_OFF + (wq ^ 1) * GB_STAGE_WAVE + px * GB_LINE;      // the partner's
+                float4 vv[16];
+                unsigned ex[4] = {0u, 0u, 0u, 0u};                // byte i & 3 of ex[i >> 2]: e8m0 of row i, this wave's half
+#pragma unroll
+                for (int i = 0; i < 16; ++i) {
+                    const float xq[4] = {xin[i].x, xin[i].y, xin[i].z, xin[i].w};
+                    float v[4];
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const float nk = __builtin_fmaf(xq[k], A[k], Bc[k]);
+                        const float t = __builtin_fmaf(acc[i][0][k], nk, acc[i][1][k]);
+                        const float u = fmaxf(t, t * p.slope);
+                        v[k] = __builtin_amdgcn_fmed3f(u, -65504.f, 65504.f);
+                    }
+                    vv[i] = make_float4(v[0], v[1], v[2], v[3]);
+                    float m = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])));   // NaN: dropped here, kept in the fp16 piece
+                    m = fmaxf(m, __shfl_xor(m, 16));
+                    m = fmaxf(m, __shfl_xor(m, 32));
+                    ex[i >> 2] |= (unsigned)msr_block_e8m0_dev(m) << (8 * (i & 3));
+                }
+                if (cg == 0) {                                    // the four lanes of a pixel hold the same bytes
+                    if (par) {
+                        *reinterpret_cast<uint2*>(stage + 16 * GB_LINE + 8 * px) = make_uint2(ex[0], ex[1]);
+                        *reinterpret_cast<unsigned*>(line + 44) = ex[2];
+                        *reinterpret_cast<unsigned*>(line + 60) = ex[3];
+                    } else {
+                        *reinterpret_cast<uint4*>(line + 64) = make_uint4(ex[0], ex[1], ex[2], ex[3]);
+                    }
+                }
+                __syncthreads();
+                unsigned pe[4];
+                asm volatile("" ::: "memory");
+                if (par) {
+                    const uint2 lo2 = *reinterpret_cast<const uint2*>(pline - px * GB_LINE + 16 * GB_LINE + 8 * px);
+                    pe[0] = lo2.x; pe[1] = lo2.y;
+                    pe[2] = *reinterpret_cast<const unsigned*>(pline + 44);
+                    pe[3] = *reinterpret_cast<const unsigned*>(pline + 60);
+                } else {
+                    const uint4 e4 = *reinterpret_cast<const uint4*>(pline + 64);
+                    pe[0] = e4.x; pe[1] = e4.y; pe[2] = e4.z; pe[3] = e4.w;
+                }
+                asm volatile("" ::: "memory");
+                // the lane's piece of the pixel's chunk: 16 bytes of fp16 (lane groups 0, 1), the wave's 12 bytes of h6 / l6
+                // (2 / 3); the odd wave of the pair appends the scale dword to them and writes the zero dword behind it
+                const int boff = cg < 2 ? 32 * half + 16 * cg : (cg == 2 ? 64 : 96) + 12 * half;
+                char* const obase = reinterpret_cast<char*>(p.out + (size_t)p.out_off + (size_t)b0 * p.out_pb + x * p.out_px + (ch & ~31)) + boff;
+                uint4 q;
+                int eb_prev = 0;
+#pragma unroll
+                for (int i = 0; i <= 16; ++i) {
+                    if (i > 0) {
+                        asm volatile("" ::: "memory");          // the pieces were written through other types
+                        q = *reinterpret_cast<const uint4*>(line + 16 * cg);
+                        asm volatile("" ::: "memory");
+                    }
+                    int eb = 0;
+                    if (i < 16) {
+                        const unsigned eo = (ex[(i & 15) >> 2] >> (8 * (i & 3))) & 0xFFu, ep = (pe[(i & 15) >> 2] >> (8 * (i & 3))) & 0xFFu;
+                        eb = (int)(eo > ep ? eo : ep);
+                        const float inv = __builtin_bit_cast(float, (254 - eb) << 23);       // 2^-E
+                        const float invl = inv * 2048.f;                                     // 2^-(E - 11)
+                        const float v[4] = {vv[i & 15].x, vv[i & 15].y, vv[i & 15].z, vv[i & 15].w};
+                        const h2 a = {(_Float16)v[0], (_Float16)v[1]}, b = {(_Float16)v[2], (_Float16)v[3]};
+                        // the e4m3 converter rounds on e2m3's grid (kernels.h msr_pack_e2m3x4_dev): 4 codes = 24 bits
+                        const unsigned h6 = msr_pack_e2m3x4_dev(v[0] * inv, v[1] * inv, v[2] * inv, v[3] * inv);
+                        const unsigned l6 = msr_pack_e2m3x4_dev((v[0] - (float)a[0]) * invl, (v[1] - (float)a[1]) * invl,
+                                                                (v[2] - (float)b[0]) * invl, (v[3] - (float)b[1]) * invl);
+                        // staged line: bytes 0..31 fp16, 32..43 h6, 48..59 l6 (44..47 and 60..63 stay free: exchange buffer)
+                        *reinterpret_cast<uint2*>(line + 8 * cg) = make_uint2(__builtin_bit_cast(unsigned, a), __builtin_bit_cast(unsigned, b));
+                        unsigned char* const lb = reinterpret_cast<unsigned char*>(line) + 3 * cg;
+                        lb[32] = (unsigned char)h6; lb[33] = (unsigned char)(h6 >> 8); lb[34] = (unsigned char)(h6 >> 16);
+                        lb[48] = (unsigned char)l6; lb[49] = (unsigned char)(l6 >> 8); lb[50] = (unsigned char)(l6 >> 16);
+                    }
+                    if (i > 0) {
+                        char* const o = obase + (size_t)(ty0 + i - 1) * p.out_py * sizeof(float);
+                        if (cg < 2 || half) {
+                            // lane groups 2, 3 of the odd wave: bytes 76..91 / 108..123 = 12 bytes of codes + the scale dword
+                            if (cg >= 2) q.w = (unsigned)(cg == 2 ? eb_prev : eb_prev - 11);
+                            *reinterpret_cast<u32x4a*>(o) = u32x4a{q.x, q.y, q.z, q.w};
+                            if (cg >= 2) *reinterpret_cast<unsigned*>(o + 16) = 0u;           // bytes 92..95 / 124..127
+                        } else {
+                            *reinterpret_cast<u32x3a*>(o) = u32x3a{q.x, q.y, q.z};
+                        }
+                    }
+                    eb_prev = eb;
+                }
+            } else
             {
                 typedef _Float16 h2 __attribute__((ext_vector_type(2)));
                 // out = lrelu((acc_g + bias_g) * (x - mean) / std + (acc_b + bias_b)): per channel nk = x * A + Bc
@@ -613,8 +723,11 @@ hipError_t conv_gbr_init() {
     hipError_t e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_gb_resident<false>),
                                        hipFuncAttributeMaxDynamicSharedMemorySize, (int)GB_LDS);
     if (e != hipSuccess) return e;
-    return hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_gb_resident<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
-                               (int)GB_LDS);
+    e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_gb_resident<true>), hipFuncAttributeMaxDynamicSharedMemorySize,
+                            (int)GB_LDS);
+    if (e != hipSuccess) return e;
+    return hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_gb_resident<false, true>),
+                               hipFuncAttributeMaxDynamicSharedMemorySize, (int)GB_LDS);
 }
 
 // Work decomposition: a work item = one 16 x 16 pixel tile x `nr` channel blocks; the N / 128 blocks of a pixel tile are cut
@@ -633,9 +746,10 @@ int conv_gbr_ranges(int B, int r, int N) {
 }
 
 hipError_t launch_conv_gbr(const GbrParams& p, int ranges, hipStream_t s) {
-    if (ranges < 1 || p.r < 16 || (p.r & (p.r - 1)) || p.N % 128 || (p.N / 128) % ranges || p.out_split != 4 || !p.src || !p.we16 || !p.be || !p.wt || !p.aux || !p.mean || !p.stdv || !p.out)
+    if (ranges < 1 || p.r < 16 || (p.r & (p.r - 1)) || p.N % 128 || (p.N / 128) % ranges || (p.out_split != 4 && p.out_split != 5) || !p.src || !p.we16 || !p.be || !p.wt || !p.aux || !p.mean || !p.stdv || !p.out)
         return hipErrorInvalidValue;
     if (p.f < 1 || p.S != p.r * p.f || p.out_px % 32 || !(p.slope >= 0.f && p.slope <= 1.f)) return hipErrorInvalidValue;
+    if (p.out_split == 5 && p.no_cross) return hipErrorInvalidValue;      // the f16 mode's consumer reads no cross pieces
     GbrGeom g;
     g.tiles_x = p.r / 16;
     g.tiles_y = p.r / 16;
@@ -652,6 +766,7 @@ hipError_t launch_conv_gbr(const GbrParams& p, int ranges, hipStream_t s) {
     }
     const int grid = g.items < n_cu ? ((g.items + 7) & ~7) : n_cu;
     if (p.no_cross) conv_gb_resident<true><<<grid, 256, GB_LDS, s>>>(p, g);
+    else if (p.out_split == 5) conv_gb_resident<false, true><<<grid, 256, GB_LDS, s>>>(p, g);
     else conv_gb_resident<false><<<grid, 256, GB_LDS, s>>>(p, g);
     return hipGetLastError();
 }

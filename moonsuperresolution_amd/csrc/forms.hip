@@ -89,9 +89,12 @@ static int split_for(int prec) {
 //    fp6 image).  Measured: the consumer gains 6.5 % on those convs, the producer's block-scale and 6-bit packing
 //    cost the gamma|beta epilogues more, net -1 % per call: it pays only once the gamma|beta convs consume fp6 too.  Any
 //    MSR_F16C_SW other than 1 (the A/B dispatches) switches it off.
-//  * conv_gb_resident (conv_gbr.hip) takes a layer whose gamma|beta conv and f16c consumer (not f16c6) run f16c, when the
+//  * conv_gb_resident (conv_gbr.hip) takes a layer whose gamma|beta conv and f16c consumer run f16c, when the
 //    layer has enough 16 x 16 pixel tiles x channel-block ranges to fill the chip (conv_gbr_ranges; MSR_GBR=0 switches it
 //    off).  Its weights are the f16c6 image with the input channels of every 32-chunk in the kernel's order (gbr_perm).
+//    Under the environment switch it leaves the f16c6 consumers to the ping-pong kernel (the measured -1 % above).
+//  * MSR_FLAG_CROSS_FP6: the same f16c6 consumers as MSR_F16C_FP6=1 selects, and their layers KEEP conv_gb_resident, which
+//    then writes the fp6 image (out_split 5); where it does not take the layer the ping-pong epilogue writes it as above.
 //  * MSR_FLAG_GB_F16X2: a gamma|beta conv that runs the ping-pong kernel on whole tiles takes 2-term fp16 products (the
 //    K-split launches run the 3-term form).
 static SpadeForm spade_form(const msr_handle* h, int r, int C, int cout, int epi) {
@@ -102,9 +105,10 @@ static SpadeForm spade_form(const msr_handle* h, int r, int C, int cout, int epi
     auto f16c_pp = [&](int N, int cin) { return f16c_ks_off ? fills(N) : pp_ksplit(B, r, N, 1, cin) >= 1; };
     const bool gb8 = h->fp8 && fills(2 * C), cv8 = gb8 && fills(cout);
     const bool gbc = h->f16c && f16c_pp(2 * C, 128), cvc = gbc && C % 64 == 0 && f16c_pp(cout, C);
-    const bool cv6 = cvc && fp6_on && C % 128 == 0 && fills(cout) && fills(2 * C);
+    static const bool sw_on = env_int("MSR_F16C_SW", 1) == 1;      // the f16c6 consumer is the stream kernel
+    const bool cv6 = cvc && (fp6_on || (h->cross6 && sw_on)) && C % 128 == 0 && fills(cout) && fills(2 * C);
     SpadeForm s;
-    s.gbr = cvc && !cv6 && conv_gbr_ranges(B, r, 2 * C) > 0;
+    s.gbr = cvc && (!cv6 || h->cross6) && conv_gbr_ranges(B, r, 2 * C) > 0;
     if (gb8) {
         s.gb = make_form(PREC_FP8, TILE_256x128_PP, 1);
     } else if (s.gbr) {

@@ -118,6 +118,7 @@ struct msr_handle {
     bool fp8 = false;                            // MSR_FLAG_FP8: declared non-parity mode (fp8 weights x bf8 activations)
     bool f16c = false;                           // MSR_FLAG_F16C: fp16 main term + fp8 cross terms in the chip-filling convs
     bool f16m = false;                           // MSR_FLAG_F16_MAIN: F16C without the cross terms in the stream / resident kernels
+    bool cross6 = false;                         // MSR_FLAG_CROSS_FP6: fp6 cross terms in the stream-kernel consumers of F16C
     msr::ConvForm enc_forms[6];                  // [i]: enc.ds<i> (i = 2..5)
     msr::SpadeForm spade_forms[7][4];            // [i][j]: gen.rb<i>.spade_<j> and gen.rb<i>.conv_<j> (i = 1..6, j = 1..3)
     std::string err;

@@ -114,7 +114,7 @@ int msr_op_conv3x3_f16c(msr_handle* h, const float* in_dev, const float* wt_dev,
 static int op_spade_gbr_impl(msr_handle* h, const float* src_dev, int32_t S, const float* we_dev, const float* be_dev,
                              const float* wt_dev, const float* bias_dev, float* out_dev, int32_t B, int32_t r, int32_t N,
                              const float* aux_dev, int32_t aux_shift, const float* mean_dev, const float* std_dev, int no_cross,
-                             void* stream) {
+                             int out_split, void* stream) {
     if (!h) return MSR_ERR_INVALID;
     if (!src_dev || !we_dev || !be_dev || !wt_dev || !bias_dev || !out_dev || !aux_dev || !mean_dev || !std_dev || B < 1 ||
         r < 16 || (r & (r - 1)) || S < r || S % r || N % 128 || aux_shift < 0 || aux_shift > 1)
@@ -127,7 +127,7 @@ static int op_spade_gbr_impl(msr_handle* h, const float* src_dev, int32_t S, con
     set_aux_dense(q, aux_dev, rx, C, aux_shift);
     q.mean = mean_dev; q.stdv = std_dev;
     set_out_padded(q, out_dev, r, r, C);
-    q.out_split = 4; q.slope = 0.2f; q.B = B; q.r = r; q.N = N; q.no_cross = no_cross;
+    q.out_split = out_split; q.slope = 0.2f; q.B = B; q.r = r; q.N = N; q.no_cross = no_cross;
     int ranges = conv_gbr_ranges(B, r, N);       // the planner's split; a layer it would not take runs one item per pixel tile
     if (ranges < 1) ranges = 1;
     // the embedding kernel as fp16 MFMA operands (msr_load_weight builds this image once per layer; this test entry per call)
@@ -150,14 +150,21 @@ int msr_op_spade_gbr(msr_handle* h, const float* src_dev, int32_t S, const float
                      const float* wt_dev, const float* bias_dev, float* out_dev, int32_t B, int32_t r, int32_t N,
                      const float* aux_dev, int32_t aux_shift, const float* mean_dev, const float* std_dev, void* stream) {
     return op_spade_gbr_impl(h, src_dev, S, we_dev, be_dev, wt_dev, bias_dev, out_dev, B, r, N, aux_dev, aux_shift, mean_dev,
-                             std_dev, 0, stream);
+                             std_dev, 0, 4, stream);
 }
 
 int msr_op_spade_gbr_f16(msr_handle* h, const float* src_dev, int32_t S, const float* we_dev, const float* be_dev,
                          const float* wt_dev, const float* bias_dev, float* out_dev, int32_t B, int32_t r, int32_t N,
                          const float* aux_dev, int32_t aux_shift, const float* mean_dev, const float* std_dev, void* stream) {
     return op_spade_gbr_impl(h, src_dev, S, we_dev, be_dev, wt_dev, bias_dev, out_dev, B, r, N, aux_dev, aux_shift, mean_dev,
-                             std_dev, 1, stream);
+                             std_dev, 1, 4, stream);
+}
+
+int msr_op_spade_gbr_f16c6(msr_handle* h, const float* src_dev, int32_t S, const float* we_dev, const float* be_dev,
+                           const float* wt_dev, const float* bias_dev, float* out_dev, int32_t B, int32_t r, int32_t N,
+                           const float* aux_dev, int32_t aux_shift, const float* mean_dev, const float* std_dev, void* stream) {
+    return op_spade_gbr_impl(h, src_dev, S, we_dev, be_dev, wt_dev, bias_dev, out_dev, B, r, N, aux_dev, aux_shift, mean_dev,
+                             std_dev, 0, 5, stream);
 }
 
 int msr_op_conv_smallcin(msr_handle* h, const float* src_dev, int32_t S, const float* w_dev, const float* bias_dev,

@@ -47,6 +47,7 @@ class RangeReport:
         self.records = [dict(r) for r in records]
         self.embed_bounds = [dict(r) for r in embed_bounds]
         self.layers = dict(layers or {})
+        self.note = ""          # what precision="auto" did with an option of the mode it left (appended to the text)
 
     @property
     def regime(self) -> str:
@@ -77,7 +78,7 @@ class RangeReport:
     def __str__(self) -> str:
         w = self.worst
         if w is None:
-            return "activation range: parity (no narrow activation tensor in this plan)"
+            return "activation range: parity (no narrow activation tensor in this plan)" + (f"; {self.note}" if self.note else "")
         layer = self.layers.get(w["producer"], "?")
         text = (f"activation range: {self.regime}; worst tensor {w['tensor']} (format {w['format']}, written by op "
                 f"{w['producer']}, {layer}): max |a| = {float(w['max_abs']):.6g}, {w['n_cross_clipped']} cross-clipped (|a| > 464), "
@@ -86,6 +87,8 @@ class RangeReport:
         over = [e for e in self.embed_bounds if not (e["max_abs"] <= F16_MAX)]
         if over:
             text += f"; embedding bound of {over[0]['tensor']} is {float(over[0]['max_abs']):.6g} > 65504"
+        if self.note:
+            text += f"; {self.note}"
         return text
 
     __repr__ = __str__
@@ -117,20 +120,29 @@ class Generator:
             "auto" builds "f16c", runs one call on ``calibrate`` and scans the activation ranges (``range_report``); it keeps
             f16c when the regime is "parity" and rebuilds as "bf16x3" from the same weights otherwise.  ``.precision`` then
             reads the mode chosen and ``.range`` the report that decided it; ``clone()`` clones the chosen mode.
+        cross: format of the f16c mode's cross terms in the main convs — "fp8" (default) or "fp6" (opt-in: e2m3 pieces with a
+            block scale per pixel and 32 channels, 1.5 instead of 2 MFMA-equivalents per product in the convs that run the
+            stream kernel, same parity grade; the measured A/B is in DESIGN.md).  "fp6" goes with precision="f16c", or with
+            "auto", which keeps it when it stays on f16c and drops it (``.cross`` reads "fp8", ``.range`` says so) when it
+            falls back to bf16x3.
         calibrate: the batch [batch_size, S, S, 2] "auto" calibrates on; None = ``synthetic_patches(batch_size, S, seed=0)``.
             Calibration holds for the data it saw: ``DEMSuperResolution(range_check=...)`` checks real tiles.
     """
 
     def __init__(self, image_size: int, batch_size: int, latent_dim: int = 256, variant: str = "gaugan",
                  weights: Union[int, Mapping[str, np.ndarray]] = 1234, eps: Union[None, int, np.ndarray] = None,
-                 device: int = 0, precision: str = "f16c", calibrate=None):
+                 device: int = 0, precision: str = "f16c", calibrate=None, cross: str = "fp8"):
         if variant not in VARIANTS:
             raise ValueError(f"unknown variant {variant!r}; expected one of {VARIANTS}")
+        if cross not in _lib.CROSS_FLAGS:
+            raise ValueError(f"unknown cross {cross!r}; expected one of {tuple(_lib.CROSS_FLAGS)}")
+        if cross != "fp8" and precision not in ("f16c", "auto"):
+            raise ValueError(f"cross={cross!r} is an option of precision='f16c' (or 'auto'), not of {precision!r}")
         if precision == "auto":
             # resolved here, above the flag table: try the fast default, keep it only in the parity regime
             if isinstance(weights, (int, np.integer)):
                 weights = make_weights(variant, image_size, latent_dim, seed=int(weights))
-            self.__init__(image_size, batch_size, latent_dim, variant, weights, eps, device, "f16c")
+            self.__init__(image_size, batch_size, latent_dim, variant, weights, eps, device, "f16c", cross=cross)
             if calibrate is None:
                 from .weights import synthetic_patches
                 calibrate = synthetic_patches(batch_size, image_size, seed=0)
@@ -140,11 +152,14 @@ class Generator:
             if report.regime != "parity":
                 self.close()
                 self.__init__(image_size, batch_size, latent_dim, variant, weights, eps, device, "bf16x3")
+                if cross != "fp8":
+                    report.note = f"cross={cross!r} dropped: it is an option of f16c, and this generator runs bf16x3"
             self.range = report
             return
         if precision not in _lib.PRECISION_FLAGS:
             raise ValueError(f"unknown precision {precision!r}; expected one of {tuple(_lib.PRECISION_FLAGS) + ('auto',)}")
         self.precision = precision
+        self.cross = cross
         self.range: Optional[RangeReport] = None
         self.image_size, self.batch_size, self.latent_dim, self.variant = image_size, batch_size, latent_dim, variant
         self._lib = _lib.load()
@@ -152,7 +167,7 @@ class Generator:
             raise RuntimeError("moonsuperresolution_amd needs a HIP device (MI355X / gfx950); there is no CPU fallback")
         self.device = torch.device("cuda", device)
         cfg = _lib.MsrConfig(image_size, batch_size, latent_dim, _lib.VARIANT_IDS[variant], device,
-                             _lib.PRECISION_FLAGS[precision])
+                             _lib.PRECISION_FLAGS[precision] | _lib.CROSS_FLAGS[cross])
         handle = C.c_void_p()
         rc = self._lib.msr_create(C.byref(cfg), C.byref(handle))
         _lib.raise_for(self._lib, None, rc, "msr_create")
@@ -167,7 +182,7 @@ class Generator:
                 raise ValueError(f"eps must be [{batch_size}, {latent_dim}], got {e.shape}")
             self._eps_fixed = torch.from_numpy(e).to(self.device)
         self._ctor = dict(image_size=image_size, batch_size=batch_size, latent_dim=latent_dim, variant=variant,
-                          eps=eps, device=device, precision=precision)
+                          eps=eps, device=device, precision=precision, cross=cross)
         self._weights: Optional[Mapping[str, np.ndarray]] = None   # what the handle holds now (clone() re-uploads it)
         self.weights_version = 0                                    # bumped by every load(); the tiler's clones follow it
         if isinstance(weights, (int, np.integer)):

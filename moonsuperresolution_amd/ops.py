@@ -387,14 +387,17 @@ def gbr_weight_image(w_kl: torch.Tensor) -> torch.Tensor:
 
 
 def spade_gbr(ctx: OpContext, src: torch.Tensor, we: torch.Tensor, be: torch.Tensor, w_img: torch.Tensor, bias: torch.Tensor,
-              r: int, x: torch.Tensor, aux_shift: int, mean: torch.Tensor, std: torch.Tensor, no_cross: bool = False) -> torch.Tensor:
+              r: int, x: torch.Tensor, aux_shift: int, mean: torch.Tensor, std: torch.Tensor, no_cross: bool = False,
+              out_mode: int = 4) -> torch.Tensor:
     """One launch of conv_gb_resident (msr_op_spade_gbr; ``no_cross``: msr_op_spade_gbr_f16, the f16 mode's form): resize +
     mask embedding + gamma|beta conv + SPADE epilogue; returns the zero-bordered f16c image [B, r + 2, r + 2, C] (float32
-    storage; f16c_decode reads it)."""
+    storage; f16c_decode reads it).  ``out_mode=5`` (msr_op_spade_gbr_f16c6): the f16c6 image instead (f16c6_decode)."""
+    if out_mode not in (4, 5) or (out_mode == 5 and no_cross):
+        raise ValueError("spade_gbr: out_mode is 4 (f16c image) or 5 (f16c6 image, not with no_cross)")
     B, S = src.shape[0], src.shape[1]
     N = w_img.shape[1]
     out = torch.zeros((B, r + 2, r + 2, N // 2), dtype=torch.float32, device=src.device)
-    fn = ctx.lib.msr_op_spade_gbr_f16 if no_cross else ctx.lib.msr_op_spade_gbr
+    fn = ctx.lib.msr_op_spade_gbr_f16 if no_cross else (ctx.lib.msr_op_spade_gbr_f16c6 if out_mode == 5 else ctx.lib.msr_op_spade_gbr)
     rc = fn(ctx.h, src.data_ptr(), S, we.data_ptr(), be.data_ptr(), w_img.data_ptr(), bias.data_ptr(), out.data_ptr(), B, r, N,
             x.data_ptr(), aux_shift, mean.data_ptr(), std.data_ptr(), torch.cuda.current_stream(src.device).cuda_stream)
     _lib.raise_for(ctx.lib, ctx.h, rc, "msr_op_spade_gbr")
