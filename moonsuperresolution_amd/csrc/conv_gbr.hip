@@ -31,18 +31,9 @@
 //                                       16 mod 32 -> the two kinds of a 32-lane group use disjoint bank halves)
 //   SC[chunk][kind][336] x 1 B          e8m0 of the piece (h6: E, l6: E - 11)      2,688 B
 //   stage[wave] 2,560 B                 epilogue line assembly (phase 1: the 20 x 20 x 2 mask patch)   -> 163,456 B
-#include "kernels.h"
-#include <cstdlib>
+#include "conv_common.h"
 
 namespace msr {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef int i32x6 __attribute__((ext_vector_type(6)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
-typedef int i32x2 __attribute__((ext_vector_type(2)));
 
 static constexpr int GB_PH = 336;
 static constexpr int GB_F_BYTES = 16 * GB_PH * 16;
@@ -78,7 +69,7 @@ struct GbrGeom {
 // NOX = true (GbrParams.no_cross, the "f16" mode): the fp6 cross terms are left out of the sweep — one fp16 product per
 // element (per-product error 2^-11; declared tolerance, include/moonsr.h MSR_FLAG_F16_MAIN).  Phase 1 and the weight
 // stream are unchanged; the cross pieces are not read.
-// F6OUT = true (GbrParams.out_split == 5): the SPADE epilogue writes the consumer's f16c6 chunk image (kernels.h PREC_F16C6)
+// F6OUT = true (GbrParams.out_split == OUT_F16C6): the SPADE epilogue writes the consumer's f16c6 chunk image (kernels.h PREC_F16C6)
 // instead of the f16c one.  A pixel's block scale spans the two waves that hold a chunk's 2 x 16 channels: they exchange
 // their per-pixel exponents once per channel block (below).  Everything else is the <false, false> kernel.
 template <bool NOX, bool F6OUT = false>
@@ -96,10 +87,8 @@ conv_gb_resident(const GbrParams p, const GbrGeom g) {
     const int px = lane & 15, cg = lane >> 4;
 
     // persistent walk: XCD x owns a contiguous range of items, its workgroups take consecutive items of it
-    const int slots = gridDim.x >> 3, xcd = blockIdx.x & 7;
-    const int tq = g.items >> 3, tr = g.items & 7;
-    const int cnt = tq + (xcd < tr ? 1 : 0);
-    const int base = xcd < tr ? xcd * (tq + 1) : tr * (tq + 1) + (xcd - tr) * tq;
+    int slots, cnt, base;
+    xcd_tile_range(g.items, slots, cnt, base);
 
     // ---- lane constants of the sweep ----
     // fp16 fragment of pixel row i, tap (dy, dx), chunk c: plane (c, piece cg), pixel (i + dy) * 18 + dx + px
@@ -746,27 +735,20 @@ int conv_gbr_ranges(int B, int r, int N) {
 }
 
 hipError_t launch_conv_gbr(const GbrParams& p, int ranges, hipStream_t s) {
-    if (ranges < 1 || p.r < 16 || (p.r & (p.r - 1)) || p.N % 128 || (p.N / 128) % ranges || (p.out_split != 4 && p.out_split != 5) || !p.src || !p.we16 || !p.be || !p.wt || !p.aux || !p.mean || !p.stdv || !p.out)
+    if (ranges < 1 || p.r < 16 || (p.r & (p.r - 1)) || p.N % 128 || (p.N / 128) % ranges || (p.out_split != OUT_F16C && p.out_split != OUT_F16C6) || !p.src || !p.we16 || !p.be || !p.wt || !p.aux || !p.mean || !p.stdv || !p.out)
         return hipErrorInvalidValue;
     if (p.f < 1 || p.S != p.r * p.f || p.out_px % 32 || !(p.slope >= 0.f && p.slope <= 1.f)) return hipErrorInvalidValue;
-    if (p.out_split == 5 && p.no_cross) return hipErrorInvalidValue;      // the f16 mode's consumer reads no cross pieces
+    if (p.out_split == OUT_F16C6 && p.no_cross) return hipErrorInvalidValue;      // the f16 mode's consumer reads no cross pieces
     GbrGeom g;
     g.tiles_x = p.r / 16;
     g.tiles_y = p.r / 16;
     g.tiles_p = g.tiles_x * g.tiles_y * p.B;
     g.nr = p.N / 128 / ranges;
     g.items = g.tiles_p * ranges;
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return hipErrorInvalidValue;
-        n_cu = prop.multiProcessorCount & ~7;
-        if (n_cu < 8) n_cu = 8;
-    }
-    const int grid = g.items < n_cu ? ((g.items + 7) & ~7) : n_cu;
+    const int grid = persistent_grid(g.items);
+    if (!grid) return hipErrorInvalidValue;
     if (p.no_cross) conv_gb_resident<true><<<grid, 256, GB_LDS, s>>>(p, g);
-    else if (p.out_split == 5) conv_gb_resident<false, true><<<grid, 256, GB_LDS, s>>>(p, g);
+    else if (p.out_split == OUT_F16C6) conv_gb_resident<false, true><<<grid, 256, GB_LDS, s>>>(p, g);
     else conv_gb_resident<false><<<grid, 256, GB_LDS, s>>>(p, g);
     return hipGetLastError();
 }

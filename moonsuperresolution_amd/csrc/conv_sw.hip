@@ -28,15 +28,9 @@
 // (4 fillers per K = 128 MFMA pair: +12 %, tools/gpu_sw_bench.py history in DESIGN.md), and the SPADE epilogue (a quarter of
 // a gamma|beta layer when exposed) is hidden only by a second wave on the SIMD.  So the planner keeps the gamma|beta convs
 // on the ping-pong kernel and gives this one the long-K main convs, whose epilogue is 1-2 % of a tile.
-#include "kernels.h"
-#include <cstdlib>
+#include "conv_common.h"
 
 namespace msr {
-
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
-typedef int i32x8 __attribute__((ext_vector_type(8)));
-typedef int i32x4 __attribute__((ext_vector_type(4)));
 
 struct SwGeom {
     int tiles_x, tiles_y, tiles_n, tiles_mn;   // 16 x 16 pixel tiles per row / column, 128-column blocks, all tiles
@@ -49,14 +43,6 @@ static constexpr size_t SW_LDS = (size_t)3 * SW_HPB * sizeof(float) + 8192;     
 #else
 static constexpr size_t SW_LDS = (size_t)3 * SW_HPB * sizeof(float);                       // 155,520 B
 #endif
-
-__device__ __forceinline__ float sw_row16_sum(float v) {
-    v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0xB1, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x4E, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x141, 0xF, 0xF, true));
-    v += __builtin_bit_cast(float, __builtin_amdgcn_mov_dpp(__builtin_bit_cast(int, v), 0x140, 0xF, 0xF, true));
-    return v;
-}
 
 // Epilogue of one wave: acc[i][j] = D[4 channels of column block j][pixel (row i, x = lane & 15)].
 // Column blocks of wave q: 16 * (4 * (q >> 1) + (q & 1) + 2 * j): for EPI_SPADE (columns interleaved 32 gamma | 32 beta per
@@ -78,7 +64,7 @@ __device__ __forceinline__ void sw_epilogue_body(const ConvParams& p, const SwGe
         const float gq[4] = {gq4.x, gq4.y, gq4.z, gq4.w}, bq[4] = {bq4.x, bq4.y, bq4.z, bq4.w};
         const float mq[4] = {mq4.x, mq4.y, mq4.z, mq4.w};
         float sq[4] = {sq4.x, sq4.y, sq4.z, sq4.w};
-        constexpr bool split = OS != 0;
+        constexpr bool split = OS != OUT_F32;
         if constexpr (split) {
 #pragma unroll
             for (int k = 0; k < 4; ++k) sq[k] = 1.f / sq[k];          // as the ping-pong kernel: multiply by 1/sigma
@@ -102,8 +88,8 @@ __device__ __forceinline__ void sw_epilogue_body(const ConvParams& p, const SwGe
                     const float t = (acc[i][0][k] + gq[k]) * normalized + (acc[i][1][k] + bq[k]);
                     v[k] = t >= 0.f ? t : t * p.slope;
                 }
-                if constexpr (OS == 4) msr_store_f16c4_dev(orow, ch, v[0], v[1], v[2], v[3]);
-                else if constexpr (OS == 1) msr_store_split4_dev(orow, ch, v[0], v[1], v[2], v[3]);
+                if constexpr (OS == OUT_F16C) msr_store_f16c4_dev(orow, ch, v[0], v[1], v[2], v[3]);
+                else if constexpr (OS == OUT_BF16X3) msr_store_split4_dev(orow, ch, v[0], v[1], v[2], v[3]);
                 else *reinterpret_cast<float4*>(orow + ch) = make_float4(v[0], v[1], v[2], v[3]);
             }
         }
@@ -144,9 +130,9 @@ __device__ __forceinline__ void sw_epilogue_body(const ConvParams& p, const SwGe
                     float mean[4], m2[4];
 #pragma unroll
                     for (int k = 0; k < 4; ++k) {
-                        const float mu = sw_row16_sum(4.f * pv[k] + s1[k]) * (1.f / 64.f);
+                        const float mu = row16_sum(4.f * pv[k] + s1[k]) * (1.f / 64.f);
                         const float dl = (pv[k] - mu) + s1[k] * 0.25f;
-                        const float t = sw_row16_sum(s2[k] - s1[k] * s1[k] * 0.25f + 4.f * dl * dl);
+                        const float t = row16_sum(s2[k] - s1[k] * s1[k] * 0.25f + 4.f * dl * dl);
                         mean[k] = bq[k] + mu;
                         m2[k] = t > 0.f ? t : 0.f;
                     }
@@ -167,11 +153,11 @@ template <int EPI>
 __device__ __forceinline__ void sw_epilogue(const ConvParams& p, const SwGeom& g, f32x4 (&acc)[16][2], int wq, int lane,
                                             int n0, int tx0, int ty0, int b0) {
     if constexpr (EPI == EPI_SPADE) {
-        if (p.out_split == 4) sw_epilogue_body<EPI, 4>(p, g, acc, wq, lane, n0, tx0, ty0, b0);
-        else if (p.out_split == 1) sw_epilogue_body<EPI, 1>(p, g, acc, wq, lane, n0, tx0, ty0, b0);
-        else sw_epilogue_body<EPI, 0>(p, g, acc, wq, lane, n0, tx0, ty0, b0);
+        if (p.out_split == OUT_F16C) sw_epilogue_body<EPI, OUT_F16C>(p, g, acc, wq, lane, n0, tx0, ty0, b0);
+        else if (p.out_split == OUT_BF16X3) sw_epilogue_body<EPI, OUT_BF16X3>(p, g, acc, wq, lane, n0, tx0, ty0, b0);
+        else sw_epilogue_body<EPI, OUT_F32>(p, g, acc, wq, lane, n0, tx0, ty0, b0);
     } else {
-        sw_epilogue_body<EPI, 0>(p, g, acc, wq, lane, n0, tx0, ty0, b0);
+        sw_epilogue_body<EPI, OUT_F32>(p, g, acc, wq, lane, n0, tx0, ty0, b0);
     }
 }
 
@@ -221,13 +207,9 @@ conv_igemm_f16c_sw(const ConvParams p, const SwGeom g) {
     const int wq = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int px = lane & 15, cg = lane >> 4;
 
-    // persistent tile walk: exactly the ping-pong kernel's (XCD x owns a contiguous range of tiles; its workgroups take
-    // consecutive tiles = same pixels, next column block, so halo and weights are shared in that XCD's L2)
-    const int items = g.tiles_mn;
-    const int slots = gridDim.x >> 3, xcd = blockIdx.x & 7;
-    const int tq = items >> 3, tr = items & 7;
-    const int cnt = tq + (xcd < tr ? 1 : 0);
-    const int base = xcd < tr ? xcd * (tq + 1) : tr * (tq + 1) + (xcd - tr) * tq;
+    // persistent tile walk: the ping-pong kernel's (xcd_tile_range, conv_common.h)
+    int slots, cnt, base;
+    xcd_tile_range(g.tiles_mn, slots, cnt, base);
     int tile = blockIdx.x >> 3;
     if (tile >= cnt) return;
 
@@ -577,7 +559,7 @@ hipError_t conv_sw_init() {
 // Cin % 64 == 0, no K split.
 hipError_t launch_conv_f16c_sw(const ConvParams& p, int epi, hipStream_t s) {
     auto pow2 = [](int v) { return v > 0 && (v & (v - 1)) == 0; };
-    if (epi == EPI_SPADE && p.out_split != 0 && p.out_split != 1 && p.out_split != 4) return hipErrorInvalidValue;
+    if (epi == EPI_SPADE && p.out_split != OUT_F32 && p.out_split != OUT_BF16X3 && p.out_split != OUT_F16C) return hipErrorInvalidValue;
     const bool f6 = p.prec == PREC_F16C6;
     if ((p.prec != PREC_F16C && !f6) || (!f6 && !p.wexp) || p.ksplit > 1 || p.stride != 1 || p.KH != 3 || p.KW != 3) return hipErrorInvalidValue;
     if (f6 && epi == EPI_SPADE) return hipErrorInvalidValue;          // the fp6 form exists for the main convs
@@ -589,15 +571,8 @@ hipError_t launch_conv_f16c_sw(const ConvParams& p, int epi, hipStream_t s) {
     g.tiles_n = p.N / 128;
     g.tiles_mn = g.tiles_x * g.tiles_y * p.B * g.tiles_n;
     conv_walk_pick(g.tiles_x * g.tiles_y * p.B, g.tiles_n, &g.walk_pb, &g.walk_nb);
-    static int n_cu = 0;
-    if (!n_cu) {
-        int dev = 0;
-        hipDeviceProp_t prop;
-        if (hipGetDevice(&dev) != hipSuccess || hipGetDeviceProperties(&prop, dev) != hipSuccess) return hipErrorInvalidValue;
-        n_cu = prop.multiProcessorCount & ~7;
-        if (n_cu < 8) n_cu = 8;
-    }
-    const int grid = g.tiles_mn < n_cu ? ((g.tiles_mn + 7) & ~7) : n_cu;
+    const int grid = persistent_grid(g.tiles_mn);
+    if (!grid) return hipErrorInvalidValue;
     if (f6) {
         if (epi == EPI_BIAS) conv_igemm_f16c_sw<EPI_BIAS, true><<<grid, 256, SW_LDS, s>>>(p, g);
         else conv_igemm_f16c_sw<EPI_RES, true><<<grid, 256, SW_LDS, s>>>(p, g);

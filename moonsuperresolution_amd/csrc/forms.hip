@@ -67,12 +67,12 @@ ConvForm conv_form(int B, int rout, int N, int stride, int epi, int prec, int ci
 // out_split of a producer whose output feeds a conv in `prec`: the operand image that conv reads
 static int split_for(int prec) {
     switch (prec) {
-        case PREC_BF16X3: return 1;     // split-bf16 words
-        case PREC_F16X2: return 2;      // split-fp16 words
-        case PREC_FP8: return 3;        // bf8 bytes
-        case PREC_F16C: return 4;       // f16c chunk image
-        case PREC_F16C6: return 5;      // f16c6 chunk image
-        default: return 0;              // fp32
+        case PREC_BF16X3: return OUT_BF16X3;
+        case PREC_F16X2: return OUT_F16X2;
+        case PREC_FP8: return OUT_BF8;
+        case PREC_F16C: return OUT_F16C;
+        case PREC_F16C6: return OUT_F16C6;
+        default: return OUT_F32;
     }
 }
 
@@ -94,7 +94,7 @@ static int split_for(int prec) {
 //    off).  Its weights are the f16c6 image with the input channels of every 32-chunk in the kernel's order (gbr_perm).
 //    Under the environment switch it leaves the f16c6 consumers to the ping-pong kernel (the measured -1 % above).
 //  * MSR_FLAG_CROSS_FP6: the same f16c6 consumers as MSR_F16C_FP6=1 selects, and their layers KEEP conv_gb_resident, which
-//    then writes the fp6 image (out_split 5); where it does not take the layer the ping-pong epilogue writes it as above.
+//    then writes the fp6 image (OUT_F16C6); where it does not take the layer the ping-pong epilogue writes it as above.
 //  * MSR_FLAG_GB_F16X2: a gamma|beta conv that runs the ping-pong kernel on whole tiles takes 2-term fp16 products (the
 //    K-split launches run the 3-term form).
 static SpadeForm spade_form(const msr_handle* h, int r, int C, int cout, int epi) {

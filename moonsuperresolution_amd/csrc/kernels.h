@@ -65,10 +65,7 @@ struct ConvParams {
     int ksplit;                   // > 1: the K loop is cut into ksplit ranges, one workgroup each (low-res layers)
     float* partial;               // [ksplit][B*Hout*Wout][N] workspace for split-K
     int prec;                     // PREC_F32: operands are fp32; PREC_BF16X3: operands are split-bf16 words
-    int out_split;                // EPI_SPADE only: 1 = write the split-bf16 image (the consumer conv runs PREC_BF16X3 / its
-                                  // fp16 twin decided by the producer of the mask embedding), 3 = write bf8 e5m2 bytes
-                                  // (PREC_FP8 consumer: one byte per channel, dword index = channel / 4), 4 = the f16c
-                                  // chunk image (PREC_F16C consumer)
+    int out_split;                // EPI_SPADE only: the OutFormat the consumer conv reads
     float* stat_partial;          // EPI_BIAS / EPI_RES, ksplit == 1: per-wave partial moments of the OUTPUT,
                                   // [P][3][N] = (count, mean, M2) per 32- or 64-row slab (P = conv_stat_slabs)
     const int* wexp;              // PREC_FP8: [N] e8m0 exponent of every output channel's weight scale, replicated in the
@@ -126,6 +123,17 @@ int moments_chunks(int G, int P);
 // profiles/r02_mfma_scale_operand_map.txt): lane group g's 32 elements are one k-block whose scale comes from lane group g;
 // here g = 0 / 1 hold the first / second half of the EVEN tap's chunk row, g = 2 / 3 of the odd tap's.
 enum ConvPrecision : int { PREC_F32 = 0, PREC_BF16X3 = 1, PREC_F16X2 = 2, PREC_FP8 = 3, PREC_F16C = 4, PREC_F16C6 = 5 };
+// Activation image a producer writes for the conv that reads it in the precision of the same number (chunk layouts above):
+// the `out_split` of the parameter structs, the OS template argument of the kernels, RangeScanItem::format.  The fields stay
+// int: the values cross the C ABI and the plan dump as numbers.
+enum OutFormat : int {
+    OUT_F32 = 0,      // plain fp32
+    OUT_BF16X3 = 1,   // split-bf16 words
+    OUT_F16X2 = 2,    // split-fp16 words
+    OUT_BF8 = 3,      // bf8 e5m2 bytes: one byte per channel, dword index = channel / 4
+    OUT_F16C = 4,     // f16c chunk image
+    OUT_F16C6 = 5,    // f16c6 chunk image
+};
 
 __host__ __device__ inline unsigned msr_bf16_rn(float v) {   // round-to-nearest-even, finite inputs
     union { float f; unsigned u; } c;
@@ -317,7 +325,7 @@ struct GbrParams {
     const float* stdv;      // [N / 2] sqrt(var + eps)
     float* out;             // zero-bordered input of the consumer conv (f16c chunk image)
     int out_px, out_py, out_pb, out_off;
-    int out_split;          // 4: the f16c chunk image (PREC_F16C consumer)
+    int out_split;          // OutFormat: OUT_F16C or OUT_F16C6
     float slope;
     int B, r, N;
     int no_cross = 0;             // 1 = leave the fp6 cross terms out ("f16" mode)
@@ -364,8 +372,7 @@ struct SmallCinParams {
     int out_px, out_py, out_pb, out_off;
     int act;            // 0 none, 1 relu, 2 leaky(slope)
     float slope;
-    int out_split;      // 1: write split-bf16 words for a PREC_BF16X3 consumer; 2: split-fp16 words (PREC_F16X2);
-                        // 3: bf8 e5m2 bytes (PREC_FP8; one dword per 4 channels); 4: the f16c chunk image (PREC_F16C)
+    int out_split;      // OutFormat, any but OUT_F16C6
 };
 hipError_t launch_conv_smallcin(const SmallCinParams& p, hipStream_t s);
 hipError_t launch_split_bf16(const float* in, float* out, long n, hipStream_t s);
@@ -388,7 +395,7 @@ struct NormActParams {
     int B, H, W, C;
     int out_px, out_py, out_pb, out_off;
     float slope;
-    int out_split;        // write split-bf16 words for a PREC_BF16X3 consumer
+    int out_split;        // OutFormat: OUT_F32 or OUT_BF16X3
 };
 hipError_t launch_norm_act(const NormActParams& p, hipStream_t s);
 
@@ -452,7 +459,7 @@ hipError_t launch_resize_cubic(const float* src, int h, int w, float* dst, int d
 // ---------------------------------------------------------------------------------------------
 struct RangeScanItem {
     const void* base;      // first byte of the tensor (of its zero border when padded)
-    int format;            // the planner's out_split: 2 split-fp16, 3 bf8 bytes, 4 f16c, 5 f16c6
+    int format;            // the planner's out_split (OutFormat): OUT_F16X2 .. OUT_F16C6
     int B, r, C;           // [B, r, r, C] interior, C % 32 == 0
     int px_bytes;          // bytes per pixel: 4 * C for the chunk formats, the padded channel count for bf8
     int padded;            // != 0: zero-bordered [B, r + 2, r + 2, .]

@@ -38,7 +38,7 @@ static int op_conv_impl(msr_handle* h, const float* in_dev, const float* wt_dev,
     HIPCHK(h, hipSetDevice(h->cfg.device));
     Padded in; in.base = const_cast<float*>(in_dev); in.r = rout * stride; in.C = Cin;
     Op op = conv_op(in, Cin, wt_dev, bias_dev, B, rout, N, stride, epilogue, conv_form(B, rout, N, stride, epilogue, prec, Cin));
-    op.conv.out_split = (epilogue == EPI_SPADE && out_split) ? 1 : 0;
+    op.conv.out_split = (epilogue == EPI_SPADE && out_split) ? OUT_BF16X3 : OUT_F32;
     if (tile >= 0) {
         op.tile = tile & 0x3F;
         if (tile & 0x80) op.conv.prec = PREC_F16X2;            // operands are split-fp16 words (ping-pong tile only)
@@ -85,11 +85,11 @@ int msr_op_conv3x3_f16c(msr_handle* h, const float* in_dev, const float* wt_dev,
     if (!wexp_dev && (epilogue == EPI_SPADE || Cin % 128 || ksplit > 1 || no_cross))
         return fail(h, MSR_ERR_INVALID, "msr_op_conv3x3_f16c: the f16c6 form takes whole-tile bias / residual launches and Cin %% 128 == 0");
     if (epilogue < EPI_BIAS || epilogue > EPI_SPADE || (epilogue != EPI_BIAS && !aux_dev) ||
-        (epilogue == EPI_SPADE && (!mean_dev || !std_dev)) || (out_mode != 0 && out_mode != 1 && out_mode != 4 && out_mode != 5) ||
-        (out_mode != 0 && epilogue != EPI_SPADE))
+        (epilogue == EPI_SPADE && (!mean_dev || !std_dev)) || (out_mode != OUT_F32 && out_mode != OUT_BF16X3 && out_mode != OUT_F16C && out_mode != OUT_F16C6) ||
+        (out_mode != OUT_F32 && epilogue != EPI_SPADE))
         return fail(h, MSR_ERR_INVALID, "msr_op_conv3x3_f16c: bad epilogue / output mode");
     // K ranges: whole chunk pairs per range (launch_pp); the split-K epilogue writes fp32, split-bf16 or the f16c image
-    if (ksplit > 1 && ((ksplit & (ksplit - 1)) || (Cin / 64) % ksplit || out_mode == 5))
+    if (ksplit > 1 && ((ksplit & (ksplit - 1)) || (Cin / 64) % ksplit || out_mode == OUT_F16C6))
         return fail(h, MSR_ERR_INVALID, "msr_op_conv3x3_f16c: ksplit %d must be a power of two dividing Cin / 64 = %d (out_mode 0, 1, 4)",
                     ksplit, Cin / 64);
     // no cross terms: the stream kernel's form only (whole tiles, bias / residual, Cin % 128 == 0, power-of-two rout)
@@ -100,7 +100,7 @@ int msr_op_conv3x3_f16c(msr_handle* h, const float* in_dev, const float* wt_dev,
     Op op = conv_op(in, Cin, wt_dev, bias_dev, B, rout, N, 1, epilogue,
                     make_form(wexp_dev ? PREC_F16C : PREC_F16C6, TILE_256x128_PP, ksplit > 1 ? ksplit : 1, 0, no_cross));
     op.conv.wexp = wexp_dev;
-    op.conv.out_split = epilogue == EPI_SPADE ? out_mode : 0;
+    op.conv.out_split = epilogue == EPI_SPADE ? out_mode : OUT_F32;
     int rc = bind_conv_entry(h, op, out_dev, out_padded, epilogue == EPI_SPADE ? N / 2 : N, aux_dev, aux_shift, mean_dev, std_dev);
     if (rc) return rc;
     // no-cross goes to the stream kernel directly: launch_pp's MSR_F16C_SW = 0 would send it to the ping-pong kernel, which has
@@ -173,7 +173,7 @@ int msr_op_conv_smallcin(msr_handle* h, const float* src_dev, int32_t S, const f
     if (!h) return MSR_ERR_INVALID;
     // the kernel reads any out_split outside 2, 3, 4 as split-bf16: only the five formats the planner writes are accepted
     if (!src_dev || !w_dev || !out_dev || B < 1 || Hout < 1 || (Cout != 64 && Cout != 128) || map < 0 || map > 1 || act < 0 ||
-        act > 2 || out_split < 0 || out_split > 4 || out_padded < 0 || out_padded > 1 ||
+        act > 2 || out_split < OUT_F32 || out_split > OUT_F16C || out_padded < 0 || out_padded > 1 ||
         (map == 0 && S != 2 * Hout) || (map == 1 && (S < Hout || S % Hout)))
         return fail(h, MSR_ERR_INVALID, "msr_op_conv_smallcin: bad argument (Cout 64 | 128, map 0: S = 2 Hout, map 1: S a "
                     "multiple of Hout, act 0..2, out_split 0..4)");
@@ -183,7 +183,7 @@ int msr_op_conv_smallcin(msr_handle* h, const float* src_dev, int32_t S, const f
     p.B = B; p.S = S; p.Hout = Hout; p.Cout = Cout;
     if (map == 0) { p.ay = 2; p.cy = 0; p.lim = S; p.f = 1; p.o = 0; }                       // encoder ds1: stride-2 SAME
     else { p.ay = 1; p.cy = -1; p.lim = Hout; p.f = S / Hout; p.o = (S / Hout) / 2; }       // SPADE mask embedding
-    const int slots = out_split == 3 ? fp8_pad(Cout) / 4 : Cout;       // bf8: one byte per channel, padded to 128
+    const int slots = out_split == OUT_BF8 ? fp8_pad(Cout) / 4 : Cout;       // bf8: one byte per channel, padded to 128
     if (out_padded) set_out_padded(p, out_dev, Hout, Hout, slots);
     else set_out_dense(p, out_dev, Hout, Hout, slots);
     p.act = act; p.slope = slope; p.out_split = out_split;
@@ -197,7 +197,7 @@ int msr_op_norm_act(msr_handle* h, const float* x_dev, const float* mean_dev, co
                     int32_t out_padded, int32_t out_split, void* stream) {
     if (!h) return MSR_ERR_INVALID;
     if (!x_dev || !mean_dev || !std_dev || !gamma_dev || !beta_dev || !out_dev || B < 1 || H < 1 || W < 1 || C < 4 || C % 4 ||
-        out_padded < 0 || out_padded > 1 || out_split < 0 || out_split > 1 || (out_split && C % 32))
+        out_padded < 0 || out_padded > 1 || out_split < OUT_F32 || out_split > OUT_BF16X3 || (out_split && C % 32))
         return fail(h, MSR_ERR_INVALID, "msr_op_norm_act: bad argument (C a multiple of 4, of 32 for split output; "
                     "out_padded, out_split 0 | 1)");
     HIPCHK(h, hipSetDevice(h->cfg.device));
@@ -284,17 +284,17 @@ int msr_op_conv3x3_fp8(msr_handle* h, const void* in_dev, const void* wt_dev, co
         N % 128)
         return fail(h, MSR_ERR_INVALID, "msr_op_conv3x3_fp8: bad argument (Cpad 128 or a multiple of 256, N %% 128, rout >= 16)");
     if (epilogue < EPI_BIAS || epilogue > EPI_SPADE || (epilogue != EPI_BIAS && !aux_dev) ||
-        (epilogue == EPI_SPADE && (!mean_dev || !std_dev)) || (out_mode != 0 && out_mode != 1 && out_mode != 3) ||
-        (out_mode != 0 && epilogue != EPI_SPADE))
+        (epilogue == EPI_SPADE && (!mean_dev || !std_dev)) || (out_mode != OUT_F32 && out_mode != OUT_BF16X3 && out_mode != OUT_BF8) ||
+        (out_mode != OUT_F32 && epilogue != EPI_SPADE))
         return fail(h, MSR_ERR_INVALID, "msr_op_conv3x3_fp8: bad epilogue / output mode");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     Padded in; in.base = const_cast<float*>(static_cast<const float*>(in_dev)); in.r = rout; in.C = Cpad / 4;
     Op op = conv_op(in, Cpad, static_cast<const float*>(wt_dev), bias_dev, B, rout, N, 1, epilogue,
                     make_form(PREC_FP8, TILE_256x128_PP, 1));
     op.conv.wexp = wexp_dev;
-    op.conv.out_split = epilogue == EPI_SPADE ? out_mode : 0;
+    op.conv.out_split = epilogue == EPI_SPADE ? out_mode : OUT_F32;
     const int Cout = epilogue == EPI_SPADE ? N / 2 : N;
-    int rc = bind_conv_entry(h, op, out_dev, out_padded, out_mode == 3 ? fp8_pad(Cout) / 4 : Cout, aux_dev, aux_shift, mean_dev,
+    int rc = bind_conv_entry(h, op, out_dev, out_padded, out_mode == OUT_BF8 ? fp8_pad(Cout) / 4 : Cout, aux_dev, aux_shift, mean_dev,
                              std_dev);
     if (rc) return rc;
     hipError_t e = launch_conv_igemm(op.conv, epilogue, op.tile, (hipStream_t)stream);
@@ -314,12 +314,12 @@ int msr_op_range_scan(msr_handle* h, const void* img_dev, int32_t format, int32_
                       msr_range_stat* out_stat, void* stream) {
     if (!h) return MSR_ERR_INVALID;
     if (!img_dev || !out_stat) return fail(h, MSR_ERR_INVALID, "msr_op_range_scan: null argument");
-    if (format < 2 || format > 5) return fail(h, MSR_ERR_INVALID, "msr_op_range_scan: format %d is not 2, 3, 4 or 5", format);
+    if (format < OUT_F16X2 || format > OUT_F16C6) return fail(h, MSR_ERR_INVALID, "msr_op_range_scan: format %d is not 2, 3, 4 or 5", format);
     if (B < 1 || r < 1 || C < 32 || C % 32 || (int64_t)B * r > (1 << 24) || (int64_t)r * C > (1 << 24))
         return fail(h, MSR_ERR_INVALID, "msr_op_range_scan: bad shape B=%d r=%d C=%d (C a multiple of 32)", B, r, C);
     HIPCHK(h, hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream;
-    const RangeScanItem item{img_dev, format, B, r, C, format == 3 ? fp8_pad(C) : 4 * C, padded != 0, 0};
+    const RangeScanItem item{img_dev, format, B, r, C, format == OUT_BF8 ? fp8_pad(C) : 4 * C, padded != 0, 0};
     char* buf = nullptr;     // [record | item]
     HIPCHK(h, hipMalloc(&buf, sizeof(RangeScanRecord) + sizeof(RangeScanItem)));
     RangeScanRecord rec{};

@@ -64,7 +64,7 @@ static int plan_spade(msr_handle* h) {
         p.ay = 2; p.cy = 0; p.lim = S; p.f = 1; p.o = 0;
         set_out_padded(p, e_in);
         p.act = 2; p.slope = 0.2f;
-        p.out_split = h->prec == PREC_BF16X3;
+        p.out_split = h->prec == PREC_BF16X3 ? OUT_BF16X3 : OUT_F32;
         op.flops = 2.0 * B * (S / 2) * (S / 2) * 18.0 * 64;
         h->ops.push_back(op);
     }
@@ -93,7 +93,7 @@ static int plan_spade(msr_handle* h) {
             Padded nx;
             snprintf(n, sizeof n, "ws.enc.p%d", i); rc = alloc_padded(h, n, r, c, &nx); if (rc) return rc;
             set_out_padded(na.na, nx);
-            na.na.out_split = h->prec == PREC_BF16X3;
+            na.na.out_split = h->prec == PREC_BF16X3 ? OUT_BF16X3 : OUT_F32;
             e_in = nx;
         } else {
             rc = dev_alloc(h, "ws.enc.flat", (size_t)B * r * r * c, false, &flat); if (rc) return rc;
@@ -415,7 +415,7 @@ int ensure_conv_partial(msr_handle* h, size_t floats) {
 }
 
 // The tensors msr_range_scan reads: every planned activation image written in a format whose pieces have a finite range
-// (out_split 2, 3, 4, 5), once each, in plan order; and the gbr ops, whose embedding is bounded on the host instead.
+// (OUT_F16X2 .. OUT_F16C6), once each, in plan order; and the gbr ops, whose embedding is bounded on the host instead.
 static void build_range_plan(msr_handle* h) {
     h->range_plan.clear();
     h->range_embeds.clear();
@@ -425,10 +425,10 @@ static void build_range_plan(msr_handle* h) {
         return nm ? nm : "";
     };
     auto add = [&](int producer, const float* out, int out_off, int split, int B, int r, int C, int px_floats) {
-        if (split < 2 || split > 5 || !out || C % 32) return;
+        if (split < OUT_F16X2 || split > OUT_F16C6 || !out || C % 32) return;
         const std::string nm = tensor_of(out);
         if (nm.empty() || nm.size() >= 48) return;
-        if (split != 3 && px_floats != C) return;                       // chunk formats: one float slot per channel
+        if (split != OUT_BF8 && px_floats != C) return;                       // chunk formats: one float slot per channel
         for (const auto& e : h->range_plan) if (e.tensor == nm) return;
         RangeScanItem it{out, split, B, r, C, px_floats * 4, out_off != 0, (int)h->range_plan.size()};
         h->range_plan.push_back({nm, producer, it});

@@ -2,7 +2,7 @@
 //
 // One memory-bound launch walks a small device table of activation tensors and leaves, per tensor, a record
 //   { max |hi| (bits of the fp32 value), interior elements, cross-piece clipped, clamped, non-finite }
-// for the formats whose pieces have a finite range (the planner's out_split): 2 split-fp16, 3 bf8 bytes, 4 f16c, 5 f16c6.
+// for the formats whose pieces have a finite range (the planner's out_split, kernels.h OutFormat): OUT_F16X2, OUT_BF8, OUT_F16C, OUT_F16C6.
 //
 //  * Only the MAIN piece is read.  In the three chunk formats it is the first 64 bytes (32 fp16) of every 128-byte chunk; an
 //    e4m3 cross piece of the f16c image clips exactly when |hi| > 464 (the largest value that still rounds to 448), so the
@@ -102,11 +102,11 @@ __global__ __launch_bounds__(kThreads) void range_scan_kernel(const RangeScanIte
         const RangeScanItem it = table[t];
         const int rows = it.B * it.r;
         if ((int)blockIdx.x >= rows) continue;                     // uniform over the workgroup: nothing of this tensor is ours
-        const bool bytes = it.format == 3;
+        const bool bytes = it.format == OUT_BF8;
         // 16-byte items per interior row: four per 128-byte chunk (the fp16 main piece), or the whole run of bf8 bytes
         const int per_row = bytes ? it.r * (it.px_bytes >> 4) : it.r * (it.C >> 5) * 4;
-        const unsigned fast = it.format == 4 ? 0x5f40u : 0x7bfeu;  // 464 | the value below 65504
-        const unsigned cross_thr = it.format == 4 ? 0x5f40u : 0xffffu;
+        const unsigned fast = it.format == OUT_F16C ? 0x5f40u : 0x7bfeu;  // 464 | the value below 65504
+        const unsigned cross_thr = it.format == OUT_F16C ? 0x5f40u : 0xffffu;
         const bool pad_ch = bytes && it.px_bytes != it.C;          // bf8 pixels padded with zero channels: not counted
         Acc a{0u, 0u, 0u, 0u, 0u};
         us2 mxv = as_us2(0u);

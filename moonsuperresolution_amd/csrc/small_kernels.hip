@@ -78,14 +78,14 @@ __global__ void __launch_bounds__(256) conv_smallcin_kernel(const SmallCinParams
                 acc.x = acc.x >= 0.f ? acc.x : acc.x * p.slope; acc.y = acc.y >= 0.f ? acc.y : acc.y * p.slope;
                 acc.z = acc.z >= 0.f ? acc.z : acc.z * p.slope; acc.w = acc.w >= 0.f ? acc.w : acc.w * p.slope;
             }
-            if (p.out_split == 4) {
+            if (p.out_split == OUT_F16C) {
                 msr_store_f16c4_dev(o + (size_t)i * p.out_px, q * 4, acc.x, acc.y, acc.z, acc.w);
-            } else if (p.out_split == 3) {
+            } else if (p.out_split == OUT_BF8) {
                 unsigned w8 = 0;
                 w8 = __builtin_amdgcn_cvt_pk_bf8_f32(acc.x, acc.y, w8, false);
                 w8 = __builtin_amdgcn_cvt_pk_bf8_f32(acc.z, acc.w, w8, true);
                 reinterpret_cast<unsigned*>(o + (size_t)i * p.out_px)[q] = w8;
-            } else if (p.out_split == 2) msr_store_split4_f16(o + (size_t)i * p.out_px, q * 4, acc.x, acc.y, acc.z, acc.w);
+            } else if (p.out_split == OUT_F16X2) msr_store_split4_f16(o + (size_t)i * p.out_px, q * 4, acc.x, acc.y, acc.z, acc.w);
             else if (p.out_split) msr_store_split4_dev(o + (size_t)i * p.out_px, q * 4, acc.x, acc.y, acc.z, acc.w);
             else *reinterpret_cast<float4*>(o + (size_t)i * p.out_px + q * 4) = acc;
         }
@@ -152,14 +152,14 @@ __global__ void __launch_bounds__(256) conv_smallcin_tiled_kernel(const SmallCin
                 acc.x = acc.x >= 0.f ? acc.x : acc.x * p.slope; acc.y = acc.y >= 0.f ? acc.y : acc.y * p.slope;
                 acc.z = acc.z >= 0.f ? acc.z : acc.z * p.slope; acc.w = acc.w >= 0.f ? acc.w : acc.w * p.slope;
             }
-            if (p.out_split == 4) {
+            if (p.out_split == OUT_F16C) {
                 msr_store_f16c4_dev(o + (size_t)i * p.out_px, q * 4, acc.x, acc.y, acc.z, acc.w);
-            } else if (p.out_split == 3) {
+            } else if (p.out_split == OUT_BF8) {
                 unsigned w8 = 0;
                 w8 = __builtin_amdgcn_cvt_pk_bf8_f32(acc.x, acc.y, w8, false);
                 w8 = __builtin_amdgcn_cvt_pk_bf8_f32(acc.z, acc.w, w8, true);
                 reinterpret_cast<unsigned*>(o + (size_t)i * p.out_px)[q] = w8;
-            } else if (p.out_split == 2) msr_store_split4_f16(o + (size_t)i * p.out_px, q * 4, acc.x, acc.y, acc.z, acc.w);
+            } else if (p.out_split == OUT_F16X2) msr_store_split4_f16(o + (size_t)i * p.out_px, q * 4, acc.x, acc.y, acc.z, acc.w);
             else if (p.out_split) msr_store_split4_dev(o + (size_t)i * p.out_px, q * 4, acc.x, acc.y, acc.z, acc.w);
             else *reinterpret_cast<float4*>(o + (size_t)i * p.out_px + q * 4) = acc;
         }
