@@ -14,6 +14,23 @@ from typing import Callable, List, Sequence, Tuple
 import numpy as np
 
 
+def tile_origins(shape: Tuple[int, int], tile_size: int) -> List[Tuple[int, int]]:
+    """generateTileList, process_full_tiles.py:313-325: (xx, yy) of every tile of a raster of ``shape``, y outer."""
+    return [(xx, yy) for yy in range(0, shape[0], tile_size) for xx in range(0, shape[1], tile_size)]
+
+
+def patch_origins_1d(p: int, image_size: int, stride: int, tile_size: int) -> range:
+    """Patch origins along one axis of the tile at ``p`` (padded-canvas coordinates), process_full_tiles.py:453-454.
+    The ONE statement of that rule on the device side: the tile loop (tiler._prepare_tile, patchOrigins), the halo mode's
+    patch grid (halo.patchGrid) and ``input_rows`` below all enumerate origins through it."""
+    return range(p, p + tile_size + image_size - stride, stride)
+
+
+def patch_grid_1d(tile_coords: Sequence[int], image_size: int, stride: int, tile_size: int) -> List[int]:
+    """Sorted union of the patch origins of the tiles at ``tile_coords`` along one axis (the halo mode's grid)."""
+    return sorted({o for p in tile_coords for o in patch_origins_1d(p, image_size, stride, tile_size)})
+
+
 def tile_rows(tiles: Sequence[Tuple[int, int]]) -> List[int]:
     return sorted({yy for _, yy in tiles})
 
@@ -191,3 +208,68 @@ def halo_zone_rows(ys: Sequence[int], image_size: int, world: int):
         if r + 2 < world and out[r]["touch_hi"] > out[r + 2]["touch_lo"]:
             raise ValueError("halo mode: too few patch rows per rank (a pixel would need three ranks)")
     return out
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# Row windows: which raster rows a rank has to read, pad and upload
+# ----------------------------------------------------------------------------------------------------------------
+def input_rows(shape: Tuple[int, int], image_size: int, stride: int, tile_size: int, rank: int, world: int,
+               mode: str) -> Tuple[int, int]:
+    """Raster rows [r0, r1) (un-padded coordinates) that the patches of ``rank`` can touch.
+
+    mode "tiles": the patches of the tiles ``shard_tile_rows`` gives the rank; mode "halo": the patch rows
+    ``halo_zone_rows`` gives it (the boundary zones it sends and merges are accumulators of those same patches: they
+    reach no further raster row).  A patch at canvas origin y reads canvas rows [y, y + S); canvas row c is raster row
+    c - (S - s) (padInputs); the range is clipped to the raster.  ``world == 1`` gives (0, H), a rank without work (0, 0).
+    Pure arithmetic on the origin enumeration the device code uses (patch_origins_1d): no torch, no library."""
+    if mode not in ("tiles", "halo"):
+        raise ValueError(f"mode must be 'tiles' or 'halo', got {mode!r}")
+    if not 0 <= rank < world:
+        raise ValueError("rank out of range")
+    H = int(shape[0])
+    S, s, T = image_size, stride, tile_size
+    if world == 1:
+        return 0, H
+    tiles = tile_origins(shape, T)
+    if mode == "tiles":
+        mine = tile_rows(shard_tile_rows(tiles, rank, world))
+        if not mine:
+            return 0, 0
+        first, last = patch_origins_1d(mine[0], S, s, T)[0], patch_origins_1d(mine[-1], S, s, T)[-1]
+    else:
+        ys = patch_grid_1d(tile_rows(tiles), S, s, T)
+        z = halo_zone_rows(ys, S, world)[rank]
+        first, last = ys[z["g0"]], ys[z["g1"] - 1]
+    r0, r1 = max(0, first - (S - s)), min(H, last + S - (S - s))
+    return (r0, r1) if r1 > r0 else (0, 0)
+
+
+def canvas_shape(shape: Tuple[int, int], image_size: int, stride: int) -> Tuple[int, int]:
+    """padInputs, process_full_tiles.py:246-267: the no_value canvas is ((dim // 1024) + 1) * 1024 + 2 (S - s) a side."""
+    halo = image_size - stride
+    return ((shape[0] // 1024) + 1) * 1024 + 2 * halo, ((shape[1] // 1024) + 1) * 1024 + 2 * halo
+
+
+def canvas_rows(shape: Tuple[int, int], image_size: int, stride: int, r0: int, r1: int) -> Tuple[int, int]:
+    """Canvas rows [c0, c1) that raster rows [r0, r1) occupy in padInputs' canvas: shifted by the S - s margin, and a
+    window that touches the raster's first / last row also takes the no_value margin above / below it."""
+    H = int(shape[0])
+    halo = image_size - stride
+    full = canvas_shape(shape, image_size, stride)[0]
+    return (0 if r0 == 0 else r0 + halo), (full if r1 == H else r1 + halo)
+
+
+def crop_for_rank(dsr, rank: int, world: int, mode: str = "tiles") -> Tuple[int, int]:
+    """Keep only the raster rows ``rank`` needs of the host rasters a DEMSuperResolution holds (setImages / loadImages
+    done, padInputs not yet): the canvas padInputs then builds is that row window, not the whole raster.  Run it before
+    ``process_map_sharded(..., dsr.processTile, rank, world)``.  Returns the rows kept."""
+    if dsr.img is None or dsr.dem is None:
+        raise ValueError("crop_for_rank needs the host rasters: call it after setImages / loadImages, before padInputs")
+    r0, r1 = input_rows(dsr.dem_shape, dsr.image_size, dsr.stride, dsr.tile_size, rank, world, mode)
+    a, b = r0 - dsr.row0, r1 - dsr.row0
+    if a < 0 or b > dsr.dem.shape[0]:
+        raise ValueError(f"the rasters held (rows [{dsr.row0}, {dsr.row0 + dsr.dem.shape[0]})) do not contain rank "
+                         f"{rank}'s rows [{r0}, {r1})")
+    dsr.setImages(np.ascontiguousarray(dsr.img[a:b]), np.ascontiguousarray(dsr.dem[a:b]), row0=r0,
+                  full_shape=dsr.dem_shape)
+    return r0, r1

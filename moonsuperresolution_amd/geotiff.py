@@ -9,6 +9,8 @@ and ``_good.tiff`` (UInt16) as LZW GeoTIFFs with ``PREDICTOR=2`` and a nodata ta
 * read: classic TIFF and BigTIFF, either byte order, strips or tiles, compression none / LZW / Deflate / PackBits,
   predictor 1 / 2 / 3, 8/16/32/64-bit (un)signed integer and IEEE float samples, chunky or planar multi-band files
   (band 1 is returned, like the reference); the result is float32.
+  ``rows=(r0, r1)`` reads a row window and decodes only the strips / tiles that intersect it; ``read_info`` returns the
+  metadata (shape included) from the header alone — what a rank of a sharded run needs to read only its own rows.
 * write: single band, little-endian, strips, LZW + horizontal predictor (or none / deflate), classic TIFF or BigTIFF
   chosen by size, GDAL_NODATA tag, and the GeoTIFF georeferencing tags of the input **passed through verbatim**
   (ModelPixelScale 33550, ModelTiepoint 33922, ModelTransformation 34264, GeoKeyDirectory 34735, GeoDoubleParams
@@ -106,10 +108,8 @@ def _values(entry, bo: str):
     return vals
 
 
-def read_geotiff(path: str, band: int = 1):
-    """Band ``band`` (1-based, like GDAL's GetRasterBand) of a (Geo)TIFF as float32, plus its metadata:
-    ``{"geo": {tag: (type, count, raw bytes)}, "nodata": float | None, "dtype": numpy dtype of the file,
-    "shape": (rows, cols), "byteorder": "<" | ">"}``.  Counterpart of loadImages (process_full_tiles.py:158-182)."""
+def _open(path: str):
+    """Header and first IFD of a (Geo)TIFF: (memory map, tag dict, byte order, meta).  No pixel block is touched."""
     buf = np.memmap(path, dtype=np.uint8, mode="r")
     head = bytes(buf[:16])
     if head[:2] == b"II":
@@ -131,18 +131,60 @@ def read_geotiff(path: str, band: int = 1):
         return _values(t[tag], bo) if tag in t else default
 
     cols, rows = val(256)[0], val(257)[0]
-    spp = val(277, (1,))[0]
     bps = val(258, (1,))[0]
     fmt = val(339, (1,))[0]
+    kind = {1: "u", 2: "i", 3: "f"}.get(fmt)
+    if kind is None or bps not in (8, 16, 32, 64) or (kind == "f" and bps < 32):
+        raise ValueError(f"{path}: unsupported sample format {fmt} / {bps} bits")
+    dt = np.dtype(f"{bo}{kind}{bps // 8}")
+    nodata = None
+    if GDAL_NODATA in t:
+        try:
+            nodata = float(t[GDAL_NODATA][2].split(b"\0")[0].decode())
+        except ValueError:
+            nodata = None
+    meta = {"geo": {k: t[k] for k in GEO_TAGS if k in t}, "nodata": nodata, "dtype": dt.newbyteorder("="),
+            "shape": (rows, cols), "byteorder": bo, "window": (0, rows)}
+    return buf, t, bo, meta
+
+
+def read_info(path: str) -> dict:
+    """The ``meta`` of ``read_geotiff`` (shape, dtype, nodata, georeferencing; ``window`` = the whole raster) from the
+    header alone: no strip or tile is decoded.  A rank needs the shape before it can choose its row window."""
+    return _open(path)[3]
+
+
+def read_geotiff(path: str, band: int = 1, rows: Optional[Tuple[int, int]] = None):
+    """Band ``band`` (1-based, like GDAL's GetRasterBand) of a (Geo)TIFF as float32, plus its metadata:
+    ``{"geo": {tag: (type, count, raw bytes)}, "nodata": float | None, "dtype": numpy dtype of the file,
+    "shape": (rows, cols), "byteorder": "<" | ">", "window": (r0, r1)}``.  Counterpart of loadImages
+    (process_full_tiles.py:158-182).
+
+    ``rows=(r0, r1)`` returns only raster rows [r0, r1) as [r1 - r0, cols] — bit for bit the slice of the full read — and
+    decodes only the strips / tiles that intersect them (blocks are compressed independently and both predictors run
+    along a row, so a block never needs its neighbours).  ``meta["shape"]`` stays the file's shape; ``meta["window"]``
+    is the window returned.  ValueError unless 0 <= r0 < r1 <= rows of the file."""
+    buf, t, bo, meta = _open(path)
+
+    def val(tag, default=None):
+        return _values(t[tag], bo) if tag in t else default
+
+    nrows, cols = meta["shape"]
+    if rows is None:
+        r0, r1 = 0, nrows
+    else:
+        r0, r1 = int(rows[0]), int(rows[1])
+        if not 0 <= r0 < r1 <= nrows:
+            raise ValueError(f"{path}: row window ({r0}, {r1}) is not inside the raster's {nrows} rows")
+    rows = nrows
+    spp = val(277, (1,))[0]
+    bps = val(258, (1,))[0]
     comp = val(259, (1,))[0]
     pred = val(317, (1,))[0]
     planar = val(284, (1,))[0]
     if not 1 <= band <= spp:
         raise ValueError(f"band {band} out of range: the file has {spp}")
-    kind = {1: "u", 2: "i", 3: "f"}.get(fmt)
-    if kind is None or bps not in (8, 16, 32, 64) or (kind == "f" and bps < 32):
-        raise ValueError(f"{path}: unsupported sample format {fmt} / {bps} bits")
-    dt = np.dtype(f"{bo}{kind}{bps // 8}")
+    dt = np.dtype(meta["dtype"]).newbyteorder(bo)
     tiled = 322 in t
     if tiled:
         bw, bh = val(322)[0], val(323)[0]
@@ -154,9 +196,9 @@ def read_geotiff(path: str, band: int = 1):
     across, down = -(-cols // bw), -(-rows // bh)
     per_plane = across * down
     chunk_spp = 1 if planar == 2 else spp
-    out = np.empty((rows, cols), np.float32)
+    out = np.empty((r1 - r0, cols), np.float32)
     plane0 = (band - 1) * per_plane if planar == 2 else 0
-    for by in range(down):
+    for by in range(r0 // bh, -(-r1 // bh)):          # the block rows that intersect [r0, r1)
         for bx in range(across):
             i = plane0 + by * across + bx
             raw = bytes(buf[offs[i]:offs[i] + cnts[i]])
@@ -188,16 +230,10 @@ def read_geotiff(path: str, band: int = 1):
                     arr = np.cumsum(arr.astype(dt.newbyteorder("=")).view(ut), axis=1, dtype=ut).view(dt.newbyteorder("="))
             ch = 0 if planar == 2 else band - 1
             y0, x0 = by * bh, bx * bw
-            hh, ww = min(h, rows - y0), min(bw, cols - x0)
-            out[y0:y0 + hh, x0:x0 + ww] = arr[:hh, :ww, ch]
-    nodata = None
-    if GDAL_NODATA in t:
-        try:
-            nodata = float(t[GDAL_NODATA][2].split(b"\0")[0].decode())
-        except ValueError:
-            nodata = None
-    meta = {"geo": {k: t[k] for k in GEO_TAGS if k in t}, "nodata": nodata, "dtype": dt.newbyteorder("="),
-            "shape": (rows, cols), "byteorder": bo}
+            ya, yb = max(y0, r0), min(y0 + h, rows, r1)      # the block's rows inside the window
+            ww = min(bw, cols - x0)
+            out[ya - r0:yb - r0, x0:x0 + ww] = arr[ya - y0:yb - y0, :ww, ch]
+    meta["window"] = (r0, r1)
     return out, meta
 
 

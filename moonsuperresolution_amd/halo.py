@@ -31,7 +31,7 @@ import numpy as np
 import torch
 
 from . import _lib
-from .distributed import halo_zone_rows
+from .distributed import halo_zone_rows, patch_grid_1d
 from .tiler import DEMSuperResolution
 
 
@@ -46,23 +46,26 @@ class HaloShardedSuperResolution(DEMSuperResolution):
             # stride relative to every T x T block would be dropped silently (and the union grid would be irregular)
             raise ValueError(f"halo mode needs a stride that divides image_size and tile_size (got stride {s}, "
                              f"image_size {S}, tile_size {T}); use the tile mode (processMap) for other strides")
-        span = T + S - s
-        ys = sorted({y for _, py in self.generateTileList() for y in range(py, py + span, s)})
-        xs = sorted({x for px, _ in self.generateTileList() for x in range(px, px + span, s)})
+        tiles = self.generateTileList()
+        ys = patch_grid_1d(sorted({py for _, py in tiles}), S, s, T)
+        xs = patch_grid_1d(sorted({px for px, _ in tiles}), S, s, T)
         return ys, xs
 
     # ------------------------------------------------------------------------------------------------------------
     def _generate_rows(self, ys: Sequence[int], xs: Sequence[int]):
         """Validity, normalisation statistics, device-side batch assembly and the generator calls for every patch at
-        rows `ys`: returns (preds [ncall * B, S, S], keys [cap, 2] canvas origins, dmm [cap, 2], valid count)."""
+        rows `ys`: returns (preds [ncall * B, S, S], keys [cap, 2] canvas origins, dmm [cap, 2], valid count).
+        The kernels that read the canvas get window rows (origin - canvas_row0, tiler.padInputs); the keys stay canvas
+        origins (msr_compact_patches subtracts tile_y = -canvas_row0)."""
         S, B = self.image_size, self.batch_size
         lib, h, dev = self._lib, self._h, self.device
-        rows, cols = self.dem_padded_shape
+        c0, rows, cols = self._window()
+        self._check_rows(f"patch rows {ys[0]} .. {ys[-1]}", ys)
         with torch.cuda.device(dev):
             cur = torch.cuda.current_stream(dev)
             stream = cur.cuda_stream
             xt = torch.tensor(xs, dtype=torch.int32, device=dev)
-            yt = torch.tensor(ys, dtype=torch.int32, device=dev)
+            yt = torch.tensor([y - c0 for y in ys], dtype=torch.int32, device=dev)
             ox = xt.repeat(len(ys))
             oy = yt.repeat_interleave(len(xs))
             n = int(ox.numel())
@@ -78,7 +81,7 @@ class HaloShardedSuperResolution(DEMSuperResolution):
             rc = lib.msr_patch_stats(h, self.img_padded.data_ptr(), self.dem_padded.data_ptr(), rows, cols, ox.data_ptr(),
                                      oy.data_ptr(), n, self.no_value, valid.data_ptr(), minmax.data_ptr(), stream)
             _lib.raise_for(lib, h, rc, "msr_patch_stats")
-            rc = lib.msr_compact_patches(h, valid.data_ptr(), ox.data_ptr(), oy.data_ptr(), minmax.data_ptr(), n, 0, 0, B,
+            rc = lib.msr_compact_patches(h, valid.data_ptr(), ox.data_ptr(), oy.data_ptr(), minmax.data_ptr(), n, 0, -c0, B,
                                          cap, sx.data_ptr(), sy.data_ptr(), mm_sel.data_ptr(), keys.data_ptr(),
                                          dmm.data_ptr(), meta.data_ptr(), stream)
             _lib.raise_for(lib, h, rc, "msr_compact_patches")
@@ -159,14 +162,24 @@ class HaloShardedSuperResolution(DEMSuperResolution):
         return mean, std, good
 
     # ------------------------------------------------------------------------------------------------------------
+    def cropInputs(self, rank: int, world: int) -> Tuple[int, int]:
+        """Keep only the raster rows this rank's patch rows read (distributed.input_rows, mode "halo") of the host rasters
+        held; padInputs then builds that row window of the canvas.  Returns the rows kept."""
+        from .distributed import crop_for_rank
+        return crop_for_rank(self, rank, world, "halo")
+
     def haloAccumulate(self, rank: int = 0, world: int = 1, band_rows: Optional[int] = None, band_bytes: int = 4 << 30,
-                       max_rows: int = 0):
+                       max_rows: int = 0, crop_inputs: bool = False):
         """Phase 1 (no communication): generate this rank's patch rows band by band and accumulate them.  Returns the
         state ``haloFinish`` takes: the accumulators of the canvas rows the rank's patches reach, what it must send to its
         neighbours and the shapes of what it receives.  ``band_rows`` patch rows per band (default: as many as fit
         ``band_bytes`` of predictions); ``max_rows`` > 0 stops after that many patch rows (benchmarks of a share of a
-        large raster: the accumulators of the rows not reached stay empty)."""
+        large raster: the accumulators of the rows not reached stay empty).  ``crop_inputs``: when the instance still
+        holds host rasters, keep only this rank's rows of them (cropInputs) before they are padded and uploaded; the
+        accumulators, the zones and the result are the same bits."""
         if self.dem_padded is None or self.dem is not None:
+            if crop_inputs and self.dem is not None:
+                self.cropInputs(rank, world)
             self.padInputs()
         S, T = self.image_size, self.tile_size
         p = S // 16
@@ -251,13 +264,15 @@ class HaloShardedSuperResolution(DEMSuperResolution):
         return (mean, std, good), (own_lo, own_hi)
 
     def processMapHalo(self, img: Optional[np.ndarray] = None, dem: Optional[np.ndarray] = None, rank: int = 0,
-                       world: int = 1, exchange: Optional[Callable] = None, band_rows: Optional[int] = None):
+                       world: int = 1, exchange: Optional[Callable] = None, band_rows: Optional[int] = None,
+                       crop_inputs: bool = False):
         """This rank's share of the map in halo mode: accumulate band by band, start the exchange of the boundary zones
         with the neighbours (non-blocking send / recv: distributed.exchange_halo_start, RCCL on the GPUs), finalise the
-        interior rows beside it, then the zones.  ``exchange``: a blocking replacement with exchange_halo's signature."""
+        interior rows beside it, then the zones.  ``exchange``: a blocking replacement with exchange_halo's signature.
+        ``crop_inputs``: pad and upload only the raster rows this rank's patches read (haloAccumulate)."""
         if img is not None:
             self.setImages(img, dem)
-        st = self.haloAccumulate(rank, world, band_rows=band_rows)
+        st = self.haloAccumulate(rank, world, band_rows=band_rows, crop_inputs=crop_inputs)
         if world == 1:
             return self.haloFinish(st)
         torch.cuda.current_stream(self.device).synchronize()      # the slabs are complete before they are sent
@@ -275,4 +290,27 @@ class HaloShardedSuperResolution(DEMSuperResolution):
         halo = self.image_size - self.stride
         h, w = self.dem_shape
         parts = [torch.cat([sl[0][k] for sl in slabs], dim=0) for k in range(3)]
+        return tuple(p[halo:halo + h, halo:halo + w].cpu().numpy() for p in parts)
+
+    def _process_files_sharded(self, preprocess: bool, rank: int, world: int, mode: str, gather: bool):
+        """processFiles(mode="halo"): this rank reads only the rows its patch rows touch, runs its share (processMapHalo:
+        the zone exchange needs an initialised process group when world > 1) and, with ``gather``, all-gathers the slabs;
+        without it the rows other ranks own stay zero."""
+        if mode != "halo":
+            return super()._process_files_sharded(preprocess, rank, world, mode, gather)
+        from .distributed import all_gather_var_rows
+        self._load_rank_rows(preprocess, rank, world, mode)
+        (m, sd, g), (own_lo, own_hi) = self.processMapHalo(rank=rank, world=world)
+        hp = self.dem_padded_shape[0]
+        if world > 1 and gather:
+            ys, _ = self.patchGrid()
+            zones = halo_zone_rows(ys, self.image_size, world)
+            counts = [(hp if z["own_hi"] is None else z["own_hi"]) - z["own_lo"] for z in zones]
+            parts = [all_gather_var_rows(t, counts) for t in (m, sd, g)]
+        else:
+            parts = [torch.zeros((hp,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device) for t in (m, sd, g)]
+            for full, t in zip(parts, (m, sd, g)):
+                full[own_lo:own_hi] = t
+        halo = self.image_size - self.stride
+        h, w = self.dem_shape
         return tuple(p[halo:halo + h, halo:halo + w].cpu().numpy() for p in parts)

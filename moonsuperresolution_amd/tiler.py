@@ -27,6 +27,7 @@ import numpy as np
 import torch
 
 from . import _lib
+from .distributed import canvas_rows, canvas_shape, patch_origins_1d, tile_origins
 
 
 @dataclasses.dataclass
@@ -144,21 +145,42 @@ class DEMSuperResolution:
         _lib.raise_for(self._lib, self._h, rc, "msr_set_blend_window")
         self.dem = self.img = None
         self.dem_padded = self.img_padded = None
+        self.row0 = 0                                # first raster row of the arrays given to setImages
+        self.canvas_row0 = 0                         # first canvas row of dem_padded / img_padded (padInputs)
 
     # ------------------------------------------------------------------------------------------------
-    def setImages(self, img: np.ndarray, dem: np.ndarray) -> None:
-        """Stand-in for loadImages + preprocess (process_full_tiles.py:158-244): takes the arrays directly."""
+    def setImages(self, img: np.ndarray, dem: np.ndarray, row0: int = 0,
+                  full_shape: Optional[Tuple[int, int]] = None) -> None:
+        """Stand-in for loadImages + preprocess (process_full_tiles.py:158-244): takes the arrays directly.
+
+        With ``row0`` / ``full_shape`` the arrays are a ROW WINDOW: raster rows [row0, row0 + img.shape[0]) of a raster
+        of ``full_shape`` (what a rank of a sharded run needs: distributed.input_rows).  ``dem_shape`` / ``img_shape``
+        stay the full shape, so the tile list, the canvas geometry and the stitched map do not change; only padInputs
+        allocates less, and a tile whose patches leave the window is an error (processTile)."""
         img = np.asarray(img, np.float32)
         dem = np.asarray(dem, np.float32)
         if img.shape != dem.shape or img.ndim != 2:
             raise ValueError("The ortho-image and the DEM must be 2-D arrays of the same shape.")
+        full = tuple(int(v) for v in (dem.shape if full_shape is None else full_shape))
+        row0 = int(row0)
+        if len(full) != 2 or full[1] != dem.shape[1] or row0 < 0 or row0 + dem.shape[0] > full[0]:
+            raise ValueError(f"rows [{row0}, {row0 + dem.shape[0]}) x {dem.shape[1]} columns are not a row window of a "
+                             f"raster of shape {full}")
         self.img, self.dem = img, dem
-        self.dem_shape = dem.shape
-        self.img_shape = img.shape
+        self.row0 = row0
+        self.dem_shape = full
+        self.img_shape = full
 
-    def loadImages(self) -> None:
+    @property
+    def windowed(self) -> bool:
+        """True when the host rasters held are a row window, not the whole raster."""
+        return self.dem is not None and tuple(self.dem.shape) != tuple(self.dem_shape)
+
+    def loadImages(self, rows: Optional[Tuple[int, int]] = None) -> None:
         """process_full_tiles.py:158-182 without GDAL: band 1 of ``<source_folder_path>/<ortho_image_name>`` and
         ``<dem_name>`` as float32 (geotiff.read_geotiff), georeferencing of the DEM kept for saveGTiff.
+        ``rows=(r0, r1)`` reads only those raster rows of both files (only the strips / tiles that hold them are decoded)
+        and sets them as a row window (setImages).
 
         Raises ValueError if a path does not exist (same messages as the reference)."""
         from . import geotiff
@@ -168,10 +190,15 @@ class DEMSuperResolution:
             raise ValueError("The path given for the ortho-image does not exist. Provided path is: " + img_path)
         if not os.path.exists(dem_path):
             raise ValueError("The path given for the dem does not exist. Provided path is: " + dem_path)
-        img, _ = geotiff.read_geotiff(img_path, band=1)
-        dem, self.geo_meta = geotiff.read_geotiff(dem_path, band=1)
+        img, img_meta = geotiff.read_geotiff(img_path, band=1, rows=rows)
+        dem, self.geo_meta = geotiff.read_geotiff(dem_path, band=1, rows=rows)
         self.geo_transform = geotiff.geotransform(self.geo_meta)
-        self.setImages(img, dem)
+        if rows is None:
+            self.setImages(img, dem)
+        else:
+            if img_meta["shape"] != self.geo_meta["shape"]:
+                raise ValueError("The ortho-image and the DEM must be 2-D arrays of the same shape.")
+            self.setImages(img, dem, row0=self.geo_meta["window"][0], full_shape=self.geo_meta["shape"])
 
     def saveGTiff(self, data: np.ndarray, data_type, name: str) -> None:
         """process_full_tiles.py:481-531 without GDAL: ``<save_path>/<map_name>_<name>.tiff``, LZW + PREDICTOR=2,
@@ -204,48 +231,128 @@ class DEMSuperResolution:
 
         ``swap_dsize=True`` keeps the reference's (rows, cols)-as-(width, height) argument of :241, so a non-square
         raster ends with a transposed-shape DEM and fails in padInputs exactly as the reference does; pass False to
-        resize to the raster's own shape."""
+        resize to the raster's own shape.
+
+        Whole rasters only: in-filling and the two resamplers are whole-raster operations with the reference's quirks
+        (DESIGN.md section 7.3), so with a row window set (setImages(row0=, full_shape=), loadImages(rows=)) this raises
+        ValueError — pre-process the whole raster first and window the result."""
         from . import preprocess as pp
         if self.img is None or self.dem is None:
             raise ValueError("preprocess needs the rasters: call loadImages() or setImages() first.")
+        if self.windowed:
+            raise ValueError(f"preprocess works on whole rasters: rows [{self.row0}, {self.row0 + self.dem.shape[0]}) of "
+                             f"{self.dem_shape[0]} are set as a row window")
         self.image, self.dem = pp.preprocess(self._lib, self._h, self.device, self.img, self.dem, self.no_value,
                                              swap_dsize=swap_dsize)
 
-    def processFiles(self, preprocess: bool = True) -> None:
+    def processFiles(self, preprocess: bool = True, rank: int = 0, world: int = 1, mode: Optional[str] = None,
+                     gather: bool = True) -> None:
         """processMap of the reference on files (process_full_tiles.py:568-587): loadImages -> preprocess ->
         padInputs -> tiles -> rebuildMap -> ``<map>_mean.tiff``, ``<map>_std.tiff``, ``<map>_good.tiff``.
-        ``preprocess=False`` skips the low-resolution-DEM synthesis (feed an already pre-processed DEM)."""
-        self.loadImages()
-        if preprocess:
-            self.preprocess()
-        mean, std, good = self.processMap()
+        ``preprocess=False`` skips the low-resolution-DEM synthesis (feed an already pre-processed DEM).
+
+        ``mode="tiles"``: this process is ``rank`` of ``world`` of a tile-row-sharded run.  It reads the shape from the
+        header (geotiff.read_info), decodes and uploads only the raster rows its tiles touch (distributed.input_rows,
+        loadImages(rows=)), runs its tile rows (distributed.process_map_sharded) and, with ``gather`` (needs an initialised
+        process group), all-gathers the finished rows; without it the rows of other ranks stay zero in the files written.
+        Pre-processing is a whole-raster operation: ``preprocess`` must be False.  ``mode="halo"`` is accepted by
+        HaloShardedSuperResolution.processFiles only."""
+        if mode is not None:
+            mean, std, good = self._process_files_sharded(preprocess, rank, world, mode, gather)
+        else:
+            self.loadImages()
+            if preprocess:
+                self.preprocess()
+            mean, std, good = self.processMap()
         self.saveGTiff(mean, mean.dtype, "mean")
         self.saveGTiff(std, std.dtype, "std")
         self.saveGTiff(good, good.dtype, "good")
 
+    def _load_rank_rows(self, preprocess: bool, rank: int, world: int, mode: str) -> Tuple[int, int]:
+        """read_info -> input_rows -> loadImages(rows=): the rows of both files that ``rank`` needs, nothing else."""
+        from . import geotiff
+        from .distributed import input_rows
+        if preprocess:
+            raise ValueError("a sharded rank reads a row window and preprocess works on whole rasters: pre-process the "
+                             "rasters first and pass preprocess=False")
+        dem_path = os.path.join(self.folder_path, self.dem_name)
+        if not os.path.exists(dem_path):
+            raise ValueError("The path given for the dem does not exist. Provided path is: " + dem_path)
+        shape = geotiff.read_info(dem_path)["shape"]
+        r0, r1 = input_rows(shape, self.image_size, self.stride, self.tile_size, rank, world, mode)
+        if r1 > r0:
+            self.loadImages(rows=(r0, r1))
+        else:                                         # a rank without work: no pixel is read
+            self.geo_meta = geotiff.read_info(dem_path)
+            self.geo_transform = geotiff.geotransform(self.geo_meta)
+            empty = np.empty((0, shape[1]), np.float32)
+            self.setImages(empty, empty, row0=0, full_shape=shape)
+        return r0, r1
+
+    def _process_files_sharded(self, preprocess: bool, rank: int, world: int, mode: str, gather: bool):
+        from .distributed import process_map_sharded
+        if mode != "tiles":
+            raise ValueError(f"DEMSuperResolution.processFiles shards by tile rows (mode='tiles'), got {mode!r}; the halo "
+                             "mode is HaloShardedSuperResolution.processFiles")
+        self._load_rank_rows(preprocess, rank, world, mode)
+        self.padInputs()
+        return process_map_sharded(self.dem_shape, self.tile_size, self.generateTileList(), self.processTile, rank, world,
+                                   gather=gather, device=self.device)
+
     def padInputs(self) -> None:
-        """process_full_tiles.py:246-267: no_value canvas ((dim//1024)+1)*1024 + 2(S-s), data at offset (S-s)."""
+        """process_full_tiles.py:246-267: no_value canvas ((dim//1024)+1)*1024 + 2(S-s), data at offset (S-s).
+
+        When the rasters set are a row window (setImages), only the canvas rows [c0, c1) those raster rows occupy are
+        allocated (distributed.canvas_rows: a window that touches the raster's first / last row keeps the no_value margin
+        above / below it).  ``canvas_row0`` = c0 and ``dem_window_shape`` = the tensors' shape; ``dem_padded_shape`` stays
+        the full canvas.  The coordinates rule: the kernels that read the canvas (msr_patch_stats, msr_extract_patches,
+        and msr_compact_patches' origins) see WINDOW rows, canvas row - c0; keys and everything downstream see canvas
+        rows.  With the whole raster given, c0 = 0 and the tensors are the full canvas."""
         S, s = self.image_size, self.stride
-        new_x = ((self.dem_shape[1] // 1024) + 1) * 1024 + (S - s) * 2
-        new_y = ((self.dem_shape[0] // 1024) + 1) * 1024 + (S - s) * 2
+        new_y, new_x = canvas_shape(self.dem_shape, S, s)
         self.pad_x = new_x - self.dem_shape[1] - (S - s)
         self.pad_y = new_y - self.dem_shape[0] - (S - s)
+        n, w = self.dem.shape
+        c0, c1 = canvas_rows(self.dem_shape, S, s, self.row0, self.row0 + n)
         with torch.cuda.device(self.device):
-            self.dem_padded = torch.full((new_y, new_x), self.no_value, dtype=torch.float32, device=self.device)
-            self.img_padded = torch.full((new_y, new_x), self.no_value, dtype=torch.float32, device=self.device)
-            h, w = self.dem_shape
-            self.dem_padded[S - s:S - s + h, S - s:S - s + w] = torch.from_numpy(self.dem).to(self.device)
-            self.img_padded[S - s:S - s + h, S - s:S - s + w] = torch.from_numpy(self.img).to(self.device)
+            self.dem_padded = torch.full((c1 - c0, new_x), self.no_value, dtype=torch.float32, device=self.device)
+            self.img_padded = torch.full((c1 - c0, new_x), self.no_value, dtype=torch.float32, device=self.device)
+            y = self.row0 + (S - s) - c0                           # the first raster row given, in window rows
+            self.dem_padded[y:y + n, S - s:S - s + w] = torch.from_numpy(self.dem).to(self.device)
+            self.img_padded[y:y + n, S - s:S - s + w] = torch.from_numpy(self.img).to(self.device)
             torch.cuda.current_stream(self.device).synchronize()   # the tile loop reads the canvases on other streams
-        self.dem_padded_shape = tuple(self.dem_padded.shape)
-        self.img_padded_shape = tuple(self.img_padded.shape)
+        self.canvas_row0 = c0
+        self.dem_window_shape = self.img_window_shape = tuple(self.dem_padded.shape)
+        self.dem_padded_shape = (new_y, new_x)
+        self.img_padded_shape = (new_y, new_x)
         self.dem = None
         self.img = None
 
     def generateTileList(self) -> List[Tuple[int, int]]:
         """process_full_tiles.py:313-325 — (xx, yy), y outer; the unit tiles are sharded by across GPUs."""
-        return [(xx, yy) for yy in range(0, self.dem_shape[0], self.tile_size)
-                for xx in range(0, self.dem_shape[1], self.tile_size)]
+        return tile_origins(self.dem_shape, self.tile_size)
+
+    def _window(self) -> Tuple[int, int, int]:
+        """(c0, rows, cols) of the canvas tensors: their first canvas row and their own shape — what the kernels that read
+        them take.  Tensors a caller assigned to dem_padded / img_padded directly are a whole canvas (c0 = 0)."""
+        rows, cols = self.dem_padded.shape
+        full = tuple(self.dem_padded_shape) == (rows, cols)
+        return (0 if full else self.canvas_row0), rows, cols
+
+    def _check_rows(self, what: str, ys: Sequence[int]) -> None:
+        """Every patch row at canvas origin y in ``ys`` reads canvas rows [y, y + S), clipped to the canvas (a patch that
+        leaves the CANVAS is invalid, as ever: msr_patch_stats).  They must lie in the row window — unless they lie wholly in
+        the no_value margin above or below the raster, where the patch is invalid with or without a window (the kernel sees
+        an origin outside its rows and reads nothing)."""
+        c0, rows, _ = self._window()
+        if c0 == 0 and rows == self.dem_padded_shape[0]:
+            return
+        halo = self.image_size - self.stride
+        for y in ys:
+            lo, hi = y, min(y + self.image_size, self.dem_padded_shape[0])
+            if not (c0 <= lo and hi <= c0 + rows) and not (hi <= halo or lo >= halo + self.dem_shape[0]):
+                raise ValueError(f"{what}: the patch row at {y} reads canvas rows [{lo}, {hi}), outside the row window "
+                                 f"[{c0}, {c0 + rows}) this instance holds")
 
     # ------------------------------------------------------------------------------------------------
     def _stream(self):
@@ -272,9 +379,9 @@ class DEMSuperResolution:
 
     def patchOrigins(self, px: int, py: int) -> np.ndarray:
         """[n, 2] int32 (xx, yy) in padded coordinates, generation order (process_full_tiles.py:453-454)."""
-        span = self.tile_size + self.image_size - self.stride
-        ys = np.arange(py, py + span, self.stride, dtype=np.int32)
-        xs = np.arange(px, px + span, self.stride, dtype=np.int32)
+        S, s, T = self.image_size, self.stride, self.tile_size
+        ys = np.array(patch_origins_1d(py, S, s, T), dtype=np.int32)
+        xs = np.array(patch_origins_1d(px, S, s, T), dtype=np.int32)
         return np.stack([np.tile(xs, len(ys)), np.repeat(ys, len(xs))], axis=1)
 
     # -- one tile = prepare (validity, min/max, device-side batch assembly) -> generate -> stitch -------------------
@@ -296,12 +403,13 @@ class DEMSuperResolution:
         if getattr(self, "_raster_token", None) != token:
             self._prep_stream.wait_stream(torch.cuda.current_stream(dev))
             self._raster_token = token
-        rows, cols = self.dem_padded_shape
-        span = T + S - s
+        c0, rows, cols = self._window()
+        rx, ry = patch_origins_1d(px, S, s, T), patch_origins_1d(py, S, s, T)
+        self._check_rows(f"tile ({px}, {py})", ry)
         st = {"px": px, "py": py}
         with torch.cuda.device(dev), torch.cuda.stream(self._prep_stream):
-            xs = torch.arange(px, px + span, s, dtype=torch.int32, device=dev)
-            ys = torch.arange(py, py + span, s, dtype=torch.int32, device=dev)
+            xs = torch.arange(rx.start, rx.stop, rx.step, dtype=torch.int32, device=dev)
+            ys = torch.arange(ry.start - c0, ry.stop - c0, ry.step, dtype=torch.int32, device=dev)   # window rows
             ox = xs.repeat(ys.numel())                      # generation order: y outer, x inner (:453-454)
             oy = ys.repeat_interleave(xs.numel())
             n = int(xs.numel() * ys.numel())
@@ -319,8 +427,9 @@ class DEMSuperResolution:
                                      ox.data_ptr(), oy.data_ptr(), n, self.no_value, valid.data_ptr(),
                                      minmax.data_ptr(), stream)
             _lib.raise_for(lib, h, rc, "msr_patch_stats")
-            rc = lib.msr_compact_patches(h, valid.data_ptr(), ox.data_ptr(), oy.data_ptr(), minmax.data_ptr(), n, px, py,
-                                         B, cap, sx.data_ptr(), sy.data_ptr(), mm_sel.data_ptr(), keys.data_ptr(),
+            # tile_y in window rows too: the keys (origin - tile origin) come out as in the full canvas
+            rc = lib.msr_compact_patches(h, valid.data_ptr(), ox.data_ptr(), oy.data_ptr(), minmax.data_ptr(), n, px,
+                                         py - c0, B, cap, sx.data_ptr(), sy.data_ptr(), mm_sel.data_ptr(), keys.data_ptr(),
                                          dmm.data_ptr(), meta.data_ptr(), stream)
             _lib.raise_for(lib, h, rc, "msr_compact_patches")
             meta_host = torch.empty(2, dtype=torch.int32, pin_memory=True)
@@ -336,7 +445,7 @@ class DEMSuperResolution:
         one zero-padded) and the stitcher, all on the current stream / the pipeline streams."""
         S, B = self.image_size, self.batch_size
         lib, h, dev = self._lib, self._h, self.device
-        rows, cols = self.dem_padded_shape
+        _, rows, cols = self._window()                # sx / sy are window origins already (_prepare_tile)
         st["event"].synchronize()                     # 8 bytes; the GPU keeps working on what is already queued
         self._range_retire()                          # the previous tile's scan (range_check), read at the same point
         nv, ncall = (int(v) for v in st["meta_host"].tolist())

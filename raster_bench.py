@@ -7,7 +7,11 @@
     python raster_bench.py --rows 15000 --cols 70000 --image-size 512 --stride 64 --batch-size 8 \
                            --simulate-rank 3 --simulate-world 8 --max-tiles 8     (one GPU takes rank 3's shard of 8)
 
-Every rank pads the raster, takes a contiguous block of 1024-px tile rows (moonsuperresolution_amd.distributed),
+    python raster_bench.py --halo --crop-inputs ...     (pad and upload only the rows this rank's patches touch)
+
+Every rank pads the raster (with --crop-inputs: only the row window distributed.input_rows gives it; the JSON reports
+input_rows, canvas_bytes and the peak torch allocation), takes a contiguous block of 1024-px tile rows
+(moonsuperresolution_amd.distributed),
 runs getPatch/normalize -> generator -> rebuildTile entirely on its GPU, and (with --gather) all-gathers the finished
 rows over RCCL.  Reports end-to-end patches/s and 512x512-tile-equivalents/s of generator work, per stage times
 of rank 0, and the share of time outside the generator (tiler + stitcher + host).
@@ -75,9 +79,14 @@ def main():
     ap.add_argument("--passes", type=int, default=1, help="run the shard this many times; the last pass is reported")
     ap.add_argument("--dump", default="", help="rank 0 writes the finished products (mean, std, good) to this .npz: the gathered "
                                                "rows with --gather, else its own rows (tests compare them across process counts)")
+    ap.add_argument("--crop-inputs", action="store_true",
+                    help="pad and upload only the raster rows this rank's patches touch (distributed.input_rows) instead of "
+                         "the whole raster; needs --halo or --gpus N")
     ap.add_argument("--precision", default="f16c")
     ap.add_argument("--pipeline", type=int, default=2)
     args = ap.parse_args()
+    if args.crop_inputs and not (args.halo or args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
+        ap.error("--crop-inputs needs a sharded run: --halo or --gpus N")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         # start the N ranks as fresh child processes before this one touches HIP
         with socket.socket() as sk:
@@ -91,7 +100,7 @@ def main():
     import torch
     import torch.distributed as dist
     from moonsuperresolution_amd import DEMSuperResolution, DSRConfig, Generator
-    from moonsuperresolution_amd.distributed import all_gather_rows, shard_tile_rows, tile_rows
+    from moonsuperresolution_amd.distributed import all_gather_rows, crop_for_rank, shard_tile_rows, tile_rows
 
     rank = int(os.environ.get("RANK", "0"))
     world = int(os.environ.get("WORLD_SIZE", "1"))
@@ -116,12 +125,16 @@ def main():
                              pipeline=args.pipeline)
     dsr.setImages(img, dem)
     del img, dem
-    dsr.padInputs()
-    t_setup = time.perf_counter() - t_setup
-    tiles = dsr.generateTileList()
     shard_rank, shard_world = rank, world
     if args.simulate_world > 0:
         shard_rank, shard_world = args.simulate_rank, args.simulate_world
+    rows_in = [0, args.rows]
+    if args.crop_inputs:
+        rows_in = list(crop_for_rank(dsr, shard_rank, shard_world, "halo" if args.halo else "tiles"))
+    dsr.padInputs()
+    canvas_bytes = sum(int(t.numel()) * t.element_size() for t in (dsr.dem_padded, dsr.img_padded))
+    t_setup = time.perf_counter() - t_setup
+    tiles = dsr.generateTileList()
     mine = shard_tile_rows(tiles, shard_rank, shard_world)
     if args.halo:
         from moonsuperresolution_amd import HaloShardedSuperResolution
@@ -131,6 +144,7 @@ def main():
         hs.dem_shape, hs.img_shape = dsr.dem_shape, dsr.img_shape
         hs.dem_padded, hs.img_padded = dsr.dem_padded, dsr.img_padded
         hs.dem_padded_shape, hs.img_padded_shape = dsr.dem_padded_shape, dsr.img_padded_shape
+        hs.row0, hs.canvas_row0, hs.dem_window_shape = dsr.row0, dsr.canvas_row0, dsr.dem_window_shape
         gen.forward_device(torch.zeros((B, S, S, 2), device="cuda").uniform_(-0.5, 0.5))
         if world > 1:
             dist.barrier()
@@ -182,7 +196,9 @@ def main():
                 "tiles512_per_s": float(tot[1]) * B * (S / 512.0) ** 2 / float(mx[0]),
                 "own_rows_rank0": [own_lo, own_hi], "zone_bytes_sent_rank0":
                     sum(int(t.numel()) * 4 for t in (st["send_down"], st["send_up"]) if t is not None),
-                "canvas": list(hs.dem_padded_shape), "precision": args.precision, "pipeline": args.pipeline}))
+                "canvas": list(hs.dem_padded_shape), "crop_inputs": bool(args.crop_inputs), "input_rows": rows_in,
+                "canvas_window": list(hs.dem_window_shape), "canvas_bytes": canvas_bytes,
+                "precision": args.precision, "pipeline": args.pipeline}))
         if world > 1:
             dist.destroy_process_group()
         return
@@ -251,7 +267,7 @@ def main():
         st0 = dsr._prepare_tile(*todo[0])
         st0["event"].synchronize()
         real = torch.empty((B, S, S, 2), device="cuda")
-        rows_p, cols_p = dsr.dem_padded_shape
+        rows_p, cols_p = dsr.dem_window_shape       # the tensors' own shape: sx / sy are window origins
         dsr._lib.msr_extract_patches(dsr._h, dsr.img_padded.data_ptr(), dsr.dem_padded.data_ptr(), rows_p, cols_p,
                                      st0["sx"].data_ptr(), st0["sy"].data_ptr(), st0["mm_sel"].data_ptr(), B,
                                      real.data_ptr(), torch.cuda.current_stream().cuda_stream)
@@ -275,7 +291,9 @@ def main():
             "generator_only_tiles512_per_s_rank0": gen_only, "generator_only_on_noise_tiles512_per_s_rank0": gen_only_noise,
             "end_to_end_over_generator_only": (calls * B * (S / 512.0) ** 2 / t_tiles / gen_only) if gen_only else None,
             "good_fraction_of_rank0_rows": good_fraction, "gathered": bool(args.gather and world > 1),
-            "canvas": list(dsr.dem_padded_shape), "shard": [shard_rank, shard_world], "tiles_this_rank": len(mine),
+            "canvas": list(dsr.dem_padded_shape), "crop_inputs": bool(args.crop_inputs), "input_rows": rows_in,
+            "canvas_window": list(dsr.dem_window_shape), "canvas_bytes": canvas_bytes,
+            "shard": [shard_rank, shard_world], "tiles_this_rank": len(mine),
             "tiles_processed_this_rank": len(todo),
             "setup_seconds_rank0": t_setup, "precision": args.precision, "pipeline": args.pipeline,
             "device_mem_gib_torch_peak": torch.cuda.max_memory_allocated() / 2 ** 30,
