@@ -229,6 +229,24 @@ int msr_resize_area(msr_handle* h, const float* src_dev, int32_t rows, int32_t c
  * A = -0.75, pixel-centre mapping, replicated border, float32; dst [dst_rows, dst_cols]. */
 int msr_resize_cubic(msr_handle* h, const float* src_dev, int32_t rows, int32_t cols, float* dst_dev,
                      int32_t dst_rows, int32_t dst_cols, void* stream);
+/* The same two resamplers on ROW WINDOWS, for a process that holds only some rows of a raster (a rank of a sharded run:
+ * moonsuperresolution_amd/preprocess.py::preprocess_rows).  src_dev holds rows [src_row0, src_row0 + src_rows) of a source of
+ * full_rows (full_src_rows) x cols; dst_dev receives rows [dst_row0, dst_row0 + dst_rows) of the whole-raster result, all
+ * dst_cols columns, and holds the bits msr_resize_area / msr_resize_cubic write to those rows: block geometry, partial edge
+ * blocks, the cubic's scale (full_src_rows / full_dst_rows) and its border clamp come from the full sizes, and only the final
+ * source row index is rebased by src_row0.  A window that lacks a source row one of the destination rows reads is
+ * MSR_ERR_INVALID (the message names the rows) before anything is launched.
+ * flags fuse the no-data marking of preprocess (process_full_tiles.py:231,233,237,242) into the pass:
+ *   MSR_RESIZE_NODATA_TO_NAN   a source value <= no_value is read as NaN
+ *   MSR_RESIZE_NAN_TO_NODATA   a NaN result is stored as no_value */
+#define MSR_RESIZE_NODATA_TO_NAN 1
+#define MSR_RESIZE_NAN_TO_NODATA 2
+int msr_resize_area_rows(msr_handle* h, const float* src_dev, int32_t src_row0, int32_t src_rows, int32_t full_rows,
+                         int32_t cols, int32_t factor, float* dst_dev, int32_t dst_row0, int32_t dst_rows, int32_t dst_cols,
+                         float no_value, int32_t flags, void* stream);
+int msr_resize_cubic_rows(msr_handle* h, const float* src_dev, int32_t src_row0, int32_t src_rows, int32_t full_src_rows,
+                          int32_t cols, float* dst_dev, int32_t dst_row0, int32_t dst_rows, int32_t full_dst_rows,
+                          int32_t dst_cols, float no_value, int32_t flags, void* stream);
 
 /* TIFF 6.0 LZW (compression 5) of HOST buffers, for the GeoTIFF reader / writer (moonsuperresolution_amd/geotiff.py;
  * the reference reads and writes LZW GeoTIFFs through GDAL: process_full_tiles.py:158-182, 481-531).

@@ -451,8 +451,20 @@ hipError_t launch_stitch_tile(const float* pred, const int* key, const float* dm
 hipError_t launch_halo_merge(const float* wa, const float* ma, const float* sa, const float* wb, const float* mb,
                              const float* sb, long n, float no_value, float* mean, float* stdv, uint8_t* good,
                              hipStream_t s);
-hipError_t launch_resize_area(const float* src, int h, int w, float* dst, int dh, int dw, int factor, hipStream_t s);
-hipError_t launch_resize_cubic(const float* src, int h, int w, float* dst, int dh, int dw, hipStream_t s);
+// Row windows of the two resamplers: src = rows [src_row0, src_row0 + src_rows) of a source of src_full rows, dst = rows
+// [dst_row0, dst_row0 + dst_rows) of the result (dst_full rows; the area resize derives them from the factor and ignores it).
+struct RowWindow {
+    int src_row0, src_rows, src_full;
+    int dst_row0, dst_rows, dst_full;
+};
+// Source rows [*lo, *hi) of the FULL raster that the window's destination rows read (empty: *hi == *lo).
+void resize_area_needs(const RowWindow& win, int factor, long* lo, long* hi);
+void resize_cubic_needs(const RowWindow& win, long* lo, long* hi);
+// Both return hipErrorInvalidValue, before any launch, when the source window lacks one of those rows.  flags: MSR_RESIZE_*.
+hipError_t launch_resize_area(const float* src, const RowWindow& win, int w, float* dst, int dw, int factor,
+                              float no_value, int flags, hipStream_t s);
+hipError_t launch_resize_cubic(const float* src, const RowWindow& win, int w, float* dst, int dw, float no_value,
+                               int flags, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
 // Activation-range scan (range_scan.hip): one launch over a device table of narrow activation images

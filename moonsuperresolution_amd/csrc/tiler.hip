@@ -1,7 +1,10 @@
 // Tiler / stitcher kernels: the NumPy half of the reference's driver (process_full_tiles.py) on the GPU.
 // Compiled with -ffp-contract=off: every float op below mirrors one NumPy op of the reference, evaluated in
 // the same type (float32 or float64) and the same order, so results are bit-exact with the CPU path.
+#include "../../include/moonsr.h"   // MSR_RESIZE_* flags
 #include "kernels.h"
+
+#include <algorithm>
 
 namespace msr {
 
@@ -323,38 +326,82 @@ hipError_t launch_halo_merge(const float* wa, const float* ma, const float* sa, 
 // twice, then INTER_CUBIC back to full size).  One thread per destination pixel, float32 operation order of
 // oracle/preprocess_ref.py (which restates OpenCV's published algorithm; this file is compiled with
 // -ffp-contract=off), so the two agree bit for bit.  HBM-bound: the full-resolution raster is read / written once.
+//
+// Both work on ROW WINDOWS (RowWindow): src holds rows [src_row0, src_row0 + src_rows) of the full source raster and dst
+// receives rows [dst_row0, dst_row0 + dst_rows) of the full result; all columns on both sides.  Everything that decides a
+// pixel's value — block geometry, partial blocks, the cubic's scale and border clamp — is computed from the FULL sizes, so a
+// window holds the bits of the same rows of the whole-raster result; only the final source row index is rebased by src_row0.
+// The launchers refuse a window that lacks a needed source row (resize_*_needs states which rows those are) before any
+// launch.  MSR_RESIZE_NODATA_TO_NAN / MSR_RESIZE_NAN_TO_NODATA fuse preprocess()'s no-data marking (v <= no_value -> NaN on
+// load, NaN -> no_value on store) into the pass: the arithmetic in between is unchanged.
 // ------------------------------------------------------------------------------------------------
-__global__ void __launch_bounds__(256) resize_area_kernel(const float* __restrict__ src, int h, int w,
-                                                          float* __restrict__ dst, int dh, int dw, int f) {
+__device__ __forceinline__ float nodata_load(float v, float no_value, int flags) {
+    return ((flags & MSR_RESIZE_NODATA_TO_NAN) && v <= no_value) ? __builtin_nanf("") : v;
+}
+
+__device__ __forceinline__ float nodata_store(float v, float no_value, int flags) {
+    return ((flags & MSR_RESIZE_NAN_TO_NODATA) && v != v) ? no_value : v;
+}
+
+// vec4: f == 4, w % 4 == 0 and src 16-byte aligned (the launcher decides), so a full block's row is one float4
+__global__ void __launch_bounds__(256) resize_area_kernel(const float* __restrict__ src, RowWindow win, int w,
+                                                          float* __restrict__ dst, int dw, int f, float no_value,
+                                                          int flags, int vec4) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (long)dh * dw) return;
-    const int dx = (int)(i % dw), dy = (int)(i / dw);
+    if (i >= (long)win.dst_rows * dw) return;
+    const int h = win.src_full;
+    const int dx = (int)(i % dw), dy = win.dst_row0 + (int)(i / dw);
     const int x0 = dx * f, y0 = dy * f;
     if (y0 >= h || x0 >= w) { dst[i] = 0.f; return; }
+    const float* base = src + ((long)y0 - win.src_row0) * w;      // y0 .. min(y0 + f, h) - 1 lie in the window (launcher)
+    float out;
     if (y0 + f <= h && x0 + f <= w) {
         // full block: rows outer, four columns at a time (sum += S[k] + S[k+1] + S[k+2] + S[k+3]), times 1/area
         float sum = 0.f;
-        for (int r = 0; r < f; ++r) {
-            const float* S = src + (size_t)(y0 + r) * w + x0;
-            int k = 0;
-            for (; k + 4 <= f; k += 4) sum = sum + (((S[k] + S[k + 1]) + S[k + 2]) + S[k + 3]);
-            for (; k < f; ++k) sum = sum + S[k];
+        if (vec4) {
+#pragma unroll
+            for (int r = 0; r < 4; ++r) {
+                const float4 q = *reinterpret_cast<const float4*>(base + (size_t)r * w + x0);
+                sum = sum + (((nodata_load(q.x, no_value, flags) + nodata_load(q.y, no_value, flags)) +
+                              nodata_load(q.z, no_value, flags)) + nodata_load(q.w, no_value, flags));
+            }
+        } else {
+            for (int r = 0; r < f; ++r) {
+                const float* S = base + (size_t)r * w + x0;
+                int k = 0;
+                for (; k + 4 <= f; k += 4)
+                    sum = sum + (((nodata_load(S[k], no_value, flags) + nodata_load(S[k + 1], no_value, flags)) +
+                                  nodata_load(S[k + 2], no_value, flags)) + nodata_load(S[k + 3], no_value, flags));
+                for (; k < f; ++k) sum = sum + nodata_load(S[k], no_value, flags);
+            }
         }
-        dst[i] = sum * (1.0f / (float)(f * f));
+        out = sum * (1.0f / (float)(f * f));
     } else {
         float sum = 0.f;
         int n = 0;
-        for (int yy = y0; yy < min(y0 + f, h); ++yy)
-            for (int xx = x0; xx < min(x0 + f, w); ++xx) { sum = sum + src[(size_t)yy * w + xx]; ++n; }
-        dst[i] = sum / (float)n;
+        for (int yy = 0; yy < min(f, h - y0); ++yy)
+            for (int xx = x0; xx < min(x0 + f, w); ++xx) {
+                sum = sum + nodata_load(base[(size_t)yy * w + xx], no_value, flags);
+                ++n;
+            }
+        out = sum / (float)n;
     }
+    dst[i] = nodata_store(out, no_value, flags);
+}
+
+// First source index of the cubic's four taps (s - 1 .. s + 2, before the border clamp) for destination index d: OpenCV's
+// float fx = (float)((dx + 0.5) * scale - 0.5), floor.  Host and device: the launcher's window check uses the kernel's own
+// expression (this file is compiled with -ffp-contract=off on both sides).
+__host__ __device__ __forceinline__ int cubic_first_tap(int d, double scale, float* t) {
+    const float f = (float)(((double)d + 0.5) * scale - 0.5);
+    const float fl = floorf(f);
+    if (t) *t = f - fl;
+    return (int)fl - 1;
 }
 
 __device__ __forceinline__ void cubic_axis(int d, double scale, int n_src, int (&idx)[4], float (&c)[4]) {
-    const float f = (float)(((double)d + 0.5) * scale - 0.5);
-    const float fl = floorf(f);
-    const int s = (int)fl;
-    const float t = f - fl;
+    float t;
+    const int s0 = cubic_first_tap(d, scale, &t);
     const float A = -0.75f;
     c[0] = ((A * (t + 1.f) - 5.f * A) * (t + 1.f) + 8.f * A) * (t + 1.f) - 4.f * A;
     c[1] = ((A + 2.f) * t - (A + 3.f)) * t * t + 1.f;
@@ -362,38 +409,68 @@ __device__ __forceinline__ void cubic_axis(int d, double scale, int n_src, int (
     c[2] = ((A + 2.f) * u - (A + 3.f)) * u * u + 1.f;
     c[3] = 1.f - c[0] - c[1] - c[2];
 #pragma unroll
-    for (int k = 0; k < 4; ++k) idx[k] = min(max(s - 1 + k, 0), n_src - 1);
+    for (int k = 0; k < 4; ++k) idx[k] = min(max(s0 + k, 0), n_src - 1);
 }
 
-__global__ void __launch_bounds__(256) resize_cubic_kernel(const float* __restrict__ src, int h, int w,
-                                                           float* __restrict__ dst, int dh, int dw) {
+__global__ void __launch_bounds__(256) resize_cubic_kernel(const float* __restrict__ src, RowWindow win, int w,
+                                                           float* __restrict__ dst, int dw, float no_value, int flags) {
     const long i = (long)blockIdx.x * 256 + threadIdx.x;
-    if (i >= (long)dh * dw) return;
-    const int dx = (int)(i % dw), dy = (int)(i / dw);
+    if (i >= (long)win.dst_rows * dw) return;
+    const int dx = (int)(i % dw), dy = win.dst_row0 + (int)(i / dw);
     int xi[4], yi[4];
     float a[4], b[4];
     cubic_axis(dx, (double)w / (double)dw, w, xi, a);
-    cubic_axis(dy, (double)h / (double)dh, h, yi, b);
+    cubic_axis(dy, (double)win.src_full / (double)win.dst_full, win.src_full, yi, b);
     float rows[4];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
-        const float* S = src + (size_t)yi[k] * w;
-        rows[k] = ((S[xi[0]] * a[0] + S[xi[1]] * a[1]) + S[xi[2]] * a[2]) + S[xi[3]] * a[3];   // horizontal pass
+        // clamped to the full extent above, rebased here; the second clamp never moves an index the launcher accepted
+        const int y = min(max(yi[k] - win.src_row0, 0), win.src_rows - 1);
+        const float* S = src + (size_t)y * w;
+        rows[k] = ((nodata_load(S[xi[0]], no_value, flags) * a[0] + nodata_load(S[xi[1]], no_value, flags) * a[1]) +
+                   nodata_load(S[xi[2]], no_value, flags) * a[2]) + nodata_load(S[xi[3]], no_value, flags) * a[3];   // horizontal
     }
-    dst[i] = ((rows[0] * b[0] + rows[1] * b[1]) + rows[2] * b[2]) + rows[3] * b[3];            // vertical pass
+    const float out = ((rows[0] * b[0] + rows[1] * b[1]) + rows[2] * b[2]) + rows[3] * b[3];    // vertical pass
+    dst[i] = nodata_store(out, no_value, flags);
 }
 
-hipError_t launch_resize_area(const float* src, int h, int w, float* dst, int dh, int dw, int factor, hipStream_t s) {
-    const long n = (long)dh * dw;
-    if (n <= 0 || factor < 1) return hipErrorInvalidValue;
-    resize_area_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(src, h, w, dst, dh, dw, factor);
+void resize_area_needs(const RowWindow& win, int factor, long* lo, long* hi) {
+    *lo = (long)win.dst_row0 * factor;
+    *hi = std::min((long)(win.dst_row0 + (long)win.dst_rows) * factor, (long)win.src_full);
+    if (*hi < *lo) *hi = *lo;                    // destination rows past the source: they are written as zeros, nothing is read
+}
+
+void resize_cubic_needs(const RowWindow& win, long* lo, long* hi) {
+    const double scale = (double)win.src_full / (double)win.dst_full;
+    const long top = win.src_full - 1;
+    // the tap index is monotone in the destination row: the first and the last row bound every row between them
+    *lo = std::min(std::max((long)cubic_first_tap(win.dst_row0, scale, nullptr), 0L), top);
+    *hi = std::min(std::max((long)cubic_first_tap(win.dst_row0 + win.dst_rows - 1, scale, nullptr) + 3, 0L), top) + 1;
+}
+
+static bool window_holds(const RowWindow& win, long lo, long hi) {
+    return hi <= lo || ((long)win.src_row0 <= lo && hi <= (long)win.src_row0 + win.src_rows);
+}
+
+hipError_t launch_resize_area(const float* src, const RowWindow& win, int w, float* dst, int dw, int factor,
+                              float no_value, int flags, hipStream_t s) {
+    const long n = (long)win.dst_rows * dw;
+    long lo, hi;
+    resize_area_needs(win, factor, &lo, &hi);
+    if (n <= 0 || factor < 1 || w < 1 || win.src_rows < 1 || !window_holds(win, lo, hi)) return hipErrorInvalidValue;
+    const int vec4 = factor == 4 && w % 4 == 0 && (reinterpret_cast<uintptr_t>(src) & 15) == 0;
+    resize_area_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(src, win, w, dst, dw, factor, no_value, flags, vec4);
     return hipGetLastError();
 }
 
-hipError_t launch_resize_cubic(const float* src, int h, int w, float* dst, int dh, int dw, hipStream_t s) {
-    const long n = (long)dh * dw;
-    if (n <= 0 || h < 1 || w < 1) return hipErrorInvalidValue;
-    resize_cubic_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(src, h, w, dst, dh, dw);
+hipError_t launch_resize_cubic(const float* src, const RowWindow& win, int w, float* dst, int dw, float no_value,
+                               int flags, hipStream_t s) {
+    const long n = (long)win.dst_rows * dw;
+    if (n <= 0 || w < 1 || win.src_rows < 1 || win.src_full < 1 || win.dst_full < 1) return hipErrorInvalidValue;
+    long lo, hi;
+    resize_cubic_needs(win, &lo, &hi);
+    if (!window_holds(win, lo, hi)) return hipErrorInvalidValue;
+    resize_cubic_kernel<<<(unsigned)((n + 255) / 256), 256, 0, s>>>(src, win, w, dst, dw, no_value, flags);
     return hipGetLastError();
 }
 

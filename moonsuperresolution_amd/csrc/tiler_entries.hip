@@ -41,14 +41,53 @@ int msr_compact_patches(msr_handle* h, const uint8_t* valid, const int32_t* ox, 
     return MSR_OK;
 }
 
+int msr_resize_area_rows(msr_handle* h, const float* src, int32_t src_row0, int32_t src_rows, int32_t full_rows,
+                         int32_t cols, int32_t factor, float* dst, int32_t dst_row0, int32_t dst_rows, int32_t dst_cols,
+                         float no_value, int32_t flags, void* stream) {
+    if (!h) return MSR_ERR_INVALID;
+    if (!src || !dst || src_row0 < 0 || src_rows <= 0 || full_rows <= 0 || src_rows > full_rows - src_row0 || cols <= 0 ||
+        factor < 1 || dst_row0 < 0 || dst_rows <= 0 || dst_cols <= 0 ||
+        (flags & ~(MSR_RESIZE_NODATA_TO_NAN | MSR_RESIZE_NAN_TO_NODATA)))
+        return fail(h, MSR_ERR_INVALID, "msr_resize_area_rows: bad argument");
+    if ((int64_t)dst_row0 + dst_rows > INT32_MAX / factor)
+        return fail(h, MSR_ERR_INVALID, "msr_resize_area_rows: destination rows x factor exceed int32");
+    const RowWindow win{src_row0, src_rows, full_rows, dst_row0, dst_rows, 0};
+    long lo, hi;
+    resize_area_needs(win, factor, &lo, &hi);
+    if (hi > lo && (lo < src_row0 || hi > (long)src_row0 + src_rows))
+        return fail(h, MSR_ERR_INVALID, "msr_resize_area_rows: destination rows [%d, %d) read source rows [%ld, %ld), the "
+                    "window holds [%d, %d)", dst_row0, dst_row0 + dst_rows, lo, hi, src_row0, src_row0 + src_rows);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, launch_resize_area(src, win, cols, dst, dst_cols, factor, no_value, flags, (hipStream_t)stream));
+    return MSR_OK;
+}
+
+int msr_resize_cubic_rows(msr_handle* h, const float* src, int32_t src_row0, int32_t src_rows, int32_t full_src_rows,
+                          int32_t cols, float* dst, int32_t dst_row0, int32_t dst_rows, int32_t full_dst_rows,
+                          int32_t dst_cols, float no_value, int32_t flags, void* stream) {
+    if (!h) return MSR_ERR_INVALID;
+    if (!src || !dst || src_row0 < 0 || src_rows <= 0 || full_src_rows <= 0 || src_rows > full_src_rows - src_row0 ||
+        cols <= 0 || dst_row0 < 0 || dst_rows <= 0 || full_dst_rows <= 0 || dst_rows > full_dst_rows - dst_row0 ||
+        dst_cols <= 0 || (flags & ~(MSR_RESIZE_NODATA_TO_NAN | MSR_RESIZE_NAN_TO_NODATA)))
+        return fail(h, MSR_ERR_INVALID, "msr_resize_cubic_rows: bad argument");
+    const RowWindow win{src_row0, src_rows, full_src_rows, dst_row0, dst_rows, full_dst_rows};
+    long lo, hi;
+    resize_cubic_needs(win, &lo, &hi);
+    if (lo < src_row0 || hi > (long)src_row0 + src_rows)
+        return fail(h, MSR_ERR_INVALID, "msr_resize_cubic_rows: destination rows [%d, %d) read source rows [%ld, %ld), the "
+                    "window holds [%d, %d)", dst_row0, dst_row0 + dst_rows, lo, hi, src_row0, src_row0 + src_rows);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, launch_resize_cubic(src, win, cols, dst, dst_cols, no_value, flags, (hipStream_t)stream));
+    return MSR_OK;
+}
+
+// The whole-raster forms: the window is the raster.
 int msr_resize_area(msr_handle* h, const float* src, int32_t rows, int32_t cols, int32_t factor, float* dst,
                     int32_t dst_rows, int32_t dst_cols, void* stream) {
     if (!h) return MSR_ERR_INVALID;
     if (!src || !dst || rows <= 0 || cols <= 0 || factor < 1 || dst_rows <= 0 || dst_cols <= 0)
         return fail(h, MSR_ERR_INVALID, "msr_resize_area: bad argument");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, launch_resize_area(src, rows, cols, dst, dst_rows, dst_cols, factor, (hipStream_t)stream));
-    return MSR_OK;
+    return msr_resize_area_rows(h, src, 0, rows, rows, cols, factor, dst, 0, dst_rows, dst_cols, 0.f, 0, stream);
 }
 
 int msr_resize_cubic(msr_handle* h, const float* src, int32_t rows, int32_t cols, float* dst, int32_t dst_rows,
@@ -56,9 +95,7 @@ int msr_resize_cubic(msr_handle* h, const float* src, int32_t rows, int32_t cols
     if (!h) return MSR_ERR_INVALID;
     if (!src || !dst || rows <= 0 || cols <= 0 || dst_rows <= 0 || dst_cols <= 0)
         return fail(h, MSR_ERR_INVALID, "msr_resize_cubic: bad argument");
-    HIPCHK(h, hipSetDevice(h->cfg.device));
-    HIPCHK(h, launch_resize_cubic(src, rows, cols, dst, dst_rows, dst_cols, (hipStream_t)stream));
-    return MSR_OK;
+    return msr_resize_cubic_rows(h, src, 0, rows, rows, cols, dst, 0, dst_rows, dst_rows, dst_cols, 0.f, 0, stream);
 }
 
 int msr_set_blend_window(msr_handle* h, const double* host_window, int32_t side) {

@@ -214,8 +214,10 @@ def halo_zone_rows(ys: Sequence[int], image_size: int, world: int):
 # Row windows: which raster rows a rank has to read, pad and upload
 # ----------------------------------------------------------------------------------------------------------------
 def input_rows(shape: Tuple[int, int], image_size: int, stride: int, tile_size: int, rank: int, world: int,
-               mode: str) -> Tuple[int, int]:
-    """Raster rows [r0, r1) (un-padded coordinates) that the patches of ``rank`` can touch.
+               mode: str, preprocess: bool = False) -> Tuple[int, int]:
+    """Raster rows [r0, r1) (un-padded coordinates) that the patches of ``rank`` can touch.  With ``preprocess``: the rows
+    of the input DEM from which those rows of the synthesised DEM are computed (preprocess.window_plan(...)["dem"]: a band
+    under 1024 rows wider a side).
 
     mode "tiles": the patches of the tiles ``shard_tile_rows`` gives the rank; mode "halo": the patch rows
     ``halo_zone_rows`` gives it (the boundary zones it sends and merges are accumulators of those same patches: they
@@ -226,6 +228,10 @@ def input_rows(shape: Tuple[int, int], image_size: int, stride: int, tile_size: 
         raise ValueError(f"mode must be 'tiles' or 'halo', got {mode!r}")
     if not 0 <= rank < world:
         raise ValueError("rank out of range")
+    if preprocess:
+        from .preprocess import window_plan
+        r0, r1 = input_rows(shape, image_size, stride, tile_size, rank, world, mode)
+        return window_plan(shape, (r0, r1))["dem"] if r1 > r0 else (0, 0)
     H = int(shape[0])
     S, s, T = image_size, stride, tile_size
     if world == 1:

@@ -292,14 +292,15 @@ class HaloShardedSuperResolution(DEMSuperResolution):
         parts = [torch.cat([sl[0][k] for sl in slabs], dim=0) for k in range(3)]
         return tuple(p[halo:halo + h, halo:halo + w].cpu().numpy() for p in parts)
 
-    def _process_files_sharded(self, preprocess: bool, rank: int, world: int, mode: str, gather: bool):
+    def _process_files_sharded(self, preprocess: bool, rank: int, world: int, mode: str, gather: bool,
+                               swap_dsize: bool = True):
         """processFiles(mode="halo"): this rank reads only the rows its patch rows touch, runs its share (processMapHalo:
         the zone exchange needs an initialised process group when world > 1) and, with ``gather``, all-gathers the slabs;
         without it the rows other ranks own stay zero."""
         if mode != "halo":
-            return super()._process_files_sharded(preprocess, rank, world, mode, gather)
+            return super()._process_files_sharded(preprocess, rank, world, mode, gather, swap_dsize)
         from .distributed import all_gather_var_rows
-        self._load_rank_rows(preprocess, rank, world, mode)
+        self._load_rank_rows(preprocess, rank, world, mode, swap_dsize)
         (m, sd, g), (own_lo, own_hi) = self.processMapHalo(rank=rank, world=world)
         hp = self.dem_padded_shape[0]
         if world > 1 and gather:

@@ -2,10 +2,16 @@
 
 ``preprocess`` = nodata in-filling of the ortho-image (result stored, never used — reference quirk), then the
 synthesis of the low-resolution DEM: x1/4 INTER_AREA -> in-filling -> x1/4 INTER_AREA -> INTER_CUBIC back to full
-size.  The two resamplers run on the GPU through the C ABI (``msr_resize_area`` / ``msr_resize_cubic``; the
-full-resolution raster is read and written once); the in-filling stays on the host exactly like the reference: the
-same ``scipy.interpolate.griddata(method="cubic")`` call on each tile that has holes, with ``scipy.ndimage.label``
-(8-connected) in place of ``cv2.connectedComponents``.
+size.  The two resamplers run on the GPU through the C ABI (``msr_resize_area_rows`` / ``msr_resize_cubic_rows``, which
+also do the no-data <-> NaN marking between the steps; the full-resolution raster is read and written once); the
+in-filling stays on the host exactly like the reference: the same ``scipy.interpolate.griddata(method="cubic")`` call on
+each tile that has holes, with ``scipy.ndimage.label`` (8-connected) in place of ``cv2.connectedComponents``.
+
+Pre-processing is local in rows: the cubic reads 4 rows of the x1/16 grid, each area step 4 source rows, and the in-filling
+works on 256-row tiles of the x1/4 grid.  ``window_plan`` states which rows of each grid a range of output rows depends on,
+and ``preprocess_rows`` computes exactly those from a row window of the input DEM — bit-identical to the same rows of the
+whole-raster result, which goes through the same code with the window [0, H).  A rank of a sharded run pre-processes its
+own band (``DEMSuperResolution.preprocess(rows=)``, ``distributed.input_rows(preprocess=True)``).
 
 OpenCV is not available here and the reference holds no fixture of ``cv2.resize`` output, so the resamplers follow
 OpenCV's published algorithm (see oracle/preprocess_ref.py, against which the kernels are bit-exact): parity with a
@@ -14,7 +20,7 @@ real OpenCV build is unpinned.
 from __future__ import annotations
 
 import ctypes as C
-from typing import Tuple
+from typing import Dict, Tuple
 
 import numpy as np
 import torch
@@ -92,28 +98,153 @@ def fillNan(image: np.ndarray, no_value: float, tile_size: int = 1024, border: i
     return out
 
 
+FILL_TILE, FILL_BORDER, FILL_AREA = 256, 32, 24     # fillNan's arguments on the x1/4 grid (process_full_tiles.py:236)
+RESIZE_NODATA_TO_NAN, RESIZE_NAN_TO_NODATA = 1, 2    # MSR_RESIZE_* of include/moonsr.h
+
+
+def _cubic_tap_rows(d0: int, d1: int, n_src: int, n_dst: int) -> Tuple[int, int]:
+    """Source rows [a, b) the cubic taps of destination rows d0 .. d1 - 1 touch, by the kernel's own expression
+    (csrc/tiler.hip::cubic_first_tap): s = floor(float32((d + 0.5) * (n_src / n_dst) - 0.5)), taps s - 1 .. s + 2 clamped to
+    the source.  s is monotone in d, so the first and the last row bound the rest."""
+    scale = n_src / n_dst
+
+    def s(d):
+        return int(np.floor(np.float32((d + 0.5) * scale - 0.5)))
+    return min(max(s(d0) - 1, 0), n_src - 1), min(max(s(d1 - 1) + 2, 0), n_src - 1) + 1
+
+
+def _plan_from_d16(shape: Tuple[int, int], a16: int, b16: int) -> Dict[str, object]:
+    """The rows of the in-filled x1/4 grid, of the x1/4 grid and of the input that rows [a16, b16) of the x1/16 grid depend
+    on, and the in-fill tiles to run (window_plan)."""
+    H = int(shape[0])
+    h4 = _cv_round(H / 4)
+    fill = (4 * a16, min(4 * b16, h4))
+    lo, hi = fill
+    tiles = []
+    for top in range(0, h4, FILL_TILE - 2 * FILL_BORDER):
+        w0, w1 = top + FILL_BORDER, min(top + FILL_TILE - FILL_BORDER, h4 - FILL_BORDER)     # the rows the tile writes
+        if w1 > w0 and w0 < fill[1] and w1 > fill[0]:
+            tiles.append(top)
+            lo, hi = min(lo, top), max(hi, min(top + FILL_TILE, h4))
+    return {"d16": (a16, b16), "fill": fill, "d4": (lo, hi), "dem": (min(4 * lo, H), min(4 * hi, H)), "tiles": tiles}
+
+
+def window_plan(shape: Tuple[int, int], out_rows: Tuple[int, int]) -> Dict[str, object]:
+    """Row ranges [first, end) that rows ``out_rows`` = [r0, r1) of the synthesised DEM of a raster of ``shape`` = (H, W)
+    depend on (``preprocess(..., swap_dsize=False)``; with h4 = rint(H / 4), h16 = rint(h4 / 4), round-half-even):
+
+      d16    rows of the x1/16 grid the cubic taps of output rows r0 .. r1 - 1 touch
+      fill   rows [4 a16, min(4 b16, h4)) of the in-filled x1/4 grid: what the second area step reads for them
+      d4     rows of the x1/4 grid: ``fill`` and the full row extent [top, min(top + 256, h4)) of every in-fill tile (top in
+             range(0, h4, 192)) whose written rows [top + 32, min(top + 224, h4 - 32)) are not empty and meet ``fill``; the
+             32 rows at either end of the grid that no tile writes pass through un-filled, as in fillNan
+      dem    rows [min(4 A4, H), min(4 B4, H)) of the input DEM: what the first area step reads for d4 = [A4, B4)
+      tiles  the tops of those tiles
+
+    Pure arithmetic; needs no GPU.  ``dem`` reaches at most 223 rows of the x1/4 grid (a tile's extent beyond a row it
+    writes) plus 3 rows of the x1/16 grid (the cubic's taps) beyond [r0, r1): under 1024 input rows a side."""
+    H = int(shape[0])
+    r0, r1 = int(out_rows[0]), int(out_rows[1])
+    if not 0 <= r0 < r1 <= H:
+        raise ValueError(f"rows [{r0}, {r1}) are not rows of a raster of {H}")
+    h16 = _cv_round(_cv_round(H / 4) / 4)
+    if h16 < 1:
+        raise ValueError(f"a raster of {H} rows has no x1/16 grid")
+    return _plan_from_d16(shape, *_cubic_tap_rows(r0, r1, h16, H))
+
+
+def _area_rows(lib, handle, src: torch.Tensor, src_row0: int, full_rows: int, dst_rows: Tuple[int, int], no_value: float,
+               flags: int) -> torch.Tensor:
+    """Rows ``dst_rows`` of the x1/4 INTER_AREA of a raster of ``full_rows`` of which ``src`` holds the rows from
+    ``src_row0`` (msr_resize_area_rows)."""
+    n, w = src.shape
+    dst = torch.empty((dst_rows[1] - dst_rows[0], _cv_round(w / 4)), dtype=torch.float32, device=src.device)
+    rc = lib.msr_resize_area_rows(handle, src.data_ptr(), src_row0, n, full_rows, w, 4, dst.data_ptr(), dst_rows[0],
+                                  dst.shape[0], dst.shape[1], no_value, flags,
+                                  torch.cuda.current_stream(src.device).cuda_stream)
+    _lib.raise_for(lib, handle, rc, "msr_resize_area_rows")
+    return dst
+
+
+def _fill_rows(band: np.ndarray, row0: int, h4: int, tiles, no_value: float) -> np.ndarray:
+    """fillNan(tile_size=256, border=32, max_fill_area=24) on rows [row0, row0 + len(band)) of an x1/4 grid of ``h4`` rows,
+    for the tiles at the row tops ``tiles`` only (window_plan), all columns.  Each tile is cut at the true ``h4`` and at the
+    grid's width, so it is the tile fillNan cuts from the whole grid and takes the same values."""
+    w = band.shape[1]
+    out = band.copy()
+    step = FILL_TILE - 2 * FILL_BORDER
+    for top in tiles:
+        bottom = min(top + FILL_TILE - FILL_BORDER, h4 - FILL_BORDER)
+        for left in range(0, w, step):
+            right = min(left + FILL_TILE - FILL_BORDER, w - FILL_BORDER)
+            if right <= left + FILL_BORDER:
+                continue
+            tile = interpolateMissingValues(band[top - row0:min(top + FILL_TILE, h4) - row0, left:left + FILL_TILE].copy(),
+                                            no_value, max_fill_area=FILL_AREA)
+            out[top + FILL_BORDER - row0:bottom - row0, left + FILL_BORDER:right] = tile[FILL_BORDER:-FILL_BORDER,
+                                                                                         FILL_BORDER:-FILL_BORDER]
+    return out
+
+
+def _lowres_rows(lib, handle, device, dem_window: np.ndarray, row0: int, shape: Tuple[int, int], plan, no_value: float
+                 ) -> torch.Tensor:
+    """Rows plan["d16"] of the x1/16 grid (device tensor, no-data as NaN) from a row window of the input DEM that holds
+    plan["dem"]: area on the d4 band, host in-filling of the plan's tiles, area on the in-filled rows."""
+    H = int(shape[0])
+    h4 = _cv_round(H / 4)
+    (m0, m1), (q0, q1), (f0, f1) = plan["dem"], plan["d4"], plan["fill"]
+    if m0 < row0 or m1 > row0 + dem_window.shape[0]:
+        raise ValueError(f"the row window [{row0}, {row0 + dem_window.shape[0]}) lacks rows of [{m0}, {m1}), which the "
+                         f"pre-processing of x1/16-grid rows {plan['d16']} reads")
+    d = torch.from_numpy(np.ascontiguousarray(dem_window[m0 - row0:m1 - row0], dtype=np.float32)).to(device)
+    d4 = _area_rows(lib, handle, d, m0, H, (q0, q1), no_value, RESIZE_NODATA_TO_NAN | RESIZE_NAN_TO_NODATA)
+    del d
+    filled = _fill_rows(d4.cpu().numpy(), q0, h4, plan["tiles"], no_value)
+    d4 = torch.from_numpy(np.ascontiguousarray(filled[f0 - q0:f1 - q0])).to(device)
+    return _area_rows(lib, handle, d4, f0, h4, plan["d16"], no_value, RESIZE_NODATA_TO_NAN)
+
+
+def _cubic_rows(lib, handle, d16: torch.Tensor, a16: int, h16: int, dst_rows: Tuple[int, int], dst_shape: Tuple[int, int],
+                no_value: float) -> np.ndarray:
+    """Rows ``dst_rows`` of the INTER_CUBIC resize to ``dst_shape`` = (rows, cols) of an x1/16 grid of ``h16`` rows of which
+    ``d16`` holds the rows from ``a16``; NaN leaves as no_value.  Host float32."""
+    dst = torch.empty((dst_rows[1] - dst_rows[0], dst_shape[1]), dtype=torch.float32, device=d16.device)
+    rc = lib.msr_resize_cubic_rows(handle, d16.data_ptr(), a16, d16.shape[0], h16, d16.shape[1], dst.data_ptr(), dst_rows[0],
+                                   dst.shape[0], dst_shape[0], dst_shape[1], no_value, RESIZE_NAN_TO_NODATA,
+                                   torch.cuda.current_stream(d16.device).cuda_stream)
+    _lib.raise_for(lib, handle, rc, "msr_resize_cubic_rows")
+    return dst.cpu().numpy()
+
+
+def preprocess_rows(lib, handle, device, dem_window: np.ndarray, row0: int, shape: Tuple[int, int],
+                    out_rows: Tuple[int, int], no_value: float) -> np.ndarray:
+    """Rows ``out_rows`` of what ``preprocess(..., swap_dsize=False)[1]`` returns for the whole raster of ``shape``, bit for
+    bit, from ``dem_window`` = its rows [row0, row0 + len(dem_window)), which must hold window_plan(shape, out_rows)["dem"]
+    (ValueError otherwise).  Only the plan's d4, fill and d16 rows are computed.  Host float32."""
+    H, W = int(shape[0]), int(shape[1])
+    dem_window = np.asarray(dem_window, np.float32)
+    if dem_window.ndim != 2 or dem_window.shape[1] != W:
+        raise ValueError(f"the row window must be 2-D with the raster's {W} columns")
+    plan = window_plan(shape, out_rows)
+    with torch.cuda.device(device):
+        d16 = _lowres_rows(lib, handle, device, dem_window, int(row0), shape, plan, no_value)
+        return _cubic_rows(lib, handle, d16, plan["d16"][0], _cv_round(_cv_round(H / 4) / 4), out_rows, (H, W), no_value)
+
+
 def preprocess(lib, handle, device, img: np.ndarray, dem: np.ndarray, no_value: float,
                swap_dsize: bool = True) -> Tuple[np.ndarray, np.ndarray]:
     """process_full_tiles.py:226-244.  Returns (filled ortho, low-resolution DEM at full size), both host float32.
 
     ``swap_dsize=True`` reproduces :241, where ``self.dem_shape`` = (rows, cols) is handed to ``cv2.resize`` as
     (width, height): the result then has shape (cols, rows), so — like the reference — only square rasters survive
-    the later ``padInputs``.  ``swap_dsize=False`` resizes to (rows, cols) proper."""
+    the later ``padInputs``.  ``swap_dsize=False`` resizes to (rows, cols) proper: preprocess_rows with the window [0, H)."""
     img = np.asarray(img, np.float32)
     dem = np.asarray(dem, np.float32)
     image = fillNan(img, no_value, tile_size=1024, border=128, max_fill_area=8)
-    with torch.cuda.device(device):
-        d = torch.from_numpy(np.ascontiguousarray(dem)).to(device)
-        d = torch.where(d <= no_value, torch.full_like(d, float("nan")), d)      # keep OpenCV from averaging no_values
-        d4 = resize_area(lib, handle, d, 4)
-        del d
-        d4 = torch.where(torch.isnan(d4), torch.full_like(d4, no_value), d4)
-        h4 = fillNan(d4.cpu().numpy(), no_value, tile_size=256, border=32, max_fill_area=24)
-        d4 = torch.from_numpy(h4).to(device)
-        d4 = torch.where(d4 <= no_value, torch.full_like(d4, float("nan")), d4)
-        d16 = resize_area(lib, handle, d4, 4)
-        dsize = (dem.shape[0], dem.shape[1]) if swap_dsize else (dem.shape[1], dem.shape[0])
-        up = resize_cubic(lib, handle, d16, dsize)
-        up = torch.where(torch.isnan(up), torch.full_like(up, no_value), up)
-        out = up.cpu().numpy()
-    return image, out
+    H, W = dem.shape
+    if not swap_dsize:
+        return image, preprocess_rows(lib, handle, device, dem, 0, (H, W), (0, H), no_value)
+    h16 = _cv_round(_cv_round(H / 4) / 4)
+    with torch.cuda.device(device):      # every row of the x1/16 grid, then the cubic to W rows of H columns
+        d16 = _lowres_rows(lib, handle, device, dem, 0, (H, W), _plan_from_d16((H, W), 0, h16), no_value)
+        return image, _cubic_rows(lib, handle, d16, 0, h16, (0, W), (W, H), no_value)

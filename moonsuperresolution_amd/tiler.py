@@ -3,7 +3,8 @@
 Same names and argument meaning as the reference for the part of the class that is on the hot path
 (``DSRConfig``, ``padInputs``, ``generateTileList``, ``processTile``, ``rebuildTile``, ``rebuildMap``) and for the
 file boundary either side of it (``loadImages`` / ``saveGTiff`` on ``geotiff.py`` instead of GDAL).  Nodata
-in-filling and low-res-DEM synthesis live in preprocess.py (``DEMSuperResolution.preprocess``) — or feed
+in-filling and low-res-DEM synthesis live in preprocess.py (``DEMSuperResolution.preprocess``; with
+``rows=`` for the row window of a sharded rank, which ``processFiles(preprocess=True, mode=...)`` uses) — or feed
 pre-processed rasters, as files (``processFiles``) or as arrays (``setImages`` / ``processMap``).
 
 What moves to the GPU (libmoonsr_hip.so, csrc/tiler.hip):
@@ -224,7 +225,7 @@ class DEMSuperResolution:
                               getattr(self, "geo_meta", None), nodata=self.no_value, dtype=out_type, compress="lzw",
                               predictor=2)
 
-    def preprocess(self, swap_dsize: bool = True) -> None:
+    def preprocess(self, swap_dsize: bool = True, rows: Optional[Tuple[int, int]] = None) -> None:
         """process_full_tiles.py:226-244: in-fill the ortho (stored in ``self.image`` and, as in the reference, never
         used afterwards), then replace ``self.dem`` by the synthesised low-resolution DEM (x1/4 area, in-fill, x1/4
         area, cubic back to full size).  Resamplers on the GPU, in-filling with SciPy on the host (preprocess.py).
@@ -233,54 +234,90 @@ class DEMSuperResolution:
         raster ends with a transposed-shape DEM and fails in padInputs exactly as the reference does; pass False to
         resize to the raster's own shape.
 
-        Whole rasters only: in-filling and the two resamplers are whole-raster operations with the reference's quirks
-        (DESIGN.md section 7.3), so with a row window set (setImages(row0=, full_shape=), loadImages(rows=)) this raises
-        ValueError — pre-process the whole raster first and window the result."""
+        ``rows=(r0, r1)``: synthesise only those raster rows, from the rows held (the whole raster, or a row window:
+        setImages(row0=, full_shape=), loadImages(rows=)).  They must contain preprocess.window_plan(dem_shape, rows)["dem"]
+        and [r0, r1) itself; a ValueError names the missing rows of the window otherwise.  Afterwards the instance holds
+        the row window [r0, r1): ``dem`` = those rows of the whole raster's synthesised DEM, bit for bit, ``img`` = the same
+        rows of the ortho as loaded, ``row0`` = r0, ``dem_shape`` unchanged — the state after setImages(row0=, full_shape=).
+        ``self.image`` is set to None: the in-filled ortho, which the reference stores and never uses, is not computed for
+        a window.  With ``swap_dsize=True`` a square raster gives the same rows as with False; a non-square one raises
+        ValueError (the transposed result of :241 has no row windows, and the reference cannot run such a raster either).
+
+        Without ``rows`` the whole raster is pre-processed, and with a row window set this raises ValueError."""
         from . import preprocess as pp
         if self.img is None or self.dem is None:
             raise ValueError("preprocess needs the rasters: call loadImages() or setImages() first.")
+        if rows is not None:
+            return self._preprocess_rows(pp, swap_dsize, (int(rows[0]), int(rows[1])))
         if self.windowed:
             raise ValueError(f"preprocess works on whole rasters: rows [{self.row0}, {self.row0 + self.dem.shape[0]}) of "
                              f"{self.dem_shape[0]} are set as a row window")
         self.image, self.dem = pp.preprocess(self._lib, self._h, self.device, self.img, self.dem, self.no_value,
                                              swap_dsize=swap_dsize)
 
+    def _preprocess_rows(self, pp, swap_dsize: bool, rows: Tuple[int, int]) -> None:
+        H, W = self.dem_shape
+        if swap_dsize and H != W:
+            raise ValueError(f"preprocess(rows=) on a {H} x {W} raster with swap_dsize=True: process_full_tiles.py:241 hands "
+                             "(rows, cols) to cv2.resize as (width, height), so a non-square raster comes out transposed; "
+                             "pass swap_dsize=False")
+        r0, r1 = rows
+        m0, m1 = pp.window_plan(self.dem_shape, rows)["dem"]
+        have = (self.row0, self.row0 + self.dem.shape[0])
+        need = (min(m0, r0), max(m1, r1))
+        if need[0] < have[0] or need[1] > have[1]:
+            missing = [f"[{a}, {b})" for a, b in ((need[0], min(need[1], have[0])), (max(need[0], have[1]), need[1])) if b > a]
+            raise ValueError(f"preprocess(rows=({r0}, {r1})) reads raster rows [{need[0]}, {need[1]}); the row window "
+                             f"[{have[0]}, {have[1]}) held lacks rows {' and '.join(missing)}")
+        dem = pp.preprocess_rows(self._lib, self._h, self.device, self.dem, self.row0, self.dem_shape, rows, self.no_value)
+        img = np.ascontiguousarray(self.img[r0 - self.row0:r1 - self.row0])
+        self.setImages(img, dem, row0=r0, full_shape=self.dem_shape)
+        self.image = None
+
     def processFiles(self, preprocess: bool = True, rank: int = 0, world: int = 1, mode: Optional[str] = None,
-                     gather: bool = True) -> None:
+                     gather: bool = True, swap_dsize: bool = True) -> None:
         """processMap of the reference on files (process_full_tiles.py:568-587): loadImages -> preprocess ->
         padInputs -> tiles -> rebuildMap -> ``<map>_mean.tiff``, ``<map>_std.tiff``, ``<map>_good.tiff``.
-        ``preprocess=False`` skips the low-resolution-DEM synthesis (feed an already pre-processed DEM).
+        ``preprocess=False`` skips the low-resolution-DEM synthesis (feed an already pre-processed DEM); ``swap_dsize`` is
+        preprocess()'s.
 
         ``mode="tiles"``: this process is ``rank`` of ``world`` of a tile-row-sharded run.  It reads the shape from the
-        header (geotiff.read_info), decodes and uploads only the raster rows its tiles touch (distributed.input_rows,
-        loadImages(rows=)), runs its tile rows (distributed.process_map_sharded) and, with ``gather`` (needs an initialised
-        process group), all-gathers the finished rows; without it the rows of other ranks stay zero in the files written.
-        Pre-processing is a whole-raster operation: ``preprocess`` must be False.  ``mode="halo"`` is accepted by
-        HaloShardedSuperResolution.processFiles only."""
+        header (geotiff.read_info), decodes only the raster rows it needs (loadImages(rows=)) — the rows its tiles touch
+        (distributed.input_rows), or with ``preprocess`` the band of input rows their synthesised DEM depends on
+        (input_rows(preprocess=True)), which it pre-processes itself (preprocess(rows=)) — uploads only its tiles' rows,
+        runs its tile rows (distributed.process_map_sharded) and, with ``gather`` (needs an initialised process group),
+        all-gathers the finished rows; without it the rows of other ranks stay zero in the files written.
+        ``mode="halo"`` is accepted by HaloShardedSuperResolution.processFiles only."""
         if mode is not None:
-            mean, std, good = self._process_files_sharded(preprocess, rank, world, mode, gather)
+            mean, std, good = self._process_files_sharded(preprocess, rank, world, mode, gather, swap_dsize)
         else:
             self.loadImages()
             if preprocess:
-                self.preprocess()
+                self.preprocess(swap_dsize=swap_dsize)
             mean, std, good = self.processMap()
         self.saveGTiff(mean, mean.dtype, "mean")
         self.saveGTiff(std, std.dtype, "std")
         self.saveGTiff(good, good.dtype, "good")
 
-    def _load_rank_rows(self, preprocess: bool, rank: int, world: int, mode: str) -> Tuple[int, int]:
-        """read_info -> input_rows -> loadImages(rows=): the rows of both files that ``rank`` needs, nothing else."""
+    def _load_rank_rows(self, preprocess: bool, rank: int, world: int, mode: str, swap_dsize: bool = True
+                        ) -> Tuple[int, int]:
+        """read_info -> input_rows -> loadImages(rows=) [-> preprocess(rows=)]: the rows of both files that ``rank`` needs,
+        nothing else.  Returns the rows held afterwards: input_rows(preprocess=False)."""
         from . import geotiff
         from .distributed import input_rows
-        if preprocess:
-            raise ValueError("a sharded rank reads a row window and preprocess works on whole rasters: pre-process the "
-                             "rasters first and pass preprocess=False")
         dem_path = os.path.join(self.folder_path, self.dem_name)
         if not os.path.exists(dem_path):
             raise ValueError("The path given for the dem does not exist. Provided path is: " + dem_path)
         shape = geotiff.read_info(dem_path)["shape"]
-        r0, r1 = input_rows(shape, self.image_size, self.stride, self.tile_size, rank, world, mode)
-        if r1 > r0:
+        geometry = (shape, self.image_size, self.stride, self.tile_size, rank, world, mode)
+        r0, r1 = input_rows(*geometry)
+        if r1 > r0 and preprocess:
+            # the band the synthesis reads, and [r0, r1) itself for the ortho: the band can end up to two rows short of a
+            # raster whose 4 * rint(H / 4) < H, rows that no resampler reads
+            m0, m1 = input_rows(*geometry, preprocess=True)
+            self.loadImages(rows=(min(m0, r0), max(m1, r1)))
+            self.preprocess(swap_dsize=swap_dsize, rows=(r0, r1))
+        elif r1 > r0:
             self.loadImages(rows=(r0, r1))
         else:                                         # a rank without work: no pixel is read
             self.geo_meta = geotiff.read_info(dem_path)
@@ -289,12 +326,13 @@ class DEMSuperResolution:
             self.setImages(empty, empty, row0=0, full_shape=shape)
         return r0, r1
 
-    def _process_files_sharded(self, preprocess: bool, rank: int, world: int, mode: str, gather: bool):
+    def _process_files_sharded(self, preprocess: bool, rank: int, world: int, mode: str, gather: bool,
+                               swap_dsize: bool = True):
         from .distributed import process_map_sharded
         if mode != "tiles":
             raise ValueError(f"DEMSuperResolution.processFiles shards by tile rows (mode='tiles'), got {mode!r}; the halo "
                              "mode is HaloShardedSuperResolution.processFiles")
-        self._load_rank_rows(preprocess, rank, world, mode)
+        self._load_rank_rows(preprocess, rank, world, mode, swap_dsize)
         self.padInputs()
         return process_map_sharded(self.dem_shape, self.tile_size, self.generateTileList(), self.processTile, rank, world,
                                    gather=gather, device=self.device)
