@@ -98,6 +98,17 @@ typedef struct {
  *                     epilogue writes the fp6 image.  Not valid with MSR_FLAG_F16_MAIN (no cross terms to move); ignored for
  *                     MSR_PIX2PIX.  Not the default: the measured A/B is in DESIGN.md. */
 #define MSR_FLAG_CROSS_FP6 32
+/*   MSR_FLAG_BF16X3 | MSR_FLAG_F16C | MSR_FLAG_FUSED_HEAD   opt-in: the last residual conv (gen.rb6.conv_2, 128 -> 128 at r = S/2)
+ *                     does not write its output; its epilogue applies leaky_relu(0.2) and reduces the 128 channels against the
+ *                     head's 25 live per-parity taps, writing 32 partial sums per pixel (ws.gen.head.partial), and a gather
+ *                     kernel adds the neighbours' sums and the bias.  The plan takes it when that conv runs the stream kernel
+ *                     on whole tiles (B * (S/32)^2 >= 256 tiles); otherwise the separate head runs unchanged (see
+ *                     msr_debug_conv_forms: kind=head_gather).  The head's products are three fp16 terms (hi = f16_rn(x),
+ *                     lo = f16_rn(x - hi)) accumulated in fp32: within ~1e-6 of the fp32 head, but the fp16 conversion
+ *                     SATURATES: an activation beyond 65504 gives a finite, wrong result where the fp32 head has no such limit.
+ *                     msr_create returns MSR_ERR_INVALID without MSR_FLAG_F16C, with MSR_FLAG_F16_MAIN or MSR_FLAG_CROSS_FP6,
+ *                     and for MSR_PIX2PIX.  Not the default: the measured A/B is in DESIGN.md. */
+#define MSR_FLAG_FUSED_HEAD 64
 
 typedef struct msr_handle msr_handle;
 
@@ -327,6 +338,15 @@ int msr_op_spade_gbr(msr_handle* h, const float* src_dev, int32_t S, const float
  * wt_dev are not read); the embedding (phase 1) is computed as in msr_op_spade_gbr.  Same arguments and checks. */
 /* msr_op_spade_gbr writing the f16c6 chunk image (MSR_FLAG_CROSS_FP6's form: fp16 | fp6 e2m3 pieces with one block scale per
  * pixel and 32 channels, the input of msr_op_conv3x3_f16c with wexp_dev == NULL) into out_dev.  Same arguments and checks. */
+/* Kernel-level entry of the fused head: msr_op_conv3x3_f16c with the residual epilogue on the stream kernel, whose epilogue
+ * writes the head's partial sums instead of the output, then the gather kernel (synchronous).  N must be 128 and the shape the
+ * stream kernel's (Cin % 128 == 0, rout >= 16 a power of two, wexp_dev given); MSR_ERR_INVALID otherwise.
+ *   head_kernel_host [4, 4, 128, 1] (host), head_bias;  out_dev [B, 2 rout, 2 rout];
+ *   partial_dev      optional [B, rout, rout, 32]: the partial sums, slot order as in csrc/kernels.h (HEAD_SLOTS) */
+int msr_op_conv3x3_f16c_head(msr_handle* h, const float* in_dev, const float* wt_dev, const int32_t* wexp_dev,
+                             const float* bias_dev, int32_t B, int32_t rout, int32_t Cin, int32_t N, const float* aux_dev,
+                             int32_t aux_shift, const float* head_kernel_host, float head_bias, float* out_dev,
+                             float* partial_dev, void* stream);
 int msr_op_spade_gbr_f16c6(msr_handle* h, const float* src_dev, int32_t S, const float* we_dev, const float* be_dev,
                            const float* wt_dev, const float* bias_dev, float* out_dev, int32_t B, int32_t r, int32_t N,
                            const float* aux_dev, int32_t aux_shift, const float* mean_dev, const float* std_dev, void* stream);
@@ -389,14 +409,17 @@ int msr_op_conv3x3_fp8(msr_handle* h, const void* in_dev, const void* wt_dev, co
 int msr_op_split_bf16(msr_handle* h, const float* in_dev, float* out_dev, int64_t count, void* stream);
 
 /* Debug / per-block parity aid: copy a named workspace tensor of the last msr_forward to a HOST buffer
- * (names: "ws.gen.x0", "ws.gen.rb3.x1", "ws.gen.rb3.out", "ws.enc.mv", ...).  Synchronises the device. */
+ * (names: "ws.gen.x0", "ws.gen.rb3.x1", "ws.gen.rb3.out", "ws.enc.mv", ...).  Synchronises the device.  Under a fused-head plan
+ * (MSR_FLAG_FUSED_HEAD) "ws.gen.rb6.out" does not exist (MSR_ERR_INVALID, the message says so); "ws.gen.head.partial" does. */
 int msr_debug_tensor(msr_handle* h, const char* name, float* host_out, int64_t count);
 /* Debug, read-only: one line "<mean tensor name> <form>" per planned moments site of the network, in plan order: A (moments
  * kernels over the tensor), B (split-K epilogue), E1 | E2 (one- | two-stage finalize of conv slabs) followed by /C (slabs of
  * the conv_igemm epilogue) or /D (ping-pong / stream kernels).  NUL-terminated; MSR_ERR_INVALID when cap is too small. */
 int msr_debug_moment_forms(msr_handle* h, char* out, int64_t cap);
 /* Debug, read-only: one line per planned op of the network, in plan order, as "key=value" words.  kind = conv | gbr
- * (conv_gb_resident) | smallcin | norm_act | dense | latent | head | moments | moments_slabs | direct; in / wt / wexp / bias / aux
+ * (conv_gb_resident) | smallcin | norm_act | dense | latent | head | head_gather (the fused head's second launch:
+ * "kind=head_gather in=ws.gen.head.partial out=output B= r=", behind a conv line with epi=5 whose mean names gen.head.wfrag) |
+ * moments | moments_slabs | direct; in / wt / wexp / bias / aux
  * / mean / std / out name the op's tensors as msr_debug_tensor knows them ("input", "eps", "output": the call's own tensors,
  * "-": none); conv and gbr lines carry prec, tile, ksplit, wt_frag, no_cross, epi, out_split, ranges (work items per pixel tile
  * of the resident kernel, else 0) and img, the weight image msr_load_weight built (F32, BF16, BF16_FRAG, F16, FP8, F16C, F16C6,

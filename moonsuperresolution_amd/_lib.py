@@ -25,6 +25,8 @@ PRECISION_FLAGS = {"fp32": 0, "bf16x3": 1, "bf16x3_gbf16": 3, "fp8": 5, "f16c": 
 # MSR_FLAG_CROSS_FP6 = 32 (with F16C, not F16_MAIN): the format of the cross terms in the stream-kernel consumers, or-ed into
 # the precision's flags (Generator(cross=...)); "fp8" is the f16c mode as it always was
 CROSS_FLAGS = {"fp8": 0, "fp6": 32}
+# MSR_FLAG_FUSED_HEAD = 64 (with F16C alone): the last residual conv emits the head's partial sums (Generator(head=...))
+HEAD_FLAGS = {"separate": 0, "fused": 64}
 
 
 class MsrConfig(C.Structure):
@@ -89,6 +91,8 @@ SYMBOLS = [
                                         C.c_int32, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
     ("msr_op_conv3x3_f16c", C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P,
                                       C.c_int32, _P, _P, C.c_int32, C.c_int32, _P]),
+    ("msr_op_conv3x3_f16c_head", C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P,
+                                           C.c_float, _P, _P, _P]),
     ("msr_op_spade_gbr", C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P, _P]),
     ("msr_op_spade_gbr_f16", C.c_int, [_P, _P, C.c_int32, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, _P, _P,
                                        _P]),

@@ -273,6 +273,16 @@ int msr_create(const msr_config* cfg, msr_handle** out) {
     if ((cfg->flags & MSR_FLAG_CROSS_FP6) && (!(cfg->flags & MSR_FLAG_F16C) || (cfg->flags & MSR_FLAG_F16_MAIN)))
         return fail(nullptr, MSR_ERR_INVALID, "MSR_FLAG_CROSS_FP6 modifies MSR_FLAG_F16C and does not go with MSR_FLAG_F16_MAIN (which computes no cross terms)");
     h->cross6 = h->f16c && (cfg->flags & MSR_FLAG_CROSS_FP6);
+    if (cfg->flags & MSR_FLAG_FUSED_HEAD) {
+        if (!(cfg->flags & MSR_FLAG_F16C))
+            return fail(nullptr, MSR_ERR_INVALID, "MSR_FLAG_FUSED_HEAD needs MSR_FLAG_F16C (the head epilogue exists in the f16c stream kernel)");
+        if (cfg->flags & (MSR_FLAG_F16_MAIN | MSR_FLAG_CROSS_FP6))
+            return fail(nullptr, MSR_ERR_INVALID, "MSR_FLAG_FUSED_HEAD does not go with MSR_FLAG_F16_MAIN or MSR_FLAG_CROSS_FP6 (they run "
+                        "other instantiations of the stream kernel, which have no head epilogue)");
+        if (cfg->variant == MSR_PIX2PIX)
+            return fail(nullptr, MSR_ERR_INVALID, "MSR_FLAG_FUSED_HEAD serves the SPADE head only, not variant pix2pix");
+        h->fused_head = true;
+    }
     if (cfg->variant == MSR_PIX2PIX) { h->prec = PREC_F32; h->gb_f16x2 = false; }   // the parity config runs on the fp32 MFMA
     build_specs(h.get());
     fill_forms(h.get());
@@ -420,7 +430,13 @@ int msr_load_weight(msr_handle* h, const char* name_c, const float* host, const 
             break;
         }
         case W_HEAD_KERNEL: {
-            // effective per-parity taps of Conv2D(1,4,'same') applied to a nearest-2x up-sampled tensor
+            // effective per-parity taps of Conv2D(1,4,'same') applied to a nearest-2x up-sampled tensor: for head_kernel, or,
+            // where the plan fuses the head, as fp16 hi | lo MFMA fragments for conv_sw.hip's sw_epilogue_head
+            if (head_fused_form(h)) {
+                const std::vector<float> wfrag = build_head_wfrag(host);
+                rc = upload(h, "gen.head.wfrag", wfrag.data(), wfrag.size());
+                break;
+            }
             const std::vector<float> weff = head_weff_upconv(host, (int)s[2]);
             rc = upload(h, "gen.head.weff", weff.data(), weff.size());
             break;

@@ -171,6 +171,100 @@ __device__ __forceinline__ void sw_epilogue(const ConvParams& p, const SwGeom& g
         __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "workgroup"); \
     }
 #endif
+// Head epilogue (EPI_RES_HEAD, kernels.h): the residual epilogue's value v = acc + residual + bias is not written; the
+// workgroup reduces a = leaky_relu(v, 0.2) over its 128 channels against the 25 live tap vectors of the SPADE head
+// (weight_images.hip head_weff_upconv) and writes the 32-slot line P[b, y, x, :] the gather kernel sums (small_kernels.hip
+// head_gather_kernel; slot order: kernels.h HEAD_SLOTS).
+//   * a lane's acc[i][0][0..3] | acc[i][1][0..3] are 8 channels of pixel (row i, x = lane & 15): one lane's 8 K values of the
+//     B operand of v_mfma_f32_16x16x32_f16 as they lie (K position 8 cg + e = channel base + 32 (e >> 2) + 4 cg + (e & 3));
+//     the A operand is the fragment image p.mean = gen.head.wfrag built in the same order ([wave][slot block][hi | lo][lane]
+//     x 16 B, build_head_wfrag), so nothing is shuffled.  D = [4 slots 16 sb + 4 cg + k][pixel], the accumulators' orientation.
+//   * three fp16 products per term, w_hi a_hi + w_hi a_lo + w_lo a_hi with hi = f16_rn(x), lo = f16_rn(x - hi), fp32
+//     accumulation (phase 1 of conv_gb_resident): 6 MFMAs per tile row.  a_hi saturates at 65504 (MSR_SATURATING_CONVERSIONS).
+//   * the four waves' partials (32 channels each) meet in LDS and are summed in the fixed order ((w0 + w1) + w2) + w3: no
+//     atomics.  At this point ring buffer `rbn` holds chunk 0 of the next tile; the other two are free once every wave has left
+//     its last phase C (first barrier).  A wave's partial of 8 rows is 16 KB: waves 0 | 1 share one free buffer, 2 | 3 the
+//     other, and the tile goes in two groups of 8 rows.  Five barriers per tile, passed by every wave on every tile; the last
+//     one keeps the next tile's halo staging (tap 3 of its first chunk) behind the last reads of the sums.
+//   * LDS line of a pixel: 8 units of 16 B, unit u at position u ^ (px >> 1): a wave's 16 pixels x 4 lane groups store
+//     conflict-free (pixel pitch 128 B = half the banks), the readers go through the same map.
+__device__ __forceinline__ void sw_epilogue_head(const ConvParams& p, f32x4 (&acc)[16][2], int wq, int lane, int tid,
+                                                 int tx0, int ty0, int b0, float* smem, int rbn) {
+    const int px = lane & 15, cg = lane >> 4;
+    const int x = tx0 + px;
+    const int cb0 = (wq >> 1) * 64 + (wq & 1) * 16 + 4 * cg;           // N = 128: n0 = 0
+    const i32x4* const wf = reinterpret_cast<const i32x4*>(p.mean) + wq * 256 + lane;
+    const i32x4 wh0 = wf[0], wl0 = wf[64], wh1 = wf[128], wl1 = wf[192];
+    float bq[2][4];
+#pragma unroll
+    for (int j = 0; j < 2; ++j) {
+        const float4 b4 = *reinterpret_cast<const float4*>(p.bias + cb0 + 32 * j);
+        bq[j][0] = b4.x; bq[j][1] = b4.y; bq[j][2] = b4.z; bq[j][3] = b4.w;
+    }
+    const int f1 = rbn == 2 ? 0 : rbn + 1, f2 = f1 == 2 ? 0 : f1 + 1;
+    constexpr int WP = 8 * 16 * 32;                                     // floats of one wave's partial of 8 rows
+    float* const mine = smem + ((wq >> 1) ? f2 : f1) * SW_HPB + (wq & 1) * WP + px * 32;
+    const int sw = (px >> 1) & 7;
+    const float* const abase = p.aux + (size_t)b0 * p.aux_pb + (x >> p.aux_shift) * p.aux_px + cb0;
+    SW_BARRIER()
+#pragma unroll
+    for (int g8 = 0; g8 < 2; ++g8) {
+        if (g8) SW_BARRIER()                                            // the sums of group 0 have been read
+#pragma unroll
+        for (int i4 = 0; i4 < 8; i4 += 4) {
+            float4 res[4][2];
+#pragma unroll
+            for (int ii = 0; ii < 4; ++ii)
+#pragma unroll
+                for (int j = 0; j < 2; ++j)
+                    res[ii][j] = *reinterpret_cast<const float4*>(abase + ((ty0 + g8 * 8 + i4 + ii) >> p.aux_shift) * p.aux_py + 32 * j);
+#pragma unroll
+            for (int ii = 0; ii < 4; ++ii) {
+                const int i = g8 * 8 + i4 + ii;
+                f16x8 ah, al;
+#pragma unroll
+                for (int j = 0; j < 2; ++j) {
+                    const float rq[4] = {res[ii][j].x, res[ii][j].y, res[ii][j].z, res[ii][j].w};
+#pragma unroll
+                    for (int k = 0; k < 4; ++k) {
+                        const float v = (acc[i][j][k] + rq[k]) + bq[j][k];       // EPI_RES's value, in its order
+                        const float a = v >= 0.f ? v : 0.2f * v;
+                        const _Float16 hi = (_Float16)a;
+                        ah[4 * j + k] = hi;
+                        al[4 * j + k] = (_Float16)(a - (float)hi);
+                    }
+                }
+                f32x4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = {0.f, 0.f, 0.f, 0.f};
+                d0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, wh0), ah, d0, 0, 0, 0);
+                d1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, wh1), ah, d1, 0, 0, 0);
+                d0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, wh0), al, d0, 0, 0, 0);
+                d1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, wh1), al, d1, 0, 0, 0);
+                d0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, wl0), ah, d0, 0, 0, 0);
+                d1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, wl1), ah, d1, 0, 0, 0);
+                float* const row = mine + (i4 + ii) * 512;
+                *reinterpret_cast<f32x4*>(row + 4 * (cg ^ sw)) = d0;
+                *reinterpret_cast<f32x4*>(row + 4 * ((4 + cg) ^ sw)) = d1;
+            }
+        }
+        SW_BARRIER()
+        const float* const s1 = smem + f1 * SW_HPB;
+        const float* const s2 = smem + f2 * SW_HPB;
+#pragma unroll
+        for (int m = 0; m < 4; ++m) {
+            const int u = tid + 256 * m;                                // 16-byte unit of the group: [8 rows][16 pixels][8]
+            const int ii = u >> 7, pxr = (u >> 3) & 15;
+            const int l = ii * 512 + pxr * 32 + 4 * ((u & 7) ^ ((pxr >> 1) & 7));
+            const f32x4 a0 = *reinterpret_cast<const f32x4*>(s1 + l), a1 = *reinterpret_cast<const f32x4*>(s1 + WP + l);
+            const f32x4 a2 = *reinterpret_cast<const f32x4*>(s2 + l), a3 = *reinterpret_cast<const f32x4*>(s2 + WP + l);
+            const f32x4 sum = ((a0 + a1) + a2) + a3;
+            float* const o = p.out + (size_t)p.out_off + (size_t)b0 * p.out_pb + (size_t)(ty0 + g8 * 8 + ii) * p.out_py +
+                             (size_t)(tx0 + pxr) * p.out_px + 4 * (u & 7);
+            *reinterpret_cast<f32x4*>(o) = sum;
+        }
+    }
+    SW_BARRIER()
+}
+
 #ifndef SW_UNROLL2
 #define SW_UNROLL2 1
 #endif
@@ -495,7 +589,8 @@ conv_igemm_f16c_sw(const ConvParams p, const SwGeom g) {
 #ifdef SW_NOEPI   // what-if build (wrong results): the cost of the exposed epilogue
         if (p.B < 0)
 #endif
-        sw_epilogue<EPI>(p, g, acc, wq, lane, n0, tx0, ty0, b0);
+        if constexpr (EPI == EPI_RES_HEAD) sw_epilogue_head(p, acc, wq, lane, tid, tx0, ty0, b0, smem, rb);
+        else sw_epilogue<EPI>(p, g, acc, wq, lane, n0, tx0, ty0, b0);
 #ifdef MSR_SW_STAMPS
         if (blockIdx.x == 8 && lane == 0 && dbg_n > 0 && dbg_n < 63 && dbg[63] == 0) dbg[63] = (unsigned)__builtin_amdgcn_s_memtime() - te0_;
 #endif
@@ -542,7 +637,7 @@ hipError_t conv_sw_init() {
     if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_f16c_sw<EPI>),                    \
                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)SW_LDS)) != hipSuccess)    \
         return e;
-    SW_SET(EPI_BIAS) SW_SET(EPI_RES) SW_SET(EPI_SPADE)
+    SW_SET(EPI_BIAS) SW_SET(EPI_RES) SW_SET(EPI_SPADE) SW_SET(EPI_RES_HEAD)
 #undef SW_SET
     if ((e = hipFuncSetAttribute(reinterpret_cast<const void*>(&conv_igemm_f16c_sw<EPI_BIAS, true>),
                                  hipFuncAttributeMaxDynamicSharedMemorySize, (int)SW_LDS)) != hipSuccess) return e;
@@ -563,6 +658,8 @@ hipError_t launch_conv_f16c_sw(const ConvParams& p, int epi, hipStream_t s) {
     const bool f6 = p.prec == PREC_F16C6;
     if ((p.prec != PREC_F16C && !f6) || (!f6 && !p.wexp) || p.ksplit > 1 || p.stride != 1 || p.KH != 3 || p.KW != 3) return hipErrorInvalidValue;
     if (f6 && epi == EPI_SPADE) return hipErrorInvalidValue;          // the fp6 form exists for the main convs
+    // the head epilogue: one column block, the plain f16c form, the fragment image of the head's weights in p.mean
+    if (epi == EPI_RES_HEAD && (f6 || p.no_cross || p.N != 128 || !p.mean || !p.aux || p.out_px != 32)) return hipErrorInvalidValue;
     if (!pow2(p.Hout) || !pow2(p.Wout) || p.Hout < 16 || p.Wout < 16 || p.N % 128 || p.Cin % (SW_UNROLL2 ? 128 : 64)) return hipErrorInvalidValue;
     if ((size_t)p.B * p.in_pb * sizeof(float) >= ((size_t)1 << 31)) return hipErrorInvalidValue;   // buffer descriptor range
     SwGeom g;
@@ -588,6 +685,7 @@ hipError_t launch_conv_f16c_sw(const ConvParams& p, int epi, hipStream_t s) {
         case EPI_BIAS: conv_igemm_f16c_sw<EPI_BIAS><<<grid, 256, SW_LDS, s>>>(p, g); break;
         case EPI_RES: conv_igemm_f16c_sw<EPI_RES><<<grid, 256, SW_LDS, s>>>(p, g); break;
         case EPI_SPADE: conv_igemm_f16c_sw<EPI_SPADE><<<grid, 256, SW_LDS, s>>>(p, g); break;
+        case EPI_RES_HEAD: conv_igemm_f16c_sw<EPI_RES_HEAD><<<grid, 256, SW_LDS, s>>>(p, g); break;
         default: return hipErrorInvalidValue;
     }
     return hipGetLastError();

@@ -21,6 +21,9 @@ extern "C" {
 int msr_debug_tensor(msr_handle* h, const char* name, float* host_out, int64_t count) {
     if (!h || !name || !host_out) return MSR_ERR_INVALID;
     auto it = h->dev.find(name);
+    if (it == h->dev.end() && !std::strcmp(name, "ws.gen.rb6.out") && head_fused_form(h))
+        return fail(h, MSR_ERR_INVALID, "ws.gen.rb6.out does not exist under MSR_FLAG_FUSED_HEAD: gen.rb6.conv_2 writes the head's "
+                    "partial sums ws.gen.head.partial [B, r, r, 32] instead of its output");
     if (it == h->dev.end()) return fail(h, MSR_ERR_INVALID, "no tensor named '%s'", name);
     if (count < 0 || (size_t)count * sizeof(float) > h->dev_bytes[name])
         return fail(h, MSR_ERR_INVALID, "%s holds %zu floats, %lld requested", name, h->dev_bytes[name] / sizeof(float),
@@ -127,6 +130,10 @@ int msr_debug_conv_forms(msr_handle* h, char* out, int64_t cap) {
             case OP_HEAD:
                 snprintf(b, sizeof b, "kind=head in=%s wt=%s out=output B=%d r=%d cin=%d tanh=%d\n", tensor_of(op.head.x).c_str(),
                          tensor_of(op.head.weff).c_str(), op.head.B, op.head.r, op.head.C, op.head.tanh_out);
+                break;
+            case OP_HEAD_GATHER:
+                snprintf(b, sizeof b, "kind=head_gather in=%s out=output B=%d r=%d\n", tensor_of(op.hg.partial).c_str(), op.hg.B,
+                         op.hg.r);
                 break;
             case OP_DIRECT:
                 snprintf(b, sizeof b, "kind=direct in=%s wt=%s out=%s B=%d r=%d N=%d\n", op.src_is_input ? "input" : tensor_of(op.dc.in0).c_str(),

@@ -151,4 +151,16 @@ void fill_forms(msr_handle* h) {
     }
 }
 
+// The fused head (kernels.h EPI_RES_HEAD) is one instantiation of the stream kernel: gen.rb6.conv_2 (128 -> 128 at r = S / 2)
+// takes it when it runs there on whole tiles in the plain f16c form.  Anywhere else (K ranges on the ping-pong kernel at small
+// shapes, MSR_F16C_SW other than 1) the plan keeps the separate head: a fallback, not an error.
+bool head_fused_form(const msr_handle* h) {
+    static const bool sw_on = env_int("MSR_F16C_SW", 1) == 1;
+    if (!h->fused_head || h->variant == MSR_PIX2PIX || !sw_on) return false;
+    const ConvForm& cv = h->spade_forms[6][2].cv;
+    const int r = h->S / 2;
+    return cv.prec == PREC_F16C && cv.tile == TILE_256x128_PP && cv.ksplit == 1 && !cv.no_cross && kGenFilters[5] == 128 &&
+           r >= 16 && (r & (r - 1)) == 0;
+}
+
 }  // namespace msr

@@ -90,7 +90,8 @@ static int launch_all(msr_handle* h, const float* in_dev, const float* eps_dev, 
                 cp.partial = h->conv_partial;
                 cp.mom_partial = h->mom_partial;
                 cp.stat_partial = op.stat_slabs > 0 ? h->stat_ws : nullptr;
-                e = launch_conv_igemm(cp, op.epi, op.tile, s);
+                // the head epilogue exists in the stream kernel only: no dispatch that could send it elsewhere
+                e = op.epi == EPI_RES_HEAD ? launch_conv_f16c_sw(cp, op.epi, s) : launch_conv_igemm(cp, op.epi, op.tile, s);
                 break;
             }
             case OP_SMALLCIN: {
@@ -124,6 +125,10 @@ static int launch_all(msr_handle* h, const float* in_dev, const float* eps_dev, 
                 fam = FAM_HEAD;
                 e = launch_head(op.head.x, op.head.weff, op.head.bias, out_dev, op.head.B, op.head.r, op.head.C,
                                 op.head.slope, op.head.tanh_out, op.head.x_py, op.head.x_pb, s);
+                break;
+            case OP_HEAD_GATHER:
+                fam = FAM_HEAD;
+                e = launch_head_gather(op.hg.partial, op.hg.bias, out_dev, op.hg.B, op.hg.r, s);
                 break;
             case OP_GBR: {
                 fam = FAM_CONV;

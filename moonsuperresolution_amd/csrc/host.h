@@ -29,7 +29,7 @@ enum WeightKind {
     W_SPADE_EMBED_BIAS,    // gen.rb<i>.spade_<j>.conv.bias: reference layout + host copy
     W_ENC_HEAD_KERNEL,     // enc.mean / enc.variance kernel -> one half of enc.heads.kernel (flag: variance)
     W_ENC_HEAD_BIAS,       // ... bias -> one half of enc.heads.bias (flag: variance)
-    W_HEAD_KERNEL,         // gen.head.kernel -> gen.head.weff
+    W_HEAD_KERNEL,         // gen.head.kernel -> gen.head.weff, or gen.head.wfrag where the plan fuses the head
     W_HEAD_BIAS,           // gen.head.bias: host copy
     W_GB_KERNEL,           // gen.rb<i>.spade_<j>.conv_gamma / conv_beta kernel -> one half of .gb.kernel (flag: beta)
     W_GB_BIAS,             // ... bias -> one half of .gb.bias (flag: beta)
@@ -46,7 +46,7 @@ struct WeightSpec {
     bool loaded = false;
 };
 
-enum OpType { OP_CONV, OP_SMALLCIN, OP_MOMENTS, OP_MOMENTS_SLABS, OP_NORMACT, OP_DENSE, OP_LATENT, OP_HEAD, OP_DIRECT, OP_GBR };
+enum OpType { OP_CONV, OP_SMALLCIN, OP_MOMENTS, OP_MOMENTS_SLABS, OP_NORMACT, OP_DENSE, OP_LATENT, OP_HEAD, OP_DIRECT, OP_GBR, OP_HEAD_GATHER };
 
 struct Op {
     OpType type;
@@ -67,6 +67,7 @@ struct Op {
     struct { const float* mv; float* z; int B, L, sampler; } lat{};
     struct { const float* x; const float* weff; float bias; int B, r, C; float slope; int tanh_out; int x_py, x_pb; } head{};
     DirectConvParams dc{};
+    struct { const float* partial; float bias; int B, r; } hg{};   // OP_HEAD_GATHER: the fused head's second launch
 };
 
 struct ProfRec { int fam; hipEvent_t a, b; double flops, bytes; int launches; };
@@ -119,6 +120,7 @@ struct msr_handle {
     bool f16c = false;                           // MSR_FLAG_F16C: fp16 main term + fp8 cross terms in the chip-filling convs
     bool f16m = false;                           // MSR_FLAG_F16_MAIN: F16C without the cross terms in the stream / resident kernels
     bool cross6 = false;                         // MSR_FLAG_CROSS_FP6: fp6 cross terms in the stream-kernel consumers of F16C
+    bool fused_head = false;                     // MSR_FLAG_FUSED_HEAD: the request; head_fused_form() says whether the plan takes it
     msr::ConvForm enc_forms[6];                  // [i]: enc.ds<i> (i = 2..5)
     msr::SpadeForm spade_forms[7][4];            // [i][j]: gen.rb<i>.spade_<j> and gen.rb<i>.conv_<j> (i = 1..6, j = 1..3)
     std::string err;
@@ -210,12 +212,15 @@ std::vector<float> build_fp8_image(const float* host, int taps, int N, int Cin, 
 std::vector<float> gbr_weight_stream(const float* w_tap_n_k, int N);
 std::vector<float> head_weff_upconv(const float* k44c, int C);
 std::vector<float> head_weff_transpose(const float* k44c, int C);
+std::vector<float> build_head_wfrag(const float* k44c);       // gen.head.wfrag: the stream kernel's head epilogue (C = 128)
 int fp8_pad(int cin);
 
 // ---- forms.hip ----
 ConvForm make_form(int prec, int tile, int ksplit, int wt_frag = 0, int no_cross = 0);
 ConvForm conv_form(int B, int rout, int N, int stride, int epi, int prec, int cin, int taps = 9);
 void fill_forms(msr_handle* h);
+// MSR_FLAG_FUSED_HEAD is set and gen.rb6.conv_2 runs the whole-tile stream-kernel form the head epilogue exists for
+bool head_fused_form(const msr_handle* h);
 
 // ---- plan.hip ----
 Op conv_op(const Padded& in, int cin, const float* wt, const float* bias, int B, int rout, int N, int stride, int epi,

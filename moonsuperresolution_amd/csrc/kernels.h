@@ -41,6 +41,8 @@ enum ConvEpilogue : int {
     EPI_PARTIAL = 3,  // split-K: raw accumulators to partial[ks][B,Hout,Wout,N]; splitk_epilogue finishes
     EPI_AFFINE = 4,   // out = act(acc * scale[c] + shift[c]): folded BatchNormalization + LeakyReLU / ReLU of the
                       // pix2pix blocks (pix2pix.py:65-86); scale == nullptr means 1
+    EPI_RES_HEAD = 5, // conv_igemm_f16c_sw only, N = 128: EPI_RES's value is not written; out = the SPADE head's partial sums
+                      // P[B, Hout, Wout, 32] of leaky_relu(value, 0.2) (HEAD_SLOTS below), `mean` = the head's fragment image
 };
 
 struct ConvParams {
@@ -49,7 +51,7 @@ struct ConvParams {
     const float* bias;    // [N] in GEMM column order
     float* out;
     const float* aux;     // EPI_RES: residual; EPI_SPADE: x (the tensor being normalised)
-    const float* mean;    // EPI_SPADE: [C]
+    const float* mean;    // EPI_SPADE: [C]; EPI_RES_HEAD: the head's fragment image (gen.head.wfrag, 16 KB)
     const float* stdv;    // EPI_SPADE: [C]  sqrt(var + eps)
     int B, Hout, Wout, Cin, N;
     int KH, KW, stride;
@@ -412,6 +414,20 @@ hipError_t launch_latent(const float* mv, const float* eps, float* z, int B, int
 //   x [B, r, r, C] at half resolution, weff = [2][2][3][3][C] effective per-parity weights, out [B, 2r, 2r].
 hipError_t launch_head(const float* x, const float* weff, float bias, float* out, int B, int r, int C, float slope,
                        int tanh_out, int x_py, int x_pb, hipStream_t s);   // x_py = 0: dense [B,r,r,C]
+
+// Fused head (opt-in, MSR_FLAG_FUSED_HEAD): the last residual conv runs conv_igemm_f16c_sw<EPI_RES_HEAD> and writes, per
+// half-resolution pixel, the head's partial sums P[b, y, x, 32] instead of its 128 output channels:
+//   P[b, y, x, slot(py, px, dy, dx)] = sum_c weff[py][px][dy][dx][c] * leaky_relu(v[b, y, x, c], 0.2)
+//   out[b, 2i + py, 2j + px]         = bias + sum over the live (dy, dx) of P[b, i + dy - 1, j + dx - 1, slot(py, px, dy, dx)]
+// (pixels outside the image contribute 0).  HEAD_SLOTS: weff[py][px][dy][dx] is live iff dy >= py and dx >= px (9 + 6 + 6 + 4 =
+// 25 entries); the slots count them in py, px, dy, dx order, slots 25..31 are written as zeros:
+//   slot = {0, 9, 15, 21}[2 py + px] + (dy - py) * (3 - px) + (dx - px)
+__host__ __device__ inline int head_slot(int py, int px, int dy, int dx) {
+    if (dy < py || dx < px) return -1;
+    return (py ? (px ? 21 : 15) : (px ? 9 : 0)) + (dy - py) * (3 - px) + (dx - px);
+}
+// head_gather_kernel: out[B, 2r, 2r] from P[B, r, r, 32], one thread per half-resolution pixel, fixed summation order
+hipError_t launch_head_gather(const float* partial, float bias, float* out, int B, int r, hipStream_t s);
 
 // ---------------------------------------------------------------------------------------------
 // Generic direct convolution (pix2pix plumbing config: Conv2D / Conv2DTranspose 4x4 s2, BN, act, concat)

@@ -111,6 +111,44 @@ int msr_op_conv3x3_f16c(msr_handle* h, const float* in_dev, const float* wt_dev,
     return MSR_OK;
 }
 
+int msr_op_conv3x3_f16c_head(msr_handle* h, const float* in_dev, const float* wt_dev, const int32_t* wexp_dev,
+                             const float* bias_dev, int32_t B, int32_t rout, int32_t Cin, int32_t N, const float* aux_dev,
+                             int32_t aux_shift, const float* head_kernel_host, float head_bias, float* out_dev,
+                             float* partial_dev, void* stream) {
+    if (!h) return MSR_ERR_INVALID;
+    if (!in_dev || !wt_dev || !wexp_dev || !bias_dev || !aux_dev || !head_kernel_host || !out_dev || B < 1)
+        return fail(h, MSR_ERR_INVALID, "msr_op_conv3x3_f16c_head: null argument");
+    if (N != 128 || Cin < 128 || Cin % 128 || rout < 16 || (rout & (rout - 1)) || aux_shift < 0 || aux_shift > 1)
+        return fail(h, MSR_ERR_INVALID, "msr_op_conv3x3_f16c_head: N must be 128, Cin a multiple of 128, rout >= 16 a power of two "
+                    "(the stream kernel's whole-tile form), aux_shift 0 | 1");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    hipStream_t s = (hipStream_t)stream;
+    Padded in; in.base = const_cast<float*>(in_dev); in.r = rout; in.C = Cin;
+    Op op = conv_op(in, Cin, wt_dev, bias_dev, B, rout, N, 1, EPI_RES_HEAD, make_form(PREC_F16C, TILE_256x128_PP, 1));
+    op.conv.wexp = wexp_dev;
+    const std::vector<float> wfrag = build_head_wfrag(head_kernel_host);
+    float *wd = nullptr, *pd = partial_dev;
+    HIPCHK(h, hipStreamSynchronize(s));
+    HIPCHK(h, hipMalloc(&wd, wfrag.size() * sizeof(float)));
+    hipError_t e = hipMemcpy(wd, wfrag.data(), wfrag.size() * sizeof(float), hipMemcpyHostToDevice);
+    if (e == hipSuccess && !pd) e = hipMalloc(&pd, (size_t)B * rout * rout * 32 * sizeof(float));
+    bool rejected = false;
+    if (e == hipSuccess) {
+        set_out_dense(op.conv, pd, rout, rout, 32);
+        set_aux_dense(op.conv, aux_dev, rout >> aux_shift, N, aux_shift);
+        op.conv.mean = wd;
+        e = launch_conv_f16c_sw(op.conv, EPI_RES_HEAD, s);
+        rejected = e != hipSuccess;
+    }
+    if (e == hipSuccess) e = launch_head_gather(pd, head_bias, out_dev, B, rout, s);
+    if (e == hipSuccess) e = hipStreamSynchronize(s);
+    hipFree(wd);
+    if (pd != partial_dev) hipFree(pd);
+    if (rejected) return fail(h, MSR_ERR_INVALID, "f16c head conv launch rejected: %s", hipGetErrorString(e));
+    if (e != hipSuccess) return fail(h, MSR_ERR_DEVICE, "msr_op_conv3x3_f16c_head failed: %s", hipGetErrorString(e));
+    return MSR_OK;
+}
+
 static int op_spade_gbr_impl(msr_handle* h, const float* src_dev, int32_t S, const float* we_dev, const float* be_dev,
                              const float* wt_dev, const float* bias_dev, float* out_dev, int32_t B, int32_t r, int32_t N,
                              const float* aux_dev, int32_t aux_shift, const float* mean_dev, const float* std_dev, int no_cross,

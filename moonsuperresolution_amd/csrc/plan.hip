@@ -141,7 +141,10 @@ static int plan_spade(msr_handle* h) {
         const bool learned = f != cin;
         float *x1, *skip = nullptr, *outb, *m1, *s1, *mo, *so;
         snprintf(n, sizeof n, "ws.gen.rb%d.x1", i); rc = dev_alloc(h, n, (size_t)B * r * r * f, false, &x1); if (rc) return rc;
-        snprintf(n, sizeof n, "ws.gen.rb%d.out", i); rc = dev_alloc(h, n, (size_t)B * r * r * f, false, &outb); if (rc) return rc;
+        // fused head: the last block's output exists only as the head's partial sums (32 floats per pixel instead of 128)
+        const bool to_head = i == 6 && head_fused_form(h);
+        if (to_head) { rc = dev_alloc(h, "ws.gen.head.partial", (size_t)B * r * r * 32, false, &outb); if (rc) return rc; }
+        else { snprintf(n, sizeof n, "ws.gen.rb%d.out", i); rc = dev_alloc(h, n, (size_t)B * r * r * f, false, &outb); if (rc) return rc; }
         snprintf(n, sizeof n, "ws.gen.rb%d.mean1", i); rc = dev_alloc(h, n, f, false, &m1); if (rc) return rc;
         snprintf(n, sizeof n, "ws.gen.rb%d.std1", i); rc = dev_alloc(h, n, f, false, &s1); if (rc) return rc;
         snprintf(n, sizeof n, "ws.gen.rb%d.meano", i); rc = dev_alloc(h, n, f, false, &mo); if (rc) return rc;
@@ -213,8 +216,9 @@ static int plan_spade(msr_handle* h) {
             snprintf(k, sizeof k, "gen.rb%d.conv_%d.kernel", i, j);
             Op cv = conv_op(ab, C, need(k), cb, B, r, f, 1, epi, sf.cv);
             cv.conv.wexp = wexp(k, sf.cv);
-            set_out_dense(cv.conv, y, r, r, f);
-            if (epi == EPI_RES) set_aux_dense(cv.conv, res, res_r, f, res_shift);
+            if (epi == EPI_RES_HEAD) { set_out_dense(cv.conv, y, r, r, 32); cv.conv.mean = need("gen.head.wfrag"); }
+            else set_out_dense(cv.conv, y, r, r, f);
+            if (epi == EPI_RES || epi == EPI_RES_HEAD) set_aux_dense(cv.conv, res, res_r, f, res_shift);
             // fused output moments (the tensor feeds a SPADE layer) unless the layer runs split-K
             if (want_stats && cv.conv.ksplit == 1) cv.stat_slabs = conv_stat_slabs(cv.conv, cv.tile);
             h->ops.push_back(cv);
@@ -241,16 +245,25 @@ static int plan_spade(msr_handle* h) {
             // skip = conv_3(lrelu(spade_3(x)))                             blocks.py:33-34
             rc = spade_then_conv(3, x_prev, r_prev, shift, cin, st_mean, st_std, skip, EPI_BIAS, nullptr, 0, 0, false); if (rc) return rc;
             // out = skip + conv_2(lrelu(spade_2(x1)))                      blocks.py:31-32,38
-            rc = spade_then_conv(2, x1, r, 0, f, m1, s1, outb, EPI_RES, skip, r, 0, true); if (rc) return rc;
+            rc = spade_then_conv(2, x1, r, 0, f, m1, s1, outb, to_head ? EPI_RES_HEAD : EPI_RES, skip, r, 0, !to_head); if (rc) return rc;
         } else {
             // out = x + conv_2(lrelu(spade_2(x1))), x read through the folded up-sample
-            rc = spade_then_conv(2, x1, r, 0, f, m1, s1, outb, EPI_RES, x_prev, r_prev, shift, true); if (rc) return rc;
+            rc = spade_then_conv(2, x1, r, 0, f, m1, s1, outb, to_head ? EPI_RES_HEAD : EPI_RES, x_prev, r_prev, shift, !to_head);
+            if (rc) return rc;
+        }
+        if (to_head) {     // nothing reads the block output or its moments: the gather finishes the head from the partial sums
+            Op hg; hg.type = OP_HEAD_GATHER; hg.out_is_output = true;
+            hg.hg = {outb, h->host_small["gen.head.bias"][0], B, r};
+            hg.flops = 2.0 * B * S * S * 16.0 * 128;      // the head's algorithmic count (its products ran in the conv's epilogue)
+            hg.bytes = (double)B * r * r * 32 * 4;
+            h->ops.push_back(hg);
+            break;
         }
         // moments of the block output == moments of its nearest-2x up-sample (every value is repeated 4x)
         push_moments(outb, B * r * r, f, mo, so);
         x_prev = outb; r_prev = r; cin = f; st_mean = mo; st_std = so;
     }
-    {
+    if (!head_fused_form(h)) {
         Op hd; hd.type = OP_HEAD; hd.out_is_output = true;
         hd.head = {x_prev, need("gen.head.weff"), h->host_small["gen.head.bias"][0], B, r_prev, 128, 0.2f, 0, 0, 0};
         hd.flops = 2.0 * B * S * S * 16.0 * 128;

@@ -700,4 +700,46 @@ hipError_t launch_head(const float* x, const float* weff, float bias, float* out
     return hipGetLastError();
 }
 
+// ------------------------------------------------------------------------------------------------
+// head_gather: the second half of the fused SPADE head (kernels.h HEAD_SLOTS).  The last residual conv has written the
+// partial sums P[B, r, r, 32] of every half-resolution pixel; one thread = one such pixel = a 2 x 2 block of outputs sums the
+// live slots of its 3 x 3 neighbourhood's lines — rows dy = 0..2, columns dx = 0..2 in that order, the bias last, as
+// head_kernel — with zeros outside the image (never the neighbouring sample's lines).  No tanh, no slope: the SPADE head only.
+// HBM-bound on P (32 floats per pixel instead of head_kernel's 128); the neighbours' lines come from L2.
+// ------------------------------------------------------------------------------------------------
+__global__ void __launch_bounds__(256) head_gather_kernel(const float* __restrict__ P, float bias, float* __restrict__ out,
+                                                          int B, int r) {
+    const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
+    const int tiles = r >> 4;
+    int t = blockIdx.x;
+    const int x = ((t % tiles) << 4) + tx;
+    t /= tiles;
+    const int y = ((t % tiles) << 4) + ty;
+    const int b = t / tiles;
+    float o00 = 0.f, o01 = 0.f, o10 = 0.f, o11 = 0.f;
+#pragma unroll
+    for (int dy = 0; dy < 3; ++dy)
+#pragma unroll
+        for (int dx = 0; dx < 3; ++dx) {
+            const int yy = y + dy - 1, xx = x + dx - 1;
+            if (yy < 0 || yy >= r || xx < 0 || xx >= r) continue;
+            const float* line = P + (((size_t)b * r + yy) * r + xx) * 32;
+            o00 += line[head_slot(0, 0, dy, dx)];
+            if (dx > 0) o01 += line[head_slot(0, 1, dy, dx)];
+            if (dy > 0) o10 += line[head_slot(1, 0, dy, dx)];
+            if (dy > 0 && dx > 0) o11 += line[head_slot(1, 1, dy, dx)];
+        }
+    o00 += bias; o01 += bias; o10 += bias; o11 += bias;
+    const int S2 = 2 * r;
+    float* ob = out + ((size_t)b * S2 + 2 * y) * S2 + 2 * x;
+    *reinterpret_cast<float2*>(ob) = make_float2(o00, o01);
+    *reinterpret_cast<float2*>(ob + S2) = make_float2(o10, o11);
+}
+
+hipError_t launch_head_gather(const float* partial, float bias, float* out, int B, int r, hipStream_t s) {
+    if (r < 16 || r % 16 || B < 1) return hipErrorInvalidValue;
+    head_gather_kernel<<<B * (r / 16) * (r / 16), 256, 0, s>>>(partial, bias, out, B, r);
+    return hipGetLastError();
+}
+
 }  // namespace msr

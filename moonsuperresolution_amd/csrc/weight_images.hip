@@ -78,6 +78,34 @@ std::vector<float> head_weff_upconv(const float* k44c, int C) {
                 }
     return weff;
 }
+// The head's effective taps as A operands of v_mfma_f32_16x16x32_f16 for the head epilogue of conv_igemm_f16c_sw (conv_sw.hip
+// sw_epilogue_head), C = 128: [wave 4][slot block 2][hi | lo][lane 64] x 8 fp16 = 16 KB.  Lane (s = lane & 15, cg = lane >> 4)
+// holds slot 16 sb + s (kernels.h HEAD_SLOTS, zero from slot 25 on) at the lane's 8 K positions, K position e = channel
+// 64 (wave >> 1) + 16 (wave & 1) + 32 (e >> 2) + 4 cg + (e & 3): the order in which the wave's accumulators hold a pixel.
+std::vector<float> build_head_wfrag(const float* k44c) {
+    constexpr int C = 128;
+    const std::vector<float> weff = head_weff_upconv(k44c, C);
+    std::vector<float> img(4096, 0.f);
+    uint16_t* const t = reinterpret_cast<uint16_t*>(img.data());
+    for (int py = 0; py < 2; ++py)
+        for (int px = 0; px < 2; ++px)
+            for (int dy = py; dy < 3; ++dy)
+                for (int dx = px; dx < 3; ++dx) {
+                    const int slot = head_slot(py, px, dy, dx), sb = slot >> 4, s = slot & 15;
+                    const float* src = &weff[((((size_t)py * 2 + px) * 3 + dy) * 3 + dx) * C];
+                    for (int w = 0; w < 4; ++w)
+                        for (int cg = 0; cg < 4; ++cg)
+                            for (int e = 0; e < 8; ++e) {
+                                const int c = 64 * (w >> 1) + 16 * (w & 1) + 32 * (e >> 2) + 4 * cg + (e & 3);
+                                unsigned hi, lo;
+                                msr_split_f16(src[c], hi, lo);
+                                const int lane = 16 * cg + s;
+                                t[(((w * 2 + sb) * 2 + 0) * 64 + lane) * 8 + e] = (uint16_t)hi;
+                                t[(((w * 2 + sb) * 2 + 1) * 64 + lane) * 8 + e] = (uint16_t)lo;
+                            }
+                }
+    return img;
+}
 std::vector<float> head_weff_transpose(const float* k44c, int C) {
     static const int kmap[2][2] = {{3, 1}, {2, 0}};
     std::vector<float> weff((size_t)36 * C, 0.f);

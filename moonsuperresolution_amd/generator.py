@@ -125,24 +125,34 @@ class Generator:
             stream kernel, same parity grade; the measured A/B is in DESIGN.md).  "fp6" goes with precision="f16c", or with
             "auto", which keeps it when it stays on f16c and drops it (``.cross`` reads "fp8", ``.range`` says so) when it
             falls back to bf16x3.
+        head: "separate" (default) or "fused" (opt-in, MSR_FLAG_FUSED_HEAD): the last residual conv emits the head's partial
+            sums (32 floats per pixel) instead of its 128-channel output and a gather kernel finishes the head.  It goes with
+            precision="f16c" and cross="fp8", or with "auto", which keeps it on f16c and drops it with a note in ``.range`` on
+            bf16x3.  The plan takes it where that conv runs the stream kernel on whole tiles (``head_fused``); at smaller
+            shapes the separate head runs.  Activations beyond fp16's 65504 saturate in the fused head (include/moonsr.h).
         calibrate: the batch [batch_size, S, S, 2] "auto" calibrates on; None = ``synthetic_patches(batch_size, S, seed=0)``.
             Calibration holds for the data it saw: ``DEMSuperResolution(range_check=...)`` checks real tiles.
     """
 
     def __init__(self, image_size: int, batch_size: int, latent_dim: int = 256, variant: str = "gaugan",
                  weights: Union[int, Mapping[str, np.ndarray]] = 1234, eps: Union[None, int, np.ndarray] = None,
-                 device: int = 0, precision: str = "f16c", calibrate=None, cross: str = "fp8"):
+                 device: int = 0, precision: str = "f16c", calibrate=None, cross: str = "fp8", head: str = "separate"):
         if variant not in VARIANTS:
             raise ValueError(f"unknown variant {variant!r}; expected one of {VARIANTS}")
         if cross not in _lib.CROSS_FLAGS:
             raise ValueError(f"unknown cross {cross!r}; expected one of {tuple(_lib.CROSS_FLAGS)}")
         if cross != "fp8" and precision not in ("f16c", "auto"):
             raise ValueError(f"cross={cross!r} is an option of precision='f16c' (or 'auto'), not of {precision!r}")
+        if head not in _lib.HEAD_FLAGS:
+            raise ValueError(f"unknown head {head!r}; expected one of {tuple(_lib.HEAD_FLAGS)}")
+        if head != "separate" and (precision not in ("f16c", "auto") or cross != "fp8" or variant == "pix2pix"):
+            raise ValueError(f"head={head!r} is an option of precision='f16c' (or 'auto') with cross='fp8' on the SPADE variants, "
+                             f"not of precision={precision!r}, cross={cross!r}, variant={variant!r}")
         if precision == "auto":
             # resolved here, above the flag table: try the fast default, keep it only in the parity regime
             if isinstance(weights, (int, np.integer)):
                 weights = make_weights(variant, image_size, latent_dim, seed=int(weights))
-            self.__init__(image_size, batch_size, latent_dim, variant, weights, eps, device, "f16c", cross=cross)
+            self.__init__(image_size, batch_size, latent_dim, variant, weights, eps, device, "f16c", cross=cross, head=head)
             if calibrate is None:
                 from .weights import synthetic_patches
                 calibrate = synthetic_patches(batch_size, image_size, seed=0)
@@ -154,12 +164,15 @@ class Generator:
                 self.__init__(image_size, batch_size, latent_dim, variant, weights, eps, device, "bf16x3")
                 if cross != "fp8":
                     report.note = f"cross={cross!r} dropped: it is an option of f16c, and this generator runs bf16x3"
+                if head != "separate":
+                    report.note = f"head={head!r} dropped: it is an option of f16c, and this generator runs bf16x3"
             self.range = report
             return
         if precision not in _lib.PRECISION_FLAGS:
             raise ValueError(f"unknown precision {precision!r}; expected one of {tuple(_lib.PRECISION_FLAGS) + ('auto',)}")
         self.precision = precision
         self.cross = cross
+        self.head = head
         self.range: Optional[RangeReport] = None
         self.image_size, self.batch_size, self.latent_dim, self.variant = image_size, batch_size, latent_dim, variant
         self._lib = _lib.load()
@@ -167,7 +180,7 @@ class Generator:
             raise RuntimeError("moonsuperresolution_amd needs a HIP device (MI355X / gfx950); there is no CPU fallback")
         self.device = torch.device("cuda", device)
         cfg = _lib.MsrConfig(image_size, batch_size, latent_dim, _lib.VARIANT_IDS[variant], device,
-                             _lib.PRECISION_FLAGS[precision] | _lib.CROSS_FLAGS[cross])
+                             _lib.PRECISION_FLAGS[precision] | _lib.CROSS_FLAGS[cross] | _lib.HEAD_FLAGS[head])
         handle = C.c_void_p()
         rc = self._lib.msr_create(C.byref(cfg), C.byref(handle))
         _lib.raise_for(self._lib, None, rc, "msr_create")
@@ -182,7 +195,7 @@ class Generator:
                 raise ValueError(f"eps must be [{batch_size}, {latent_dim}], got {e.shape}")
             self._eps_fixed = torch.from_numpy(e).to(self.device)
         self._ctor = dict(image_size=image_size, batch_size=batch_size, latent_dim=latent_dim, variant=variant,
-                          eps=eps, device=device, precision=precision, cross=cross)
+                          eps=eps, device=device, precision=precision, cross=cross, head=head)
         self._weights: Optional[Mapping[str, np.ndarray]] = None   # what the handle holds now (clone() re-uploads it)
         self.weights_version = 0                                    # bumped by every load(); the tiler's clones follow it
         if isinstance(weights, (int, np.integer)):
@@ -301,6 +314,12 @@ class Generator:
         rc = self._lib.msr_debug_conv_forms(self._h, buf, len(buf))
         _lib.raise_for(self._lib, self._h, rc, "msr_debug_conv_forms")
         return parse_conv_forms(buf.value.decode())
+
+    @property
+    def head_fused(self) -> bool:
+        """Whether the plan took ``head="fused"``: it holds the gather op (the separate head runs at shapes where the last
+        residual conv does not run the stream kernel on whole tiles)."""
+        return any(op.get("kind") == "head_gather" for op in self.conv_forms())
 
     # -- activation ranges -----------------------------------------------------------------------------
     def range_scan_async(self) -> None:

@@ -9,6 +9,7 @@ import torch
 from . import _lib
 
 EPI_BIAS, EPI_RES, EPI_SPADE = 0, 1, 2
+EPI_RES_HEAD = 5        # the stream kernel's residual epilogue that emits the head's partial sums (csrc/kernels.h)
 TILE_128, TILE_64, TILE_128_K16, TILE_HALO, TILE_HALO16, TILE_PP, TILE_FRAG, TILE_F16X2 = 0, 1, 2, 3, 4, 5, 0x40, 0x80
 
 
@@ -422,20 +423,85 @@ def gbr_embed_image(we_hwio: torch.Tensor) -> torch.Tensor:
     return v.contiguous().view(torch.int16).reshape(-1).view(torch.float32).clone()
 
 
-def head_taps_upconv(k44c: torch.Tensor) -> torch.Tensor:
+def head_taps_upconv(k44c: torch.Tensor, dtype=torch.float32) -> torch.Tensor:
     """Head kernel [4, 4, C] (Conv2D(1, 4, 'same') after UpSampling2D(2), networks.py:54-56) -> the effective per-parity taps
     weff[py][px][dy + 1][dx + 1][C] the head kernel reads (weight_images.hip head_weff_upconv, uploaded as gen.head.weff): TF SAME for
     k = 4 pads 1 before / 2 after, so output parity p reads half-resolution offsets {-1, 0, 0, +1} (p = 0) or {0, 0, +1, +1}
-    (p = 1) for kh = 0..3; taps that land on the same pixel are added in fp32, in kh, kw order."""
-    k = k44c.float().cpu()
+    (p = 1) for kh = 0..3; taps that land on the same pixel are added in fp32 (``dtype``: float64 for a reference), in kh, kw
+    order."""
+    k = k44c.to(dtype).cpu()
     dmap = lambda parity, t: (0 if t == 0 else 2 if t == 3 else 1) if parity == 0 else (1 if t < 2 else 2)   # noqa: E731
-    weff = torch.zeros((2, 2, 3, 3, k.shape[2]), dtype=torch.float32)
+    weff = torch.zeros((2, 2, 3, 3, k.shape[2]), dtype=dtype)
     for py in range(2):
         for px in range(2):
             for kh in range(4):
                 for kw in range(4):
                     weff[py, px, dmap(py, kh), dmap(px, kw)] += k[kh, kw]
     return weff
+
+
+def head_slots() -> dict:
+    """Slot table of the fused head's partial sums (csrc/kernels.h HEAD_SLOTS): {(py, px, dy, dx): slot} for the 25 live
+    entries of ``head_taps_upconv``'s weff[py][px][dy][dx] (dy >= py and dx >= px), counted in py, px, dy, dx order; slots
+    25..31 of a line are zero."""
+    table, n = {}, 0
+    for py in range(2):
+        for px in range(2):
+            for dy in range(py, 3):
+                for dx in range(px, 3):
+                    table[(py, px, dy, dx)] = n
+                    n += 1
+    return table
+
+
+def head_partials(x: torch.Tensor, k44c: torch.Tensor) -> torch.Tensor:
+    """What the head epilogue computes, in the dtype of ``x`` [B, r, r, C] (host): P[b, y, x, slot] = sum_c weff[slot][c] *
+    leaky_relu(x[b, y, x, c], 0.2), 32 slots per pixel (``head_slots``), the coinciding taps summed in that dtype too."""
+    weff = head_taps_upconv(k44c, x.dtype)
+    a = torch.where(x >= 0, x, 0.2 * x)
+    P = torch.zeros(tuple(x.shape[:3]) + (32,), dtype=x.dtype)
+    for (py, px, dy, dx), s in head_slots().items():
+        P[..., s] = a @ weff[py, px, dy, dx]
+    return P
+
+
+def head_from_partials(P: torch.Tensor, bias: float) -> torch.Tensor:
+    """The gather of the fused head restated in torch, in the dtype of ``P`` [B, r, r, 32] (float32 or float64, host or
+    device): out[b, 2i + py, 2j + px] = bias + sum over the live (dy, dx) of P[b, i + dy - 1, j + dx - 1, slot(py, px, dy, dx)],
+    zero outside the image, summed in the kernel's order (dy, then dx, the bias last)."""
+    B, r = P.shape[0], P.shape[1]
+    pad = torch.zeros((B, r + 2, r + 2, 32), dtype=P.dtype, device=P.device)
+    pad[:, 1:-1, 1:-1] = P
+    out = torch.zeros((B, 2 * r, 2 * r), dtype=P.dtype, device=P.device)
+    slots = head_slots()
+    for py in range(2):
+        for px in range(2):
+            acc = torch.zeros((B, r, r), dtype=P.dtype, device=P.device)
+            for dy in range(py, 3):
+                for dx in range(px, 3):
+                    acc = acc + pad[:, dy:dy + r, dx:dx + r, slots[(py, px, dy, dx)]]
+            out[:, py::2, px::2] = acc + bias
+    return out
+
+
+def conv3x3_f16c_head(ctx: OpContext, x_img: torch.Tensor, w_img: torch.Tensor, wexp: torch.Tensor, bias: torch.Tensor, rout: int,
+                      aux: torch.Tensor, aux_shift: int, head_kernel: "np.ndarray", head_bias: float, want_partial: bool = False):
+    """The fused head at kernel level (msr_op_conv3x3_f16c_head): the f16c residual conv on the stream kernel with the head
+    epilogue, then the gather.  ``head_kernel`` [4, 4, 128] float32 (host).  Returns out [B, 2 rout, 2 rout], and with
+    ``want_partial`` also the partial sums [B, rout, rout, 32]."""
+    import numpy as np
+    B, Cin = x_img.shape[0], x_img.shape[3]
+    N = w_img.shape[1]
+    k = np.ascontiguousarray(head_kernel, dtype=np.float32)
+    assert k.shape == (4, 4, 128)
+    out = torch.zeros((B, 2 * rout, 2 * rout), dtype=torch.float32, device=x_img.device)
+    part = torch.zeros((B, rout, rout, 32), dtype=torch.float32, device=x_img.device) if want_partial else None
+    rc = ctx.lib.msr_op_conv3x3_f16c_head(ctx.h, x_img.data_ptr(), w_img.data_ptr(), wexp.data_ptr(), bias.data_ptr(), B, rout, Cin,
+                                          N, aux.data_ptr(), aux_shift, k.ctypes.data_as(C.c_void_p), float(head_bias),
+                                          out.data_ptr(), part.data_ptr() if want_partial else None,
+                                          torch.cuda.current_stream(x_img.device).cuda_stream)
+    _lib.raise_for(ctx.lib, ctx.h, rc, "msr_op_conv3x3_f16c_head")
+    return (out, part) if want_partial else out
 
 
 def heads_concat(mean: torch.Tensor, variance: torch.Tensor) -> torch.Tensor:

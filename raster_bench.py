@@ -83,6 +83,8 @@ def main():
                     help="pad and upload only the raster rows this rank's patches touch (distributed.input_rows) instead of "
                          "the whole raster; needs --halo or --gpus N")
     ap.add_argument("--precision", default="f16c")
+    ap.add_argument("--head", default="separate", choices=("separate", "fused"),
+                    help="fused: the last residual conv emits the head's partial sums (Generator(head=...), opt-in)")
     ap.add_argument("--pipeline", type=int, default=2)
     args = ap.parse_args()
     if args.crop_inputs and not (args.halo or args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
@@ -120,7 +122,7 @@ def main():
     S, s, B, T = args.image_size, args.stride, args.batch_size, args.tile_size
     t_setup = time.perf_counter()
     img, dem = synthetic_raster(args.rows, args.cols, seed=0)
-    gen = Generator(S, B, variant="gaugan", weights=1234, eps=7, device=local, precision=args.precision)
+    gen = Generator(S, B, variant="gaugan", weights=1234, eps=7, device=local, precision=args.precision, head=args.head)
     dsr = DEMSuperResolution(DSRConfig(image_size=S, stride=s, batch_size=B, tile_size=T), model=gen, device=local,
                              pipeline=args.pipeline)
     dsr.setImages(img, dem)
