@@ -159,6 +159,41 @@ int msr_graph_enable(msr_handle* h, int32_t on);
 /* Latent z [batch, latent] of the last msr_forward (debug / parity aid), copied to a device buffer. */
 int msr_last_latent(msr_handle* h, float* z_dev, void* stream);
 
+/* ---- sampler noise --------------------------------------------------------------------------- */
+/* Counter-based N(0,1) noise for eps_dev of msr_forward: eps_dev[b][l] (b < B, l < L, float32, 16-byte aligned) is a pure
+ * function of (seed, the id of row b, l) — not of B, of the row's position in the batch, of the stream or of earlier calls.
+ * Row b's id is the three uint32 words ids_dev[3b .. 3b+2] (device memory), or (first_row + b, 0, 0) when ids_dev is NULL
+ * (first_row is ignored otherwise).  Any B >= 1 and any L that is a positive multiple of 4 (B * L / 4 < 2^31), not only the
+ * handle's; the handle gives the device and carries the error text.  Asynchronous on `stream`: one small kernel, no
+ * allocation.  Replaces tf.random.normal (sampling.py:13) where a caller wants reproducible products: the tiler passes ids
+ * that name the patch occurrence, so the noise does not depend on ranks, row windows or stream pipelining.
+ *
+ * The recipe is part of the ABI (a change of it is a change of MSR_ABI_VERSION).  All arithmetic after the integer block is
+ * IEEE float32 with round-to-nearest + - * / and sqrt, one rounding per operation (no fused multiply-add), in exactly the
+ * order written; constants are float32 values written as C hex-float literals.
+ *   words    (w0, w1, w2, w3) = Philox4x32-10(counter = (l >> 2, id0, id1, id2), key = (seed & 0xFFFFFFFF, seed >> 32)),
+ *            multipliers 0xD2511F53 / 0xCD9E8D57, key increments 0x9E3779B9 / 0xBB67AE85, 10 rounds (Random123).
+ *   values   eps[b][4g + 0] = R(w0) * C(w1)    eps[b][4g + 1] = R(w0) * S(w1)          (g = l >> 2: Box-Muller, twice)
+ *            eps[b][4g + 2] = R(w2) * C(w3)    eps[b][4g + 3] = R(w2) * S(w3)
+ *   R(n)     = sqrt(-2 ln u), u = (n + 0.5) / 2^32:
+ *            lz = leading zeros of n (32 for n = 0);  t = ((2n + 1) << lz) >> 9  (64-bit integer; 2^23 <= t < 2^24);
+ *            m = float(t) * 0x1p-23;  e = -1 - lz;  if t >= 0xB504F4 { m = m * 0.5;  e = e + 1; }
+ *            s = (m - 1) / (m + 1);  s2 = s * s;
+ *            p = 0x1.c71c72p-4;  p = p * s2 + 0x1.24924ap-3;  p = p * s2 + 0x1.99999ap-3;  p = p * s2 + 0x1.555556p-2;
+ *            p = p * s2 + 1;  ln = float(e) * 0x1.62e43p-1 + (s + s) * p;  R = sqrt(-2 * ln)
+ *   C, S(n)  = cos, sin of 2 pi (n + 0.5) / 2^32:
+ *            o = n >> 29;  f = n & 0x1FFFFFFF;  if o is odd { f = 0x1FFFFFFF - f; }
+ *            a = float(((f >> 6) << 1) | 1) * 0x1p-24;  x = a * 0x1.921fb6p-1;  x2 = x * x;
+ *            q = 0x1.71de3ap-19;  q = q * x2 - 0x1.a01a02p-13;  q = q * x2 + 0x1.111112p-7;  q = q * x2 - 0x1.555556p-3;
+ *            sn = x + x * (x2 * q);
+ *            r = -0x1.27e4fcp-22;  r = r * x2 + 0x1.a01a02p-16;  r = r * x2 - 0x1.6c16c2p-10;  r = r * x2 + 0x1.555556p-5;
+ *            r = r * x2 - 0.5;  cs = 1 + x2 * r;
+ *            (C, S) = (sn, cs) if o is 1, 2, 5 or 6, else (cs, sn);  C = -C if o is 2, 3, 4 or 5;  S = -S if o >= 4.
+ * u lies in the open interval (0, 1), so every value is finite; |eps| <= sqrt(66 ln 2) = 6.77.
+ * moonsuperresolution_amd.ops.sampler_noise is the NumPy twin, equal bit for bit. */
+int msr_sampler_noise(msr_handle* h, uint64_t seed, const uint32_t* ids_dev, uint32_t first_row, float* eps_dev, int32_t B,
+                      int32_t L, void* stream);
+
 /* ---- tiler / stitcher ------------------------------------------------------------------------ */
 /* Replaces getPatch + normalize for a whole tile (process_full_tiles.py:269-311, 453-457).
  * For every patch origin (ox[i], oy[i]) (padded-canvas coordinates, int32 on device):

@@ -62,6 +62,7 @@ SYMBOLS = [
     ("msr_forward_gated", C.c_int, [_P, _P, _P, _P, C.c_int32, _P, _P]),
     ("msr_graph_enable", C.c_int, [_P, C.c_int32]),
     ("msr_last_latent", C.c_int, [_P, _P, _P]),
+    ("msr_sampler_noise", C.c_int, [_P, C.c_uint64, _P, C.c_uint32, _P, C.c_int32, C.c_int32, _P]),
     ("msr_patch_stats", C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, _P, C.c_int32, C.c_float, _P, _P, _P]),
     ("msr_extract_patches", C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, _P]),
     ("msr_compact_patches", C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P,

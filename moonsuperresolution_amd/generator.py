@@ -130,15 +130,32 @@ class Generator:
             precision="f16c" and cross="fp8", or with "auto", which keeps it on f16c and drops it with a note in ``.range`` on
             bf16x3.  The plan takes it where that conv runs the stream kernel on whole tiles (``head_fused``); at smaller
             shapes the separate head runs.  Activations beyond fp16's 65504 saturate in the fused head (include/moonsr.h).
+        sampler: where the "gaugan" sampler's noise comes from when ``eps`` is None — "torch" (default: ``torch.randn`` once per
+            call, as ``tf.random.normal``: it follows torch's global generator and the order of the calls) or "counter" (opt-in:
+            msr_sampler_noise fills a persistent [batch_size, latent_dim] device buffer before every call; row b's noise is a
+            pure function of ``seed`` and the row's id — ``forward_device(noise_ids=...)``, or (calls * batch_size + b, 0, 0)
+            from this instance's call counter, ``reset_sampler``).  Reproducible, independent of how calls are spread over
+            ranks, row windows and pipeline handles when the caller's ids are (the tiler's are), and the noise pointer never
+            changes, so ``use_graph`` replays.  "counter" goes with variant="gaugan" and eps=None.
+        seed: the 64-bit seed of sampler="counter".
         calibrate: the batch [batch_size, S, S, 2] "auto" calibrates on; None = ``synthetic_patches(batch_size, S, seed=0)``.
             Calibration holds for the data it saw: ``DEMSuperResolution(range_check=...)`` checks real tiles.
     """
 
     def __init__(self, image_size: int, batch_size: int, latent_dim: int = 256, variant: str = "gaugan",
                  weights: Union[int, Mapping[str, np.ndarray]] = 1234, eps: Union[None, int, np.ndarray] = None,
-                 device: int = 0, precision: str = "f16c", calibrate=None, cross: str = "fp8", head: str = "separate"):
+                 device: int = 0, precision: str = "f16c", calibrate=None, cross: str = "fp8", head: str = "separate",
+                 sampler: str = "torch", seed: int = 0):
         if variant not in VARIANTS:
             raise ValueError(f"unknown variant {variant!r}; expected one of {VARIANTS}")
+        if sampler not in ("torch", "counter"):
+            raise ValueError(f"unknown sampler {sampler!r}; expected 'torch' or 'counter'")
+        if sampler == "counter" and variant != "gaugan":
+            raise ValueError(f"sampler='counter' is the noise of variant='gaugan'; variant {variant!r} draws none")
+        if sampler == "counter" and eps is not None:
+            raise ValueError("sampler='counter' generates the noise of every call; it does not go with a fixed eps")
+        if not 0 <= int(seed) < 1 << 64:
+            raise ValueError(f"seed must be in [0, 2^64), got {seed}")
         if cross not in _lib.CROSS_FLAGS:
             raise ValueError(f"unknown cross {cross!r}; expected one of {tuple(_lib.CROSS_FLAGS)}")
         if cross != "fp8" and precision not in ("f16c", "auto"):
@@ -152,16 +169,19 @@ class Generator:
             # resolved here, above the flag table: try the fast default, keep it only in the parity regime
             if isinstance(weights, (int, np.integer)):
                 weights = make_weights(variant, image_size, latent_dim, seed=int(weights))
-            self.__init__(image_size, batch_size, latent_dim, variant, weights, eps, device, "f16c", cross=cross, head=head)
+            self.__init__(image_size, batch_size, latent_dim, variant, weights, eps, device, "f16c", cross=cross, head=head,
+                          sampler=sampler, seed=seed)
             if calibrate is None:
                 from .weights import synthetic_patches
                 calibrate = synthetic_patches(batch_size, image_size, seed=0)
             # the sampler noise of the calibration call: the fixed one if the caller gave one, else a seeded draw (repeatable)
-            noise = None if self._eps_fixed is not None else make_latent_noise(batch_size, latent_dim)
+            # (the counter sampler's own noise, from row 0: range_report)
+            noise = None if self._eps_fixed is not None or sampler == "counter" else make_latent_noise(batch_size, latent_dim)
             report = self.range_report(calibrate, eps=noise)
             if report.regime != "parity":
                 self.close()
-                self.__init__(image_size, batch_size, latent_dim, variant, weights, eps, device, "bf16x3")
+                self.__init__(image_size, batch_size, latent_dim, variant, weights, eps, device, "bf16x3", sampler=sampler,
+                              seed=seed)
                 if cross != "fp8":
                     report.note = f"cross={cross!r} dropped: it is an option of f16c, and this generator runs bf16x3"
                 if head != "separate":
@@ -194,8 +214,13 @@ class Generator:
             if e.shape != (batch_size, latent_dim):
                 raise ValueError(f"eps must be [{batch_size}, {latent_dim}], got {e.shape}")
             self._eps_fixed = torch.from_numpy(e).to(self.device)
+        self.sampler, self.seed = sampler, int(seed)
+        self._sampler_calls = 0                                     # calls that took their row ids from this counter
+        self._noise: Optional[torch.Tensor] = None                  # sampler="counter": the buffer every call's noise is written to
+        if sampler == "counter":
+            self._noise = torch.empty((batch_size, latent_dim), dtype=torch.float32, device=self.device)
         self._ctor = dict(image_size=image_size, batch_size=batch_size, latent_dim=latent_dim, variant=variant,
-                          eps=eps, device=device, precision=precision, cross=cross, head=head)
+                          eps=eps, device=device, precision=precision, cross=cross, head=head, sampler=sampler, seed=int(seed))
         self._weights: Optional[Mapping[str, np.ndarray]] = None   # what the handle holds now (clone() re-uploads it)
         self.weights_version = 0                                    # bumped by every load(); the tiler's clones follow it
         if isinstance(weights, (int, np.integer)):
@@ -205,7 +230,7 @@ class Generator:
     def clone(self) -> "Generator":
         """A second handle with the weights this handle holds NOW (the last ``load``, not the constructor's), its own
         workspace: for issuing independent calls on another stream, where the latency-bound head of one call overlaps
-        the matrix-bound tail of the other."""
+        the matrix-bound tail of the other.  Sampler and seed are the same; the clone's call counter starts at 0."""
         twin = Generator(weights=self._weights, **self._ctor)
         twin.weights_version = self.weights_version
         twin.range = self.range                  # an "auto" generator's clone is the chosen mode, not calibrated again
@@ -230,8 +255,13 @@ class Generator:
 
     # -- the call ------------------------------------------------------------------------------------
     def forward_device(self, batch: torch.Tensor, eps: Optional[torch.Tensor] = None,
-                       out: Optional[torch.Tensor] = None, gate: Optional[torch.cuda.Event] = None) -> torch.Tensor:
+                       out: Optional[torch.Tensor] = None, gate: Optional[torch.cuda.Event] = None,
+                       noise_ids: Optional[torch.Tensor] = None) -> torch.Tensor:
         """Device fast path: ``batch`` [B,S,S,2] float32 on this GPU -> [B,S,S,1] on the GPU (no host copy).
+
+        ``noise_ids`` (sampler="counter" only): int32 / uint32 [B, 3] on this GPU, contiguous — the id of every row's noise
+        (msr_sampler_noise); it is read on the current stream.  Without it the rows are (calls * B + b, 0, 0) of this
+        instance's call counter.  An explicit ``eps`` is used as given and draws nothing.
 
         Asynchronous on torch's current stream.  ``gate``: an event recorded at the end of the previous, independent
         call on another handle / stream — the matrix-bound part of this call waits for it, the latency-bound head
@@ -248,10 +278,16 @@ class Generator:
         if self.variant == "gaugan":
             if eps is None:
                 eps = self._eps_fixed
-            if eps is None:
+            if eps is None and self.sampler == "counter":
+                eps = self._fill_noise(noise_ids)
+                noise_ids = None
+            elif eps is None:
                 eps = torch.randn((B, self.latent_dim), dtype=torch.float32, device=self.device)
             eps = eps.to(device=self.device, dtype=torch.float32).contiguous()
             eps_ptr = eps.data_ptr()
+        if noise_ids is not None:
+            raise ValueError("noise_ids name the rows of sampler='counter' noise: this call draws none "
+                             f"(sampler={self.sampler!r}, variant={self.variant!r}, eps {'given' if eps is not None else 'None'})")
         stream = torch.cuda.current_stream(self.device).cuda_stream
         if gate is not None:
             rc = self._lib.msr_forward_gated(self._h, batch.data_ptr(), eps_ptr, out.data_ptr(), B, stream,
@@ -260,6 +296,29 @@ class Generator:
             rc = self._lib.msr_forward(self._h, batch.data_ptr(), eps_ptr, out.data_ptr(), B, stream)
         _lib.raise_for(self._lib, self._h, rc, "msr_forward")
         return out
+
+    def _fill_noise(self, noise_ids: Optional[torch.Tensor]) -> torch.Tensor:
+        """sampler="counter": write this call's noise into the persistent buffer on the current stream and return the buffer.
+        The previous call's latent kernel, earlier on the stream this handle's calls are issued on, has read it by then."""
+        B = self.batch_size
+        ids_ptr, first_row = None, 0
+        if noise_ids is not None:
+            if tuple(noise_ids.shape) != (B, 3) or noise_ids.dtype not in (torch.int32, torch.uint32) or \
+                    noise_ids.device != self.device or not noise_ids.is_contiguous():
+                raise ValueError(f"noise_ids must be a contiguous int32 / uint32 tensor of shape {(B, 3)} on {self.device}, got "
+                                 f"{noise_ids.dtype} {tuple(noise_ids.shape)} on {noise_ids.device}")
+            ids_ptr = noise_ids.data_ptr()
+        else:
+            first_row = (self._sampler_calls * B) & 0xFFFFFFFF
+            self._sampler_calls += 1
+        rc = self._lib.msr_sampler_noise(self._h, self.seed, ids_ptr, first_row, self._noise.data_ptr(), B, self.latent_dim,
+                                         torch.cuda.current_stream(self.device).cuda_stream)
+        _lib.raise_for(self._lib, self._h, rc, "msr_sampler_noise")
+        return self._noise
+
+    def reset_sampler(self, calls: int = 0) -> None:
+        """sampler="counter": set the call counter, so that the next call without ``noise_ids`` draws rows calls * B .. ."""
+        self._sampler_calls = int(calls)
 
     def __call__(self, batch, training: bool = False) -> np.ndarray:
         """``model(np.array(batch), training=False)`` of process_full_tiles.py:338.
@@ -350,12 +409,17 @@ class Generator:
     def range_report(self, batch=None, eps=None) -> RangeReport:
         """Which regime of the narrow formats the last call ran in (RangeReport).  With ``batch`` [B, S, S, 2] (``eps`` as the
         constructor's array form, for "gaugan"), one call is run on it first.  Modes without narrow tensors ("fp32", "bf16x3")
-        return an empty report whose regime is "parity"."""
+        return an empty report whose regime is "parity".  With sampler="counter" and no ``eps`` that call draws rows 0 .. B - 1
+        and leaves the call counter as it was."""
         with torch.cuda.device(self.device):
             if batch is not None:
                 x = torch.from_numpy(np.ascontiguousarray(np.asarray(batch), dtype=np.float32)).to(self.device)
                 e = None if eps is None else torch.from_numpy(np.ascontiguousarray(eps, dtype=np.float32)).to(self.device)
-                self.forward_device(x, eps=e)
+                calls, self._sampler_calls = self._sampler_calls, 0
+                try:
+                    self.forward_device(x, eps=e)
+                finally:
+                    self._sampler_calls = calls
             self.range_scan_async()
             return self.range_read()
 

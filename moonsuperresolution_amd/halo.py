@@ -88,10 +88,21 @@ class HaloShardedSuperResolution(DEMSuperResolution):
             nv, ncall = (int(v) for v in meta.cpu().tolist())
             self._range_retire()                      # range_check: the previous band's scan, read with this band's counts
             preds = torch.empty((max(ncall * B, 1), S, S), dtype=torch.float32, device=dev)
+            self.last_noise_ids = None                # [cap, 3] of the band just issued, with the counter sampler
             if self._gen is not None:
                 if self._gens is None:
                     self._make_pipeline()
                 batches = [torch.empty((B, S, S, 2), dtype=torch.float32, device=dev) for _ in self._gens]
+                ids = None
+                if self.counter_noise:
+                    # The noise follows the patch: id (canvas origin x, y, 0xFFFFFFFF), whatever band or batch it lands in;
+                    # the padding rows of the last call draw (slot, 0xFFFFFFFE, 0xFFFFFFFF).
+                    slot = torch.arange(cap, dtype=torch.int32, device=dev)
+                    live = slot < nv
+                    ids = torch.full((cap, 3), -1, dtype=torch.int32, device=dev)
+                    ids[:, 0] = torch.where(live, keys[:, 0], slot)
+                    ids[:, 1] = torch.where(live, keys[:, 1], torch.full_like(slot, -2))
+                self.last_noise_ids = ids
                 for ps in self._pstreams:
                     ps.wait_stream(cur)
                 for c in range(ncall):
@@ -101,12 +112,13 @@ class HaloShardedSuperResolution(DEMSuperResolution):
                                                      sx[c * B:].data_ptr(), sy[c * B:].data_ptr(),
                                                      mm_sel[c * B:].data_ptr(), B, batches[k].data_ptr(), self._stream())
                         _lib.raise_for(lib, h, rc, "msr_extract_patches")
-                        self._gens[k].forward_device(batches[k], out=preds[c * B:(c + 1) * B].unsqueeze(-1))
+                        self._gens[k].forward_device(batches[k], out=preds[c * B:(c + 1) * B].unsqueeze(-1),
+                                                     noise_ids=None if ids is None else ids[c * B:(c + 1) * B])
                         if c == 0:
                             self._range_enqueue(self._gens[k])
                 for ps in self._pstreams:
                     cur.wait_stream(ps)
-                    for t in batches + [preds, sx, sy, mm_sel]:
+                    for t in batches + [preds, sx, sy, mm_sel] + ([] if ids is None else [ids]):
                         t.record_stream(ps)
             else:
                 batch = torch.empty((B, S, S, 2), dtype=torch.float32, device=dev)

@@ -662,3 +662,129 @@ def range_scan(ctx: OpContext, img: torch.Tensor, fmt: int, B: int, r: int, chan
                                    torch.cuda.current_stream(img.device).cuda_stream)
     _lib.raise_for(ctx.lib, ctx.h, rc, "msr_op_range_scan")
     return range_stat_dict(rec)
+
+
+# ---- counter-based sampler noise (csrc/sampler.hip, include/moonsr.h msr_sampler_noise) ---------------------------------------
+def philox4x32_10(counter, key):
+    """Philox4x32-10 on uint32 arrays: ``counter`` [..., 4], ``key`` [..., 2] (broadcast against each other) -> [..., 4]."""
+    import numpy as np
+    c = np.asarray(counter).astype(np.uint32)
+    k = np.asarray(key).astype(np.uint32)
+    if c.shape[-1] != 4 or k.shape[-1] != 2:
+        raise ValueError(f"counter must be [..., 4] and key [..., 2], got {c.shape} and {k.shape}")
+    shape = np.broadcast_shapes(c.shape[:-1], k.shape[:-1])
+    c0, c1, c2, c3 = (np.broadcast_to(c[..., i], shape).astype(np.uint64) for i in range(4))
+    k0, k1 = (np.broadcast_to(k[..., i], shape).astype(np.uint64) for i in range(2))
+    mask = np.uint64(0xFFFFFFFF)
+    for _ in range(10):
+        p0, p1 = np.uint64(0xD2511F53) * c0, np.uint64(0xCD9E8D57) * c2       # 32 x 32 -> 64 bits: no overflow
+        c0, c1, c2, c3 = (p1 >> np.uint64(32)) ^ c1 ^ k0, p1 & mask, (p0 >> np.uint64(32)) ^ c3 ^ k1, p0 & mask
+        k0, k1 = (k0 + np.uint64(0x9E3779B9)) & mask, (k1 + np.uint64(0xBB67AE85)) & mask
+    return np.stack([c0, c1, c2, c3], axis=-1).astype(np.uint32)
+
+
+def _f32(hexfloat: str):
+    import numpy as np
+    return np.float32(float.fromhex(hexfloat))        # every constant of the recipe is a float32 written exactly
+
+
+def _clz32(n):
+    """Leading zeros of uint32 values (32 for 0), by binary search with shifts."""
+    import numpy as np
+    x = n.astype(np.uint32)
+    lz = np.zeros(x.shape, np.int32)
+    for sh in (16, 8, 4, 2, 1):
+        top_clear = (x >> np.uint32(32 - sh)) == 0
+        lz += np.where(top_clear, sh, 0).astype(np.int32)
+        x = np.where(top_clear, x << np.uint32(sh), x)
+    return lz + (x == 0)                              # all 32 shifted out: the value was 0
+
+
+def _sampler_radius(n):
+    """sqrt(-2 ln u), u = (n + 0.5) / 2^32, op for op as csrc/sampler.hip::radius (float32 throughout)."""
+    import numpy as np
+    one, half = np.float32(1.0), np.float32(0.5)
+    lz = _clz32(n)
+    t = ((((n.astype(np.uint64) << np.uint64(1)) | np.uint64(1)) << lz.astype(np.uint64)) >> np.uint64(9)).astype(np.uint32)
+    m = t.astype(np.float32) * _f32("0x1p-23")
+    e = -1 - lz
+    big = t >= np.uint32(0xB504F4)
+    m = np.where(big, m * half, m)
+    e = np.where(big, e + 1, e)
+    s = (m - one) / (m + one)
+    s2 = s * s
+    p = np.full(s.shape, _f32("0x1.c71c72p-4"), np.float32)
+    p = p * s2 + _f32("0x1.24924ap-3")
+    p = p * s2 + _f32("0x1.99999ap-3")
+    p = p * s2 + _f32("0x1.555556p-2")
+    p = p * s2 + one
+    lnm = (s + s) * p
+    ln = e.astype(np.float32) * _f32("0x1.62e43p-1") + lnm
+    return np.sqrt(np.float32(-2.0) * ln)
+
+
+def _sampler_cos_sin(n):
+    """(cos, sin) of 2 pi (n + 0.5) / 2^32, op for op as csrc/sampler.hip::cos_sin."""
+    import numpy as np
+    one, half = np.float32(1.0), np.float32(0.5)
+    octant = n >> np.uint32(29)
+    f = n & np.uint32(0x1FFFFFFF)
+    f = np.where((octant & np.uint32(1)) != 0, np.uint32(0x1FFFFFFF) - f, f)
+    a = (((f >> np.uint32(6)) << np.uint32(1)) | np.uint32(1)).astype(np.float32) * _f32("0x1p-24")
+    x = a * _f32("0x1.921fb6p-1")
+    x2 = x * x
+    ps = np.full(x.shape, _f32("0x1.71de3ap-19"), np.float32)
+    ps = ps * x2 - _f32("0x1.a01a02p-13")
+    ps = ps * x2 + _f32("0x1.111112p-7")
+    ps = ps * x2 - _f32("0x1.555556p-3")
+    sn = x + x * (x2 * ps)
+    pc = np.full(x.shape, _f32("-0x1.27e4fcp-22"), np.float32)
+    pc = pc * x2 + _f32("0x1.a01a02p-16")
+    pc = pc * x2 - _f32("0x1.6c16c2p-10")
+    pc = pc * x2 + _f32("0x1.555556p-5")
+    pc = pc * x2 - half
+    cs = one + x2 * pc
+    swap = (((octant + np.uint32(1)) >> np.uint32(1)) & np.uint32(1)) != 0
+    c = np.where(swap, sn, cs)
+    s = np.where(swap, cs, sn)
+    c = np.where((((octant + np.uint32(2)) >> np.uint32(2)) & np.uint32(1)) != 0, -c, c)
+    s = np.where((octant >> np.uint32(2)) != 0, -s, s)
+    return c, s
+
+
+def sampler_noise(seed: int, ids=None, B: Optional[int] = None, L: int = 256, first_row: int = 0):
+    """Host twin of msr_sampler_noise, bit for bit: the [B, L] float32 noise of rows whose ids are ``ids`` [B, 3] (any integer
+    type; values are taken modulo 2^32, so -1 is 0xFFFFFFFF) or, without ids, (first_row + b, 0, 0) for b < B."""
+    import numpy as np
+    if L < 4 or L % 4:
+        raise ValueError(f"L must be a positive multiple of 4, got {L}")
+    if ids is None:
+        if B is None:
+            raise ValueError("sampler_noise needs ids or B")
+        rows = (np.arange(B, dtype=np.uint64) + np.uint64(int(first_row) & 0xFFFFFFFF)) & np.uint64(0xFFFFFFFF)
+        ids = np.stack([rows, np.zeros_like(rows), np.zeros_like(rows)], axis=1)
+    ids = (np.asarray(ids).astype(np.int64) & 0xFFFFFFFF).astype(np.uint32)
+    if ids.ndim != 2 or ids.shape[1] != 3 or (B is not None and ids.shape[0] != B):
+        raise ValueError(f"ids must be [B, 3], got {ids.shape}")
+    B, G = ids.shape[0], L // 4
+    seed = int(seed) & 0xFFFFFFFFFFFFFFFF
+    counter = np.empty((B, G, 4), np.uint32)
+    counter[..., 0] = np.arange(G, dtype=np.uint32)[None, :]
+    counter[..., 1:] = ids[:, None, :]
+    w = philox4x32_10(counter, np.array([seed & 0xFFFFFFFF, seed >> 32], dtype=np.uint32))
+    c0, s0 = _sampler_cos_sin(w[..., 1])
+    c1, s1 = _sampler_cos_sin(w[..., 3])
+    r0, r1 = _sampler_radius(w[..., 0]), _sampler_radius(w[..., 2])
+    return np.stack([r0 * c0, r0 * s0, r1 * c1, r1 * s1], axis=-1).reshape(B, L).astype(np.float32)
+
+
+def sampler_noise_device(ctx: OpContext, seed: int, B: int, L: int, ids: Optional[torch.Tensor] = None, first_row: int = 0,
+                         out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """One launch of msr_sampler_noise on the current stream: ``ids`` int32 / uint32 [B, 3] on the device or None (then rows
+    first_row + b); fills and returns ``out`` (the first B * L floats of it) or a new [B, L] tensor."""
+    if out is None:
+        out = torch.empty((B, L), dtype=torch.float32, device=ctx.device)
+    rc = ctx.lib.msr_sampler_noise(ctx.h, int(seed), None if ids is None else ids.contiguous().data_ptr(), int(first_row),
+                                   out.data_ptr(), B, L, torch.cuda.current_stream(ctx.device).cuda_stream)
+    _lib.raise_for(ctx.lib, ctx.h, rc, "msr_sampler_noise")
+    return out

@@ -415,6 +415,11 @@ class DEMSuperResolution:
                 g.prepare()
             torch.cuda.synchronize(self.device)
 
+    @property
+    def counter_noise(self) -> bool:
+        """True when the model is a Generator with sampler="counter": the loops then name every row's noise (noise_ids)."""
+        return self._gen is not None and getattr(self._gen, "sampler", "torch") == "counter"
+
     def patchOrigins(self, px: int, py: int) -> np.ndarray:
         """[n, 2] int32 (xx, yy) in padded coordinates, generation order (process_full_tiles.py:453-454)."""
         S, s, T = self.image_size, self.stride, self.tile_size
@@ -460,6 +465,14 @@ class DEMSuperResolution:
             keys = torch.empty((cap, 2), dtype=torch.int32, device=dev)
             dmm = torch.empty((cap, 2), dtype=torch.float32, device=dev)
             meta = torch.empty(2, dtype=torch.int32, device=dev)
+            if self.counter_noise:
+                # Row d of the tile's compacted list draws the noise (d, px, py), padding rows of the last call included: the
+                # id names the tile (canvas coordinates) and the position in its compaction, nothing of this rank or run.
+                ids = torch.empty((cap, 3), dtype=torch.int32, device=dev)
+                ids[:, 0] = torch.arange(cap, dtype=torch.int32, device=dev)
+                ids[:, 1] = px
+                ids[:, 2] = py
+                st["noise_ids"] = ids
             stream = self._prep_stream.cuda_stream
             rc = lib.msr_patch_stats(h, self.img_padded.data_ptr(), self.dem_padded.data_ptr(), rows, cols,
                                      ox.data_ptr(), oy.data_ptr(), n, self.no_value, valid.data_ptr(),
@@ -489,6 +502,7 @@ class DEMSuperResolution:
         nv, ncall = (int(v) for v in st["meta_host"].tolist())
         total = ncall * B
         sx, sy, mm_sel = st["sx"], st["sy"], st["mm_sel"]
+        ids = st.get("noise_ids")                     # sampler="counter" only; None leaves every call as it always was
         self._last = (st["keys"], nv, ncall)
         self._last_calls = None
         with torch.cuda.device(dev):
@@ -514,7 +528,7 @@ class DEMSuperResolution:
                     ps.wait_event(st["event"])
                     if buf["free"] is not None:
                         ps.wait_event(buf["free"])
-                    for t in (sx, sy, mm_sel):
+                    for t in (sx, sy, mm_sel) + (() if ids is None else (ids,)):
                         t.record_stream(ps)
                 gated = self.gated and len(self._gens) > 1
                 for c in range(ncall):
@@ -525,7 +539,8 @@ class DEMSuperResolution:
                                                      mm_sel[c * B:].data_ptr(), B, batches[k].data_ptr(), self._stream())
                         _lib.raise_for(lib, h, rc, "msr_extract_patches")
                         self._gens[k].forward_device(batches[k], out=preds[c * B:(c + 1) * B].unsqueeze(-1),
-                                                     gate=self._gate if gated else None)
+                                                     gate=self._gate if gated else None,
+                                                     noise_ids=None if ids is None else ids[c * B:(c + 1) * B])
                         if c == 0:
                             self._range_enqueue(self._gens[k])
                         if gated:
