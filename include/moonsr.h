@@ -461,6 +461,10 @@ int msr_debug_moment_forms(msr_handle* h, char* out, int64_t cap);
  * GBR); smallcin and norm_act lines carry out_split.  Needs a plan (after the first msr_forward or msr_forward_flops).
  * NUL-terminated; MSR_ERR_INVALID when cap is too small. */
 int msr_debug_conv_forms(msr_handle* h, char* out, int64_t cap);
+/* Debug, read-only: the kernel a whole-tile (no K ranges) f16c launch of msr_op_conv3x3_f16c / of the plan goes to under this
+ * process's MSR_F16C_SW, by the launcher's own rule: 1 = the stream kernel (conv_sw.hip), 0 = the ping-pong kernel.
+ * cin in channels, epilogue 0 bias | 1 residual | 2 SPADE, out_mode as msr_op_conv3x3_f16c (0, 1, 4, 5). */
+int msr_debug_f16c_kernel(int32_t cin, int32_t epilogue, int32_t out_mode);
 /* ---- activation-range scan ------------------------------------------------------------------------ */
 /* The f16c family (MSR_FLAG_F16C, _F16_MAIN, _FP8, _GB_F16X2) stores the inputs of the big convs in narrow pieces with finite
  * ranges; tests/test_gpu_conv_kernel.py::test_f16c_saturation_regimes states the three regimes of one activation a:

@@ -503,6 +503,14 @@ static hipError_t launch_pp_epi(const ConvParams& p, const TileGeom& g, int epi,
     return hipGetLastError();
 }
 
+// conv_sw.hip (one software-pipelined wave per SIMD) takes the long-K main convs; the gamma|beta convs stay here, where
+// a second wave on the SIMD hides their SPADE epilogue.  MSR_F16C_SW = 0: everything here, 2: everything there (A/B).
+bool f16c_whole_tile_on_stream(int Cin, int epi, int out_split) {
+    static const int sw_mode = env_int("MSR_F16C_SW", 1);
+    return Cin % 128 == 0 && !(epi == EPI_SPADE && out_split == OUT_F16C6) &&     // (the fp6 image is written by this kernel's epilogue only)
+           (sw_mode == 2 || (sw_mode == 1 && epi != EPI_SPADE));
+}
+
 hipError_t launch_pp(const ConvParams& p, int epi, hipStream_t s) {
     TileGeom g;
     if (!make_geom(p, 256, 128, 32, g)) return hipErrorInvalidValue;
@@ -535,12 +543,7 @@ hipError_t launch_pp(const ConvParams& p, int epi, hipStream_t s) {
     }
     if (p.prec == PREC_F16C) {
         if (!p.wexp) return hipErrorInvalidValue;
-        // conv_sw.hip (one software-pipelined wave per SIMD) takes the long-K main convs; the gamma|beta convs stay here, where
-        // a second wave on the SIMD hides their SPADE epilogue.  MSR_F16C_SW = 0: everything here, 2: everything there (A/B).
-        static const int sw_mode = env_int("MSR_F16C_SW", 1);
-        if (p.Cin % 128 == 0 && !(epi == EPI_SPADE && p.out_split == OUT_F16C6) &&     // (the fp6 image is written by this kernel's epilogue only)
-            (sw_mode == 2 || (sw_mode == 1 && epi != EPI_SPADE)))
-            return launch_conv_f16c_sw(p, epi, s);
+        if (f16c_whole_tile_on_stream(p.Cin, epi, p.out_split)) return launch_conv_f16c_sw(p, epi, s);
         return launch_pp_epi<PP_F16C>(p, g, epi, grid, s);
     }
     if (p.prec == PREC_FP8) {

@@ -148,6 +148,10 @@ int msr_debug_conv_forms(msr_handle* h, char* out, int64_t cap) {
     return MSR_OK;
 }
 
+int msr_debug_f16c_kernel(int32_t cin, int32_t epilogue, int32_t out_mode) {
+    return f16c_whole_tile_on_stream(cin, epilogue, epilogue == EPI_SPADE ? out_mode : OUT_F32) ? 1 : 0;
+}
+
 int msr_range_scan(msr_handle* h, void* stream) {
     if (!h) return MSR_ERR_INVALID;
     if (!h->forward_seen) return fail(h, MSR_ERR_STATE, "msr_range_scan: no msr_forward has run on this handle yet");

@@ -347,6 +347,8 @@ hipError_t conv_igemm_init();   // sets dynamic-LDS attributes once
 // 2 sends the gamma|beta convs there too (A/B runs)
 hipError_t conv_sw_init();
 hipError_t launch_conv_f16c_sw(const ConvParams& p, int epilogue, hipStream_t s);
+// launch_pp's rule for a whole-tile PREC_F16C launch under the process's MSR_F16C_SW: true = the stream kernel takes it
+bool f16c_whole_tile_on_stream(int Cin, int epilogue, int out_split);
 hipError_t launch_conv_igemm(const ConvParams& p, int epilogue, int tile, hipStream_t s);
 // picks the tile and the K split for a problem size (fills the chip for the low-resolution layers)
 int conv_pick_tile(int M, int N, int epilogue, int prec, int ksteps = 0);

@@ -337,6 +337,79 @@ def f16c6_decode(img: torch.Tensor):
     return hi, piece(64), piece(96)
 
 
+# ---- host twins of "the kernel was handed this scale": one output channel's e8m0 bytes moved, the decoded parts rescaled ----
+def _check_e8m0(b: torch.Tensor, what: str):
+    if int(b.min()) < 1 or int(b.max()) > 254:
+        raise ValueError(f"{what}: a shifted scale byte leaves e8m0's finite range [1, 254]")
+
+
+def _rescale_row(part: torch.Tensor, channel: int, d: int) -> torch.Tensor:
+    out = part.clone()
+    out[:, channel] = out[:, channel] * 2.0 ** d          # a power of two: exact
+    return out
+
+
+def f16c_weight_decode(w_img: torch.Tensor, wexp: torch.Tensor):
+    """f16c weight image [taps][N][Cin] + wexp [N] -> (hi, h8, lo8) float64, as the kernels read them: bytes 64..95 of a chunk
+    are the e4m3 codes of the lo piece (scale = byte 0 of wexp[n]), bytes 96..127 of the hi piece (scale = byte 1)."""
+    shp = w_img.shape
+    n = shp[-1] // 32
+    b = w_img.contiguous().view(torch.uint8).reshape(shp[:-1] + (n, 128))
+    hi = b[..., 0:64].contiguous().view(torch.float16).reshape(shp).double()
+    l8 = b[..., 64:96].contiguous().view(torch.float8_e4m3fn).reshape(shp).double()
+    h8 = b[..., 96:128].contiguous().view(torch.float8_e4m3fn).reshape(shp).double()
+    e = wexp.to(torch.int64).to(w_img.device)
+    sl, sh = _pow2((e & 255) - 127)[None, :, None], _pow2(((e >> 8) & 255) - 127)[None, :, None]
+    return hi, h8 * sh, l8 * sl
+
+
+def f16c_shift_wexp(wexp: torch.Tensor, wparts, channel: int, d_lo: int, d_hi: int):
+    """A copy of ``wexp`` (f16c_weight_image) with the two e8m0 bytes of ONE output channel moved by d_lo / d_hi binades (byte 0
+    = 127 + el scales the w_lo pieces, byte 1 = 127 + eh the w_h8 pieces), and the de-quantised (hi, h8, lo8) parts rescaled to
+    match: what a kernel that is handed these scales must compute."""
+    e = wexp.to(torch.int64).clone()
+    lo, hi = (e[channel] & 255) + d_lo, ((e[channel] >> 8) & 255) + d_hi
+    _check_e8m0(torch.stack([lo, hi]), "f16c_shift_wexp")
+    e[channel] = (e[channel] & ~0xFFFF) | lo | (hi << 8)
+    wh, w8, wl = wparts
+    return e.to(torch.int32), (wh, _rescale_row(w8, channel, d_hi), _rescale_row(wl, channel, d_lo))
+
+
+def f16c6_weight_decode(w_img: torch.Tensor):
+    """f16c6 weight image -> (hi, h6, l6) float64 (the lo piece is stored first: f16c6_weight_image)."""
+    hi, first, second = f16c6_decode(w_img)
+    return hi, second, first
+
+
+def f16c6_shift_wscale(w_img: torch.Tensor, wparts, channel: int, d_lo: int, d_hi: int):
+    """The same for the f16c6 weight image, whose scales ride inside it: byte 88 (lo piece) and byte 120 (hi piece) of every
+    128-byte chunk of weight row ``channel``, all taps.  Returns (image copy, rescaled (hi, h6, l6))."""
+    shp = w_img.shape
+    b = w_img.contiguous().view(torch.uint8).reshape(shp[0], shp[1], shp[2] // 32, 128).clone()
+    lo, hi = b[:, channel, :, 88].to(torch.int64) + d_lo, b[:, channel, :, 120].to(torch.int64) + d_hi
+    _check_e8m0(torch.stack([lo, hi]), "f16c6_shift_wscale")
+    b[:, channel, :, 88], b[:, channel, :, 120] = lo.to(torch.uint8), hi.to(torch.uint8)
+    wh, w6, wl = wparts
+    return (b.reshape(shp[0], shp[1], -1).view(torch.float32).reshape(shp),
+            (wh, _rescale_row(w6, channel, d_hi), _rescale_row(wl, channel, d_lo)))
+
+
+def fp8_weight_decode(w_bytes: torch.Tensor, wexp: torch.Tensor, cin: int) -> torch.Tensor:
+    """fp8 weight image [taps][N][Cpad] uint8 + wexp [N] -> de-quantised float64 weights [taps][N][cin] (scale = byte 0)."""
+    e = wexp.to(torch.int64).to(w_bytes.device)
+    return w_bytes[:, :, :cin].contiguous().view(torch.float8_e4m3fn).double() * _pow2((e & 255) - 127)[None, :, None]
+
+
+def fp8_shift_wexp(wexp: torch.Tensor, wdq: torch.Tensor, channel: int, d: int):
+    """The same for fp8_weight_image's wexp: the four equal e8m0 bytes of ONE channel moved by d binades."""
+    e = wexp.to(torch.int64).clone() & 0xFFFFFFFF
+    b = (e[channel] & 255) + d
+    _check_e8m0(b.reshape(1), "fp8_shift_wexp")
+    e[channel] = b | (b << 8) | (b << 16) | (b << 24)
+    e = torch.where(e >= 2 ** 31, e - 2 ** 32, e)
+    return e.to(torch.int32), _rescale_row(wdq, channel, d)
+
+
 F16C_NO_CROSS = 0x10000     # msr_op_conv3x3_f16c out_mode bit: MSR_FLAG_F16_MAIN's form (x_hi * w_hi only, stream kernel)
 
 

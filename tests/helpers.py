@@ -2,6 +2,20 @@
 import numpy as np
 
 
+def record_dir():
+    """The repository's directory for run records (where the GPU parity tests append their jsonl lines): the `*_out/` entry of
+    .gitignore."""
+    import os
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    try:
+        for line in open(os.path.join(root, ".gitignore")):
+            if line.strip().endswith("_out/"):
+                return os.path.join(root, line.strip().rstrip("/"))
+    except OSError:
+        pass
+    return os.path.join(root, "run_out")
+
+
 def rel_linf(a, b):
     """Relative L-infinity error used for every floating-point parity statement: max|a-b| / max|b|."""
     a = np.asarray(a, np.float64)
@@ -148,3 +162,96 @@ def dense_kch(K, N):
     while kch > 16 and gx * ((K + kch - 1) // kch) < 1024:
         kch >>= 1
     return kch
+
+
+def rel_linf_per_channel(a, b):
+    """One entry per last-dimension channel: max over pixels |a - b| / max over pixels |b| (float64; numpy arrays or torch
+    tensors on any device).  A channel whose reference is identically zero reports inf if ``a`` is not zero there (0 if it
+    is): no epsilon in the denominator, which would hide such a channel."""
+    import torch
+    a = torch.as_tensor(a).double()
+    b = torch.as_tensor(b).double().to(a.device)
+    C = b.shape[-1]
+    err = (a - b).abs().reshape(-1, C).amax(0)
+    den = b.abs().reshape(-1, C).amax(0)
+    out = torch.where(den > 0, err / den.clamp_min(1e-300), torch.where(err > 0, torch.full_like(err, float("inf")),
+                                                                        torch.zeros_like(err)))
+    return out.cpu().numpy()
+
+
+def conv_channel_inputs(B, r, cin, cout, seed, res=None, x_decades=None):
+    """Operands for the per-channel conv tests (host tensors): x, w and skip as tests/test_gpu_conv_kernel.py::test_conv_f16c
+    builds them (weights spanning three decades over the output channels; ``x_decades`` = (lo, hi): x scaled over its input
+    channels as test_conv_f16c6 does), and a bias scaled like its channel (randn * logspace), so that every channel's reference
+    magnitude is set by its own weights.  res: the residual's aux_shift (None: no skip)."""
+    import torch
+    g = torch.Generator(device="cpu").manual_seed(seed)
+    ls = torch.logspace(-2, 1, cout)
+    x = torch.randn((B, r, r, cin), generator=g)
+    if x_decades is not None:
+        x = x * torch.logspace(x_decades[0], x_decades[1], cin)
+    w = torch.randn((3, 3, cin, cout), generator=g) / np.sqrt(9 * cin) * ls
+    b = torch.randn(cout, generator=g) * ls
+    skip = torch.randn((B, r >> res, r >> res, cout), generator=g) if res is not None else None
+    return x, w, b, skip
+
+
+def f16c_terms(xparts_pad, wparts, r, dtype=None, terms=(True, True, True)):
+    """The f16c family's three terms on de-quantised operands, on whatever device they live, summed in ``dtype`` (float64, or
+    float32 = plain fp32 accumulation): x_hi * w_hi + x_h * w_lo + x_lo * w_h.  xparts_pad: zero-bordered [B, r + 2, r + 2, C]
+    (hi, h, lo) pieces; wparts [9][N][C] (hi, h, lo); ``terms`` switches a term off."""
+    (xh, x8, xl), (wh, w8, wl) = xparts_pad, wparts
+    y = conv_taps(xh, wh, r, dtype=dtype) if terms[0] else 0
+    if terms[1]:
+        y = y + conv_taps(x8, wl, r, dtype=dtype)
+    if terms[2]:
+        y = y + conv_taps(xl, w8, r, dtype=dtype)
+    return y
+
+
+def persistent_item_rounds(items, n_cu):
+    """Host restatement of persistent_grid + xcd_tile_range (csrc/conv_igemm.hip, conv_common.h): for each logical work item
+    0..items-1 of a persistent conv launch on a device with ``n_cu`` compute units, (slot, round): the position of its
+    workgroup inside the XCD's range and how many items that workgroup took before it (round >= 1: the workgroup has moved to
+    another tile).  Workgroup (xcd, slot) takes items base + slot + k * slots of the XCD's range [base, base + cnt)."""
+    n_cu = max(n_cu & ~7, 8)
+    grid = (items + 7) & ~7 if items < n_cu else n_cu
+    slots, tq, tr = grid >> 3, items >> 3, items & 7
+    out = np.zeros((items, 2), np.int64)
+    for xcd in range(8):
+        cnt = tq + (1 if xcd < tr else 0)
+        base = xcd * (tq + 1) if xcd < tr else tr * (tq + 1) + (xcd - tr) * tq
+        for i in range(cnt):
+            out[base + i] = (i % slots, i // slots)
+    return out
+
+
+def conv_walk_item(t, tiles_m, tiles_n, walk=True):
+    """Host restatement of conv_walk_pick + MSR_WALK (csrc/conv_igemm.hip, kernels.h): logical tile t -> (channel block,
+    pixel tile).  ``walk=False``: channel block fastest (launches that do not call conv_walk)."""
+    pb, nb = (8, 4) if walk and tiles_n > 4 and tiles_n % 4 == 0 and tiles_m % 8 == 0 else (1, tiles_n)
+    grp, sub = pb * tiles_n, pb * nb
+    blk, rem = divmod(t, grp)
+    ng, j = divmod(rem, sub)
+    jp = j // nb
+    return ng * nb + (j - jp * nb), blk * pb + jp
+
+
+def later_round_mask(B, r, N, n_cu, walk=True, pick=None, new_block=False):
+    """bool [B, r // 16, r // 16, N // 128]: the (16 x 16 pixel tile, 128-channel block) items of a whole-tile persistent conv
+    launch that ``pick(slot, round)`` selects (default: round >= 1, the items a workgroup computes after its first one).
+    ``new_block``: of those, only the items whose channel block differs from that of the workgroup's previous item (item
+    t - slots of the same XCD range): the ones for which the workgroup must really re-read its scales and bias."""
+    ty = r // 16
+    tiles_m, tiles_n = B * ty * ty, N // 128
+    items = tiles_m * tiles_n
+    slots = min((items + 7) & ~7, max(n_cu & ~7, 8)) >> 3
+    pick = pick or (lambda slot, rnd: rnd >= 1)
+    mask = np.zeros((B, ty, ty, tiles_n), bool)
+    for t, (slot, rnd) in enumerate(persistent_item_rounds(items, n_cu)):
+        if pick(slot, rnd):
+            tn, tmi = conv_walk_item(t, tiles_m, tiles_n, walk)
+            if new_block and (rnd < 1 or conv_walk_item(t - slots, tiles_m, tiles_n, walk)[0] == tn):
+                continue
+            mask[tmi // (ty * ty), (tmi // ty) % ty, tmi % ty, tn] = True
+    return mask

@@ -53,6 +53,7 @@ import pytest
 import torch
 
 from tests.helpers import conv_taps, dense_kch, pad_hw, rel_linf, smallcin_ref, unsplit
+from tests.helpers import record_dir as _record_dir
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 U = 2.0 ** -24
@@ -122,18 +123,6 @@ _SEEN_FORMS = set()
 def form_of(op):
     return (op["kind"], op.get("prec", 0), op.get("tile", 0), op.get("ksplit", 1) > 1, op.get("wt_frag", 0),
             op.get("no_cross", 0), op.get("out_split", 0))
-
-
-def _record_dir():
-    """The repository's directory for run records (where tests/test_gpu_baseline_configs.py appends its parity lines): the
-    `*_out/` entry of .gitignore."""
-    try:
-        for line in open(os.path.join(ROOT, ".gitignore")):
-            if line.strip().endswith("_out/"):
-                return os.path.join(ROOT, line.strip().rstrip("/"))
-    except OSError:
-        pass
-    return os.path.join(ROOT, "run_out")
 
 
 def _print_only(**kw):
