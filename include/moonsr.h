@@ -223,6 +223,16 @@ int msr_compact_patches(msr_handle* h, const uint8_t* valid_dev, const int32_t* 
                         const float* minmax_dev, int32_t n, int32_t tile_x, int32_t tile_y, int32_t batch, int32_t cap,
                         int32_t* sel_x_dev, int32_t* sel_y_dev, float* sel_minmax_dev, int32_t* key_dev,
                         float* dmm_dev, int32_t* meta_dev, void* stream);
+/* msr_compact_patches for a caller that carries the unfilled tail of one compaction into the next (the halo mode's
+ * batching="rank": a rank's valid patches form ONE sequence cut at multiples of `batch`, whatever the bands it is generated
+ * in).  Slots [0, carry_n) of the five output arrays are the caller's: it copies the carried rows there (device to device)
+ * and the kernel leaves them untouched.  The stable compaction starts at slot carry_n, the (-1,-1) padding runs from
+ * carry_n + valid to cap, and meta = {carry_n + valid, ceil((carry_n + valid) / batch)}.
+ * carry_n outside [0, batch) or cap < ceil((carry_n + n) / batch) * batch is MSR_ERR_INVALID before anything is launched. */
+int msr_compact_patches_carry(msr_handle* h, const uint8_t* valid_dev, const int32_t* ox_dev, const int32_t* oy_dev,
+                              const float* minmax_dev, int32_t n, int32_t tile_x, int32_t tile_y, int32_t batch, int32_t cap,
+                              int32_t carry_n, int32_t* sel_x_dev, int32_t* sel_y_dev, float* sel_minmax_dev,
+                              int32_t* key_dev, float* dmm_dev, int32_t* meta_dev, void* stream);
 /* Replaces processBatch's "+0.5" and rebuildTile (process_full_tiles.py:340, 363-414) for one tile.
  *   pred_dev    [n, S, S]  generator outputs (last channel), in generation order
  *   key_dev     [n, 2]     int32 (x, y) of each patch relative to the tile origin (padded coords)
@@ -244,10 +254,25 @@ int msr_stitch_partial(msr_handle* h, const float* pred_dev, const int32_t* key_
  * elements) and, with resume != 0, continuing the running update from what the window already holds instead of from zero:
  * the banded form of the halo mode (moonsuperresolution_amd/halo.py) — a rank generates its patch rows band by band (in
  * generation order), accumulates each band into the canvas rows it reaches and frees its predictions.  The sequence of
- * updates per pixel is the all-at-once sequence, so the result does not depend on the band size, bit for bit. */
+ * updates per pixel is the all-at-once sequence, so the STITCHER does not depend on the band size, bit for bit, given
+ * identical predictions.  The predictions of a model with batch statistics (SPADE) depend on their batch mates: they are
+ * independent of the bands only when the batches are (halo.py, batching="rank": msr_compact_patches_carry). */
 int msr_stitch_accumulate(msr_handle* h, const float* pred_dev, const int32_t* key_dev, const float* dmm_dev, int32_t n,
                           int32_t tile_size, int32_t stride, float* wsum_dev, float* mean_dev, float* s_dev, int32_t pitch,
                           int32_t resume, void* stream);
+/* The same accumulation for a whole band in one pass, instead of one msr_stitch_accumulate per T x T block: one thread per
+ * pixel of canvas rows [row_lo, row_hi) x [0, width) of an accumulator slab whose row 0 / column 0 the three pointers name
+ * (row pitch `pitch` >= width elements, row 0 = canvas row acc_row0 <= row_lo).  key_dev holds CANVAS origins (what
+ * msr_compact_patches writes with tile_x = tile_y = 0); the band's patch grid is ngx x ngy cells, cell (0, 0) at canvas
+ * origin (grid_x0, grid_y0), cells `stride` apart; grid_ws_dev is a caller-provided int32 workspace of ngx * ngy cells.
+ * Origins off the grid or not on the stride are ignored.  Every pixel resumes from the slab, applies the updates of the
+ * patches covering it (y outer, x inner) and writes back: the bits msr_stitch_accumulate(resume = 1) leaves over the blocks.
+ * Null pointers, pitch < width, an empty or inverted row range, row_lo < acc_row0 and a non-positive grid are
+ * MSR_ERR_INVALID before anything is launched. */
+int msr_stitch_accumulate_band(msr_handle* h, const float* pred_dev, const int32_t* key_dev, const float* dmm_dev, int32_t n,
+                               int32_t stride, int32_t grid_x0, int32_t grid_y0, int32_t ngx, int32_t ngy,
+                               int32_t* grid_ws_dev, float* wsum_dev, float* mean_dev, float* s_dev, int32_t pitch,
+                               int32_t acc_row0, int32_t row_lo, int32_t row_hi, int32_t width, void* stream);
 /* Pairwise (Chan) combine of two sets of accumulators of the same `count` pixels — a = the rank with the earlier patch
  * rows, b = the later one, or b == NULL — followed by rebuildTile's finalisation (good = w_sum > 0,
  * std = sqrt(S / w_sum), no_value where not good; process_full_tiles.py:409-413). */

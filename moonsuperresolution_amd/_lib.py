@@ -67,9 +67,13 @@ SYMBOLS = [
     ("msr_extract_patches", C.c_int, [_P, _P, _P, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, _P, _P]),
     ("msr_compact_patches", C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P,
                                       _P, _P, _P, _P]),
+    ("msr_compact_patches_carry", C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                            C.c_int32, _P, _P, _P, _P, _P, _P, _P]),
     ("msr_stitch_tile", C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, _P, _P, _P, _P]),
     ("msr_stitch_partial", C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P]),
     ("msr_stitch_accumulate", C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, C.c_int32, C.c_int32, _P]),
+    ("msr_stitch_accumulate_band", C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                             _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P]),
     ("msr_halo_merge", C.c_int, [_P, _P, _P, _P, _P, _P, _P, C.c_int64, C.c_float, _P, _P, _P, _P]),
     ("msr_set_blend_window", C.c_int, [_P, _P, C.c_int32]),
     ("msr_resize_area", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int32, C.c_int32, _P]),

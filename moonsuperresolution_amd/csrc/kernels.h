@@ -460,12 +460,19 @@ hipError_t launch_extract_patches(const float* img, const float* dem, int rows, 
                                   const int* oy, const float* minmax, int n, int S, float* out, hipStream_t s);
 hipError_t launch_compact_patches(const uint8_t* valid, const int* ox, const int* oy, const float* minmax, int n,
                                   int tile_x, int tile_y, int B, int cap, int* sel_x, int* sel_y, float* sel_mm,
-                                  int* key, float* dmm, int* meta, hipStream_t s);
+                                  int* key, float* dmm, int* meta, hipStream_t s, int carry_n = 0);   // carry_n: slots
+                                  // [0, carry_n) of the outputs are the caller's; compaction and counts start behind them
 hipError_t launch_stitch_tile(const float* pred, const int* key, const float* dmm, int n, int S, int T, int stride,
                               float no_value, int as_implemented, const double* window, int* grid_ws,
                               float* mean, float* stdv, uint8_t* good, hipStream_t s, float* wsum_partial = nullptr,
                               int pitch = 0, int resume = 0);   // partial output only: row pitch of the three accumulator
                                                                 // images (0 = T), resume = start from their current content
+// One pass over canvas rows [row_lo, row_hi) x [0, width) of an accumulator slab (row 0 = canvas row acc_row0) with the
+// patches of a band: key = canvas origins, grid cell (0, 0) = origin (grid_x0, grid_y0), grid_ws = ngx * ngy ints.
+hipError_t launch_stitch_accumulate_band(const float* pred, const int* key, const float* dmm, int n, int S, int stride,
+                                         int grid_x0, int grid_y0, int ngx, int ngy, int* grid_ws, const double* window,
+                                         float* wsum, float* mean, float* s_acc, int pitch, int acc_row0, int row_lo,
+                                         int row_hi, int width, hipStream_t s);
 hipError_t launch_halo_merge(const float* wa, const float* ma, const float* sa, const float* wb, const float* mb,
                              const float* sb, long n, float no_value, float* mean, float* stdv, uint8_t* good,
                              hipStream_t s);

@@ -136,17 +136,20 @@ hipError_t launch_extract_patches(const float* img, const float* dem, int rows, 
 //   sel_mm [cap][4]       their {img_min, img_max, dem_min, dem_max}, zeros for padding
 //   key [cap][2]          origins relative to the tile (the reference's dict keys), (-1,-1) for padding
 //   dmm [cap][2]          {dem_min, dem_max} (what stitch_tile takes)
+// carry_n > 0 (msr_compact_patches_carry, the halo mode's batching="rank"): slots [0, carry_n) of the five outputs hold the
+// unfilled tail of an earlier band, put there by the caller; they are left alone, the compaction starts at slot carry_n and
+// the counts in `meta` include them.
 // ------------------------------------------------------------------------------------------------
 __global__ void __launch_bounds__(1024) compact_patches_kernel(const uint8_t* __restrict__ valid,
                                                                const int* __restrict__ ox, const int* __restrict__ oy,
                                                                const float* __restrict__ minmax, int n, int tile_x,
-                                                               int tile_y, int B, int cap, int* __restrict__ sel_x,
-                                                               int* __restrict__ sel_y, float* __restrict__ sel_mm,
-                                                               int* __restrict__ key, float* __restrict__ dmm,
-                                                               int* __restrict__ meta) {
+                                                               int tile_y, int B, int cap, int carry_n,
+                                                               int* __restrict__ sel_x, int* __restrict__ sel_y,
+                                                               float* __restrict__ sel_mm, int* __restrict__ key,
+                                                               float* __restrict__ dmm, int* __restrict__ meta) {
     __shared__ int wsum[16];
     const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-    int base = 0;
+    int base = carry_n;
     for (int start = 0; start < n; start += 1024) {
         const int i = start + threadIdx.x;
         const int v = i < n ? (valid[i] != 0) : 0;
@@ -184,9 +187,9 @@ __global__ void __launch_bounds__(1024) compact_patches_kernel(const uint8_t* __
 
 hipError_t launch_compact_patches(const uint8_t* valid, const int* ox, const int* oy, const float* minmax, int n,
                                   int tile_x, int tile_y, int B, int cap, int* sel_x, int* sel_y, float* sel_mm,
-                                  int* key, float* dmm, int* meta, hipStream_t s) {
-    compact_patches_kernel<<<1, 1024, 0, s>>>(valid, ox, oy, minmax, n, tile_x, tile_y, B, cap, sel_x, sel_y, sel_mm,
-                                              key, dmm, meta);
+                                  int* key, float* dmm, int* meta, hipStream_t s, int carry_n) {
+    compact_patches_kernel<<<1, 1024, 0, s>>>(valid, ox, oy, minmax, n, tile_x, tile_y, B, cap, carry_n, sel_x, sel_y,
+                                              sel_mm, key, dmm, meta);
     return hipGetLastError();
 }
 
@@ -269,6 +272,79 @@ hipError_t launch_stitch_tile(const float* pred, const int* key, const float* dm
                                                                          no_value, as_implemented, window, mean,
                                                                          stdv, good, wsum_partial, pitch > 0 ? pitch : T,
                                                                          wsum_partial ? resume : 0);
+    return hipGetLastError();
+}
+
+// ------------------------------------------------------------------------------------------------
+// stitch_accumulate_band: the halo mode's accumulation of one band of patch rows in ONE pass over the canvas rows the band
+// reaches, instead of one stitch_tile pass per T x T block (msr_stitch_accumulate, which rewrites whole blocks — also their
+// rows the band never reaches — and needs the keys rebased per block on the host).  The patch grid is the band's own:
+// cell (gx, gy) is the patch at canvas origin (grid_x0 + gx * stride, grid_y0 + gy * stride), `key` holds canvas origins as
+// compact_patches wrote them.  One thread per pixel of canvas rows [row_lo, row_hi) x [0, width): it walks the cells covering
+// it, y outer, x inner (ky in (y - S + p, y - p], likewise x, clamped to the grid), resumes from the accumulator slab and
+// writes back.  The update is stitch_tile_kernel's with as_implemented = 0, expression for expression and type for type, and
+// a pixel meets its patches in the same order, so the slab holds the bits the per-block passes leave.
+// Layout as stitch_tile: 16 consecutive x per 16-lane row, so a wave reads 4 rows x 64 B of each accumulator and of a patch.
+// ------------------------------------------------------------------------------------------------
+__global__ void stitch_band_grid_kernel(const int* __restrict__ key, int n, int stride, int grid_x0, int grid_y0, int ngx,
+                                        int ngy, int* __restrict__ grid) {
+    const int i = blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const int dx = key[2 * i] - grid_x0, dy = key[2 * i + 1] - grid_y0;
+    if (dx < 0 || dy < 0 || dx % stride || dy % stride) return;
+    const int gx = dx / stride, gy = dy / stride;
+    if (gx < ngx && gy < ngy) grid[(size_t)gy * ngx + gx] = i;
+}
+
+__global__ void __launch_bounds__(256) stitch_band_kernel(const float* __restrict__ pred, const float* __restrict__ dmm,
+                                                          const int* __restrict__ grid, int n, int S, int stride,
+                                                          int grid_x0, int grid_y0, int ngx, int ngy,
+                                                          const double* __restrict__ window, float* __restrict__ wsum_o,
+                                                          float* __restrict__ mean_o, float* __restrict__ s_o, int pitch,
+                                                          int acc_row0, int row_lo, int row_hi, int width) {
+    const int x = blockIdx.x * 16 + (threadIdx.x & 15);
+    const int y = row_lo + blockIdx.y * 16 + (threadIdx.x >> 4);
+    if (x >= width || y >= row_hi) return;
+    const int purge = S / 16, ws = S - 2 * purge;
+    // cells whose origin k lies in (a - S + purge, a - purge], a relative to the grid origin
+    auto lo_idx = [&](int a) { int v = a - S + purge + 1; return v <= 0 ? 0 : (v + stride - 1) / stride; };
+    auto hi_idx = [&](int a, int ng) { int v = a - purge; return v < 0 ? -1 : min(v / stride, ng - 1); };
+    const int ax = x - grid_x0, ay = y - grid_y0;
+    const int gy0 = lo_idx(ay), gy1 = hi_idx(ay, ngy), gx0 = lo_idx(ax), gx1 = hi_idx(ax, ngx);
+    if (gy0 > gy1 || gx0 > gx1) return;              // no cell of this band covers the pixel: it keeps what it holds
+    const size_t o = (size_t)(y - acc_row0) * pitch + x;
+    float w_sum = wsum_o[o], mean = mean_o[o], s_acc = s_o[o];
+    for (int gy = gy0; gy <= gy1; ++gy) {
+        const int py = ay - gy * stride;
+        for (int gx = gx0; gx <= gx1; ++gx) {
+            const int slot = grid[(size_t)gy * ngx + gx];
+            if (slot < 0 || slot >= n) continue;
+            const int px = ax - gx * stride;
+            const float pr = pred[(size_t)slot * S * S + (size_t)py * S + px] + 0.5f;       // :340
+            const float lo = dmm[2 * slot], hi = dmm[2 * slot + 1];
+            const float xval = pr * (hi - lo) + lo;                                          // :395
+            const double w = window[(size_t)(py - purge) * ws + (px - purge)];
+            w_sum = (float)((double)w_sum + w);                                              // :397
+            const float d_old = xval - mean;
+            const float mean_new = (float)((double)mean + (w / (double)w_sum) * (double)d_old);   // :401
+            const float d_new = xval - mean_new;
+            s_acc = (float)((double)s_acc + (w * (double)d_old) * (double)d_new);            // :402, textbook West
+            mean = mean_new;
+        }
+    }
+    wsum_o[o] = w_sum; mean_o[o] = mean; s_o[o] = s_acc;
+}
+
+hipError_t launch_stitch_accumulate_band(const float* pred, const int* key, const float* dmm, int n, int S, int stride,
+                                         int grid_x0, int grid_y0, int ngx, int ngy, int* grid_ws, const double* window,
+                                         float* wsum, float* mean, float* s_acc, int pitch, int acc_row0, int row_lo,
+                                         int row_hi, int width, hipStream_t s) {
+    hipError_t e = hipMemsetAsync(grid_ws, 0xFF, sizeof(int) * (size_t)ngx * ngy, s);
+    if (e != hipSuccess) return e;
+    if (n > 0) stitch_band_grid_kernel<<<(n + 255) / 256, 256, 0, s>>>(key, n, stride, grid_x0, grid_y0, ngx, ngy, grid_ws);
+    stitch_band_kernel<<<dim3((width + 15) / 16, (row_hi - row_lo + 15) / 16), 256, 0, s>>>(
+        pred, dmm, grid_ws, n, S, stride, grid_x0, grid_y0, ngx, ngy, window, wsum, mean, s_acc, pitch, acc_row0, row_lo,
+        row_hi, width);
     return hipGetLastError();
 }
 

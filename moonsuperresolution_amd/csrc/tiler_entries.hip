@@ -41,6 +41,25 @@ int msr_compact_patches(msr_handle* h, const uint8_t* valid, const int32_t* ox, 
     return MSR_OK;
 }
 
+int msr_compact_patches_carry(msr_handle* h, const uint8_t* valid, const int32_t* ox, const int32_t* oy, const float* minmax,
+                              int32_t n, int32_t tile_x, int32_t tile_y, int32_t batch, int32_t cap, int32_t carry_n,
+                              int32_t* sel_x, int32_t* sel_y, float* sel_mm, int32_t* key, float* dmm, int32_t* meta,
+                              void* stream) {
+    if (!h) return MSR_ERR_INVALID;
+    if (!valid || !ox || !oy || !minmax || !sel_x || !sel_y || !sel_mm || !key || !dmm || !meta || n < 0 || batch < 1)
+        return fail(h, MSR_ERR_INVALID, "msr_compact_patches_carry: bad argument");
+    if (carry_n < 0 || carry_n >= batch)
+        return fail(h, MSR_ERR_INVALID, "msr_compact_patches_carry: carry_n %d outside [0, %d)", carry_n, batch);
+    const int64_t need = ((int64_t)carry_n + n + batch - 1) / batch * batch;
+    if (cap < need)
+        return fail(h, MSR_ERR_INVALID, "msr_compact_patches_carry: cap %d < ceil((%d + %d) / %d) * %d", cap, carry_n, n, batch,
+                    batch);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    HIPCHK(h, launch_compact_patches(valid, ox, oy, minmax, n, tile_x, tile_y, batch, cap, sel_x, sel_y, sel_mm, key, dmm,
+                                     meta, (hipStream_t)stream, carry_n));
+    return MSR_OK;
+}
+
 int msr_resize_area_rows(msr_handle* h, const float* src, int32_t src_row0, int32_t src_rows, int32_t full_rows,
                          int32_t cols, int32_t factor, float* dst, int32_t dst_row0, int32_t dst_rows, int32_t dst_cols,
                          float no_value, int32_t flags, void* stream) {
@@ -175,6 +194,29 @@ int msr_stitch_accumulate(msr_handle* h, const float* pred, const int32_t* key, 
         return fail(h, MSR_ERR_INVALID, "msr_stitch_accumulate: bad argument (pitch >= tile_size)");
     return stitch_impl(h, pred, key, dmm, n, tile_size, stride, 0.f, /*as_implemented=*/0, mean, s_acc, nullptr, wsum, stream,
                        pitch, resume ? 1 : 0);
+}
+
+int msr_stitch_accumulate_band(msr_handle* h, const float* pred, const int32_t* key, const float* dmm, int32_t n,
+                               int32_t stride, int32_t grid_x0, int32_t grid_y0, int32_t ngx, int32_t ngy, int32_t* grid_ws,
+                               float* wsum, float* mean, float* s_acc, int32_t pitch, int32_t acc_row0, int32_t row_lo,
+                               int32_t row_hi, int32_t width, void* stream) {
+    if (!h) return MSR_ERR_INVALID;
+    if (!wsum || !mean || !s_acc || !grid_ws || n < 0 || (n > 0 && (!pred || !key || !dmm)))
+        return fail(h, MSR_ERR_INVALID, "msr_stitch_accumulate_band: null pointer");
+    if (stride <= 0 || stride > h->S)
+        return fail(h, MSR_ERR_INVALID, "msr_stitch_accumulate_band: stride %d invalid for image_size %d", stride, h->S);
+    if (ngx <= 0 || ngy <= 0 || (int64_t)ngx * ngy > INT32_MAX)
+        return fail(h, MSR_ERR_INVALID, "msr_stitch_accumulate_band: patch grid %d x %d", ngx, ngy);
+    if (width <= 0 || pitch < width)
+        return fail(h, MSR_ERR_INVALID, "msr_stitch_accumulate_band: pitch %d < width %d", pitch, width);
+    if (row_hi <= row_lo || row_lo < acc_row0)
+        return fail(h, MSR_ERR_INVALID, "msr_stitch_accumulate_band: rows [%d, %d) empty, inverted or above the slab's row %d",
+                    row_lo, row_hi, acc_row0);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    if (!h->window) { int rc = default_window(h); if (rc) return rc; }
+    HIPCHK(h, launch_stitch_accumulate_band(pred, key, dmm, n, h->S, stride, grid_x0, grid_y0, ngx, ngy, grid_ws, h->window,
+                                            wsum, mean, s_acc, pitch, acc_row0, row_lo, row_hi, width, (hipStream_t)stream));
+    return MSR_OK;
 }
 
 int msr_halo_merge(msr_handle* h, const float* wa, const float* ma, const float* sa, const float* wb, const float* mb,

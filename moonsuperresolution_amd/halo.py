@@ -17,15 +17,30 @@ The exact, reference-identical multi-GPU mode is the tile-row sharding of distri
 Memory (round 3): a rank works through its patch rows in BANDS (``band_rows`` patch rows at a time, default sized to
 ``band_bytes`` = 4 GiB of predictions): a band is generated, accumulated into the canvas rows it reaches — in place, block by
 block, with only the band's own keys (msr_stitch_accumulate: the running update resumes from what earlier bands left, so the
-result does not depend on the band size, bit for bit) — and its predictions are freed.  What stays resident is the rank's
+STITCHER does not depend on the band size, bit for bit, given identical predictions) — and its predictions are freed.  The
+predictions themselves are band-invariant only for a model without batch statistics, or under ``batching="rank"`` (below):
+with the default ``batching="band"`` every band is compacted and batched on its own and ends in its own zero-padded call, so
+the batch mates of a patch — and through SPADE's batch moments its output — follow the band cut.  What stays resident is the rank's
 accumulator slab (3 float32 images of the canvas rows its patches reach: 2.1 GB for a 1/8 share of the 15000 x 70000 raster)
 plus one band; round 2 kept all predictions of the rank (34 GB at that size).
 Exchange: the two boundary-zone slabs go to the neighbours as non-blocking send / recv while the interior rows (reached by this
 rank's patches only) are finalised; the zones are finalised when the neighbours' slabs have arrived.
+
+Two opt-in forms (the defaults are the code paths as they were; whether either default flips is a later decision):
+  ``batching="rank"``    the rank's valid patches, in generation order, are ONE sequence cut into calls of B at multiples of B
+                         of that sequence (batch_schedule).  A band issues whole calls only; its unfilled tail (< B patches) is
+                         carried in front of the next band's patches (msr_compact_patches_carry) and only the rank's last
+                         call is zero-padded.  Every issued chunk is a consecutive slice of the all-at-once sequence, so the
+                         resumed accumulation still applies each pixel's updates in that sequence's order; the rows a chunk
+                         reaches start at the first carried patch row.  With the counter sampler the padding rows of the last
+                         call draw (index in the rank's sequence, 0xFFFFFFFE, 0xFFFFFFFF).  The products then equal
+                         oracle/tiler_ref.py::process_map_halo's whatever ``band_rows`` / ``band_bytes`` is.
+  ``accumulate="band"``  one launch over the canvas rows a band reaches (msr_stitch_accumulate_band) instead of one full-block
+                         pass per T x T block the band touches: the same bits, no per-block key tensors, no host syncs.
 """
 from __future__ import annotations
 
-from typing import Callable, Optional, Sequence, Tuple
+from typing import Callable, List, Optional, Sequence, Tuple
 
 import numpy as np
 import torch
@@ -33,6 +48,35 @@ import torch
 from . import _lib
 from .distributed import halo_zone_rows, patch_grid_1d
 from .tiler import DEMSuperResolution
+
+
+def batch_schedule(valid_per_band: Sequence[int], batch_size: int) -> List[Tuple[int, int]]:
+    """The calls of ``batching="rank"`` before the final flush: [(calls issued by the band, patches carried after it)].
+    A band issues the whole calls of (carry + its valid patches) and carries the rest (< batch_size) on; what the last band
+    carries goes into one more, zero-padded call (flush_padding), so the rank makes ceil(total / batch_size) calls and the
+    k-th call holds patches [k * batch_size, (k + 1) * batch_size) of the rank's sequence, wherever the bands are cut."""
+    if batch_size < 1:
+        raise ValueError(f"batch_size {batch_size} < 1")
+    out, carry = [], 0
+    for nv in valid_per_band:
+        if nv < 0:
+            raise ValueError(f"negative valid count {nv}")
+        calls, carry = divmod(carry + int(nv), batch_size)
+        out.append((calls, carry))
+    return out
+
+
+def flush_padding(valid_per_band: Sequence[int], batch_size: int) -> List[Tuple[int, int, int]]:
+    """Noise ids (as uint32 triples) of the padding rows of the rank's last call under ``batching="rank"``: the row's index
+    in the rank's whole compacted sequence — patches issued by earlier calls plus its slot in the flush call — then
+    0xFFFFFFFE, 0xFFFFFFFF.  Empty when the sequence fills its last call (or is empty)."""
+    sched = batch_schedule(valid_per_band, batch_size)
+    issued = batch_size * sum(c for c, _ in sched)
+    carry = sched[-1][1] if sched else 0
+    return [(issued + slot, 0xFFFFFFFE, 0xFFFFFFFF) for slot in range(carry, batch_size)] if carry else []
+
+
+_CARRIED = ("sx", "sy", "mm_sel", "keys", "dmm")
 
 
 class HaloShardedSuperResolution(DEMSuperResolution):
@@ -52,11 +96,15 @@ class HaloShardedSuperResolution(DEMSuperResolution):
         return ys, xs
 
     # ------------------------------------------------------------------------------------------------------------
-    def _generate_rows(self, ys: Sequence[int], xs: Sequence[int]):
+    def _generate_rows(self, ys: Sequence[int], xs: Sequence[int], carry: Optional[dict] = None, last: bool = True):
         """Validity, normalisation statistics, device-side batch assembly and the generator calls for every patch at
-        rows `ys`: returns (preds [ncall * B, S, S], keys [cap, 2] canvas origins, dmm [cap, 2], valid count).
+        rows `ys`: returns (preds [ncall * B, S, S], keys [cap, 2] canvas origins, dmm [cap, 2], patches to stitch).
         The kernels that read the canvas get window rows (origin - canvas_row0, tiler.padInputs); the keys stay canvas
-        origins (msr_compact_patches subtracts tile_y = -canvas_row0)."""
+        origins (msr_compact_patches subtracts tile_y = -canvas_row0).
+        ``carry`` (batching="rank"): the rank's state {"n": patches carried, "issued": patches of the calls made so far, and
+        the carried rows of the five compaction outputs}.  They stand in front of this band's patches; only whole calls are
+        issued, unless ``last``, and the rest is left in ``carry``.  The patches to stitch are the live rows of the calls
+        issued (with carry=None: the band's valid patches, as ever)."""
         S, B = self.image_size, self.batch_size
         lib, h, dev = self._lib, self._h, self.device
         c0, rows, cols = self._window()
@@ -69,7 +117,8 @@ class HaloShardedSuperResolution(DEMSuperResolution):
             ox = xt.repeat(len(ys))
             oy = yt.repeat_interleave(len(xs))
             n = int(ox.numel())
-            cap = max(B, (n + B - 1) // B * B)
+            carry_n = 0 if carry is None else carry["n"]
+            cap = max(B, (carry_n + n + B - 1) // B * B)
             valid = torch.empty(n, dtype=torch.uint8, device=dev)
             minmax = torch.empty((n, 4), dtype=torch.float32, device=dev)
             sx = torch.empty(cap, dtype=torch.int32, device=dev)
@@ -81,11 +130,27 @@ class HaloShardedSuperResolution(DEMSuperResolution):
             rc = lib.msr_patch_stats(h, self.img_padded.data_ptr(), self.dem_padded.data_ptr(), rows, cols, ox.data_ptr(),
                                      oy.data_ptr(), n, self.no_value, valid.data_ptr(), minmax.data_ptr(), stream)
             _lib.raise_for(lib, h, rc, "msr_patch_stats")
-            rc = lib.msr_compact_patches(h, valid.data_ptr(), ox.data_ptr(), oy.data_ptr(), minmax.data_ptr(), n, 0, -c0, B,
-                                         cap, sx.data_ptr(), sy.data_ptr(), mm_sel.data_ptr(), keys.data_ptr(),
-                                         dmm.data_ptr(), meta.data_ptr(), stream)
-            _lib.raise_for(lib, h, rc, "msr_compact_patches")
-            nv, ncall = (int(v) for v in meta.cpu().tolist())
+            if carry is None:
+                rc = lib.msr_compact_patches(h, valid.data_ptr(), ox.data_ptr(), oy.data_ptr(), minmax.data_ptr(), n, 0, -c0,
+                                             B, cap, sx.data_ptr(), sy.data_ptr(), mm_sel.data_ptr(), keys.data_ptr(),
+                                             dmm.data_ptr(), meta.data_ptr(), stream)
+                _lib.raise_for(lib, h, rc, "msr_compact_patches")
+            else:
+                out = dict(zip(_CARRIED, (sx, sy, mm_sel, keys, dmm)))
+                for name in _CARRIED if carry_n else ():
+                    out[name][:carry_n].copy_(carry[name])          # the earlier band's tail, device to device
+                rc = lib.msr_compact_patches_carry(h, valid.data_ptr(), ox.data_ptr(), oy.data_ptr(), minmax.data_ptr(), n, 0,
+                                                   -c0, B, cap, carry_n, sx.data_ptr(), sy.data_ptr(), mm_sel.data_ptr(),
+                                                   keys.data_ptr(), dmm.data_ptr(), meta.data_ptr(), stream)
+                _lib.raise_for(lib, h, rc, "msr_compact_patches_carry")
+            tot, ncall = (int(v) for v in meta.cpu().tolist())
+            nv = tot - carry_n                            # this band's own valid patches
+            seq0 = 0                                      # index, in the sequence the calls are cut from, of slot 0
+            if carry is not None:
+                seq0 = carry["issued"]
+                if not last:
+                    ncall = tot // B                      # whole calls only: the tail waits for the next band
+            n_out = min(tot, ncall * B)
             self._range_retire()                      # range_check: the previous band's scan, read with this band's counts
             preds = torch.empty((max(ncall * B, 1), S, S), dtype=torch.float32, device=dev)
             self.last_noise_ids = None                # [cap, 3] of the band just issued, with the counter sampler
@@ -96,11 +161,12 @@ class HaloShardedSuperResolution(DEMSuperResolution):
                 ids = None
                 if self.counter_noise:
                     # The noise follows the patch: id (canvas origin x, y, 0xFFFFFFFF), whatever band or batch it lands in;
-                    # the padding rows of the last call draw (slot, 0xFFFFFFFE, 0xFFFFFFFF).
+                    # the padding rows of the last call draw (slot, 0xFFFFFFFE, 0xFFFFFFFF) — the slot in the band, or, with
+                    # batching="rank", in the rank's whole sequence, so that they too are the same for every band cut.
                     slot = torch.arange(cap, dtype=torch.int32, device=dev)
-                    live = slot < nv
+                    live = slot < tot
                     ids = torch.full((cap, 3), -1, dtype=torch.int32, device=dev)
-                    ids[:, 0] = torch.where(live, keys[:, 0], slot)
+                    ids[:, 0] = torch.where(live, keys[:, 0], slot + seq0)
                     ids[:, 1] = torch.where(live, keys[:, 1], torch.full_like(slot, -2))
                 self.last_noise_ids = ids
                 for ps in self._pstreams:
@@ -129,8 +195,13 @@ class HaloShardedSuperResolution(DEMSuperResolution):
                     _lib.raise_for(lib, h, rc, "msr_extract_patches")
                     out = np.array(self.model(batch.cpu().numpy(), training=False))[:, :, :, -1]
                     preds[c * B:(c + 1) * B] = torch.from_numpy(np.ascontiguousarray(out, dtype=np.float32)).to(dev)
+            if carry is not None:
+                for name, t in zip(_CARRIED, (sx, sy, mm_sel, keys, dmm)):
+                    carry[name] = t[n_out:tot].clone()    # < B rows; the band's arrays go with its predictions
+                carry["n"] = tot - n_out
+                carry["issued"] = seq0 + ncall * B
             self.last_counts_halo = (nv, ncall)
-            return preds, keys, dmm, nv
+            return preds, keys, dmm, n_out
 
     def _accumulate_band(self, acc, y_b0: int, preds, keys, dmm, nv: int, band_lo: int, band_hi: int) -> None:
         """Add the patches of one band (canvas rows [band_lo, band_hi) are the rows they reach) to the accumulator slab
@@ -153,6 +224,25 @@ class HaloShardedSuperResolution(DEMSuperResolution):
                                                    win[0].data_ptr(), win[1].data_ptr(), win[2].data_ptr(), pitch, 1,
                                                    self._stream())
                     _lib.raise_for(lib, h, rc, "msr_stitch_accumulate")
+
+    def _accumulate_band_once(self, acc, y_b0: int, preds, keys, dmm, n: int, y_first: int, y_last: int,
+                              xs: Sequence[int]) -> None:
+        """_accumulate_band in one launch (msr_stitch_accumulate_band): the ``n`` patches, whose rows lie in
+        [y_first, y_last] (canvas origins, on the stride), update the canvas rows they reach; the keys go as they are."""
+        S, s = self.image_size, self.stride
+        p = S // 16
+        lib, h, dev = self._lib, self._h, self.device
+        pitch = acc.shape[2]
+        row_lo, row_hi = max(y_first + p, y_b0), min(y_last + S - p, y_b0 + acc.shape[1])
+        if row_hi <= row_lo or n <= 0:
+            return
+        ngx, ngy = (xs[-1] - xs[0]) // s + 1, (y_last - y_first) // s + 1
+        with torch.cuda.device(dev):
+            grid = torch.empty(ngx * ngy, dtype=torch.int32, device=dev)
+            rc = lib.msr_stitch_accumulate_band(h, preds.data_ptr(), keys.data_ptr(), dmm.data_ptr(), n, s, xs[0], y_first,
+                                                ngx, ngy, grid.data_ptr(), acc[0].data_ptr(), acc[1].data_ptr(),
+                                                acc[2].data_ptr(), pitch, y_b0, row_lo, row_hi, pitch, self._stream())
+            _lib.raise_for(lib, h, rc, "msr_stitch_accumulate_band")
 
     def _finalize(self, a, b=None):
         """msr_halo_merge over [3, rows, W] accumulators -> (mean, std, good)."""
@@ -181,14 +271,22 @@ class HaloShardedSuperResolution(DEMSuperResolution):
         return crop_for_rank(self, rank, world, "halo")
 
     def haloAccumulate(self, rank: int = 0, world: int = 1, band_rows: Optional[int] = None, band_bytes: int = 4 << 30,
-                       max_rows: int = 0, crop_inputs: bool = False):
+                       max_rows: int = 0, crop_inputs: bool = False, batching: str = "band", accumulate: str = "blocks"):
         """Phase 1 (no communication): generate this rank's patch rows band by band and accumulate them.  Returns the
         state ``haloFinish`` takes: the accumulators of the canvas rows the rank's patches reach, what it must send to its
         neighbours and the shapes of what it receives.  ``band_rows`` patch rows per band (default: as many as fit
         ``band_bytes`` of predictions); ``max_rows`` > 0 stops after that many patch rows (benchmarks of a share of a
         large raster: the accumulators of the rows not reached stay empty).  ``crop_inputs``: when the instance still
         holds host rasters, keep only this rank's rows of them (cropInputs) before they are padded and uploaded; the
-        accumulators, the zones and the result are the same bits."""
+        accumulators, the zones and the result are the same bits.
+        ``batching``: "band" cuts every band's valid patches into calls on their own (each band ends in a zero-padded call);
+        "rank" cuts the rank's whole sequence at multiples of B and carries a band's unfilled tail into the next band, so the
+        batches — and the products of a model with batch statistics — do not depend on the bands.  ``accumulate``: "blocks"
+        stitches a band block by block, "band" in one launch; the same bits.  See the module docstring."""
+        if batching not in ("band", "rank"):
+            raise ValueError(f"batching must be 'band' or 'rank', got {batching!r}")
+        if accumulate not in ("blocks", "band"):
+            raise ValueError(f"accumulate must be 'blocks' or 'band', got {accumulate!r}")
         if self.dem_padded is None or self.dem is not None:
             if crop_inputs and self.dem is not None:
                 self.cropInputs(rank, world)
@@ -214,21 +312,38 @@ class HaloShardedSuperResolution(DEMSuperResolution):
         with torch.cuda.device(self.device):
             slab = torch.zeros((3, n_by * T, n_bx * T), dtype=torch.float32, device=self.device)
             done = 0
+            carry = {"n": 0, "issued": 0} if batching == "rank" else None
+            first_row = None                             # the patch row the carried patches start at (or lie behind)
+            counts, marks = [], []
             for b0 in range(0, len(my_ys), band_rows):
                 band = my_ys[b0:b0 + band_rows]
                 if max_rows and done + len(band) > max_rows:
                     band = band[:max_rows - done]
                 if not band:
                     break
-                preds, keys, dmm, nv = self._generate_rows(band, xs)
-                self._accumulate_band(slab, y_b0, preds, keys, dmm, nv, band[0] + p, band[-1] + S - p)
+                done += len(band)
+                last = b0 + band_rows >= len(my_ys) or bool(max_rows and done >= max_rows)
+                if carry is None or carry["n"] == 0:
+                    first_row = band[0]
+                preds, keys, dmm, n_out = self._generate_rows(band, xs, carry, last)
+                marks.append([torch.cuda.Event(enable_timing=True) for _ in range(2)])
+                marks[-1][0].record()
+                if accumulate == "band":
+                    self._accumulate_band_once(slab, y_b0, preds, keys, dmm, n_out, first_row, band[-1], xs)
+                elif carry is None or n_out:
+                    self._accumulate_band(slab, y_b0, preds, keys, dmm, n_out, first_row + p, band[-1] + S - p)
+                marks[-1][1].record()
+                if carry is not None and self.last_counts_halo[1]:
+                    first_row = band[0]                  # a band that issued a call carries only patches of its own
+                counts.append(self.last_counts_halo)
                 nv_tot += self.last_counts_halo[0]
                 nc_tot += self.last_counts_halo[1]
-                done += len(band)
                 del preds, keys, dmm                     # the band's predictions are not needed again
             acc = slab[:, lo - y_b0:hi - y_b0, :wp]
         self._range_retire()                          # the last band's scan
         self.last_counts_halo = (nv_tot, nc_tot)
+        self.last_band_counts = counts                # per band: (valid patches of the band, calls it issued)
+        self._band_marks = marks
         self.last_band_rows = band_rows
         st = dict(rank=rank, world=world, acc=acc, lo=lo, hi=hi, own_lo=own_lo, own_hi=own_hi, wp=wp,
                   send_down=acc[:, :own_lo - lo] if rank > 0 else None,                     # rows [touch_lo, own_lo)
@@ -236,6 +351,11 @@ class HaloShardedSuperResolution(DEMSuperResolution):
                   down_rows=max(0, zones[rank - 1]["touch_hi"] - own_lo) if rank > 0 else 0,
                   up_rows=max(0, own_hi - zones[rank + 1]["touch_lo"]) if rank < world - 1 else 0)
         return st
+
+    def bandStitchSeconds(self) -> List[float]:
+        """Device time of every band's accumulation in the last haloAccumulate (waits for the work to finish)."""
+        torch.cuda.synchronize(self.device)
+        return [a.elapsed_time(b) / 1e3 for a, b in self._band_marks]
 
     def haloFinish(self, st, from_down=None, from_up=None, *, exchange: Optional[Callable] = None):
         """Phase 2: combine the boundary zones with the neighbours' accumulators (from_down = rank - 1's rows
@@ -277,14 +397,16 @@ class HaloShardedSuperResolution(DEMSuperResolution):
 
     def processMapHalo(self, img: Optional[np.ndarray] = None, dem: Optional[np.ndarray] = None, rank: int = 0,
                        world: int = 1, exchange: Optional[Callable] = None, band_rows: Optional[int] = None,
-                       crop_inputs: bool = False):
+                       crop_inputs: bool = False, batching: str = "band", accumulate: str = "blocks"):
         """This rank's share of the map in halo mode: accumulate band by band, start the exchange of the boundary zones
         with the neighbours (non-blocking send / recv: distributed.exchange_halo_start, RCCL on the GPUs), finalise the
         interior rows beside it, then the zones.  ``exchange``: a blocking replacement with exchange_halo's signature.
-        ``crop_inputs``: pad and upload only the raster rows this rank's patches read (haloAccumulate)."""
+        ``crop_inputs``: pad and upload only the raster rows this rank's patches read; ``batching`` / ``accumulate``: the
+        band-invariant batch sequence and the one-launch accumulation (haloAccumulate)."""
         if img is not None:
             self.setImages(img, dem)
-        st = self.haloAccumulate(rank, world, band_rows=band_rows, crop_inputs=crop_inputs)
+        st = self.haloAccumulate(rank, world, band_rows=band_rows, crop_inputs=crop_inputs, batching=batching,
+                                 accumulate=accumulate)
         if world == 1:
             return self.haloFinish(st)
         torch.cuda.current_stream(self.device).synchronize()      # the slabs are complete before they are sent
@@ -305,15 +427,15 @@ class HaloShardedSuperResolution(DEMSuperResolution):
         return tuple(p[halo:halo + h, halo:halo + w].cpu().numpy() for p in parts)
 
     def _process_files_sharded(self, preprocess: bool, rank: int, world: int, mode: str, gather: bool,
-                               swap_dsize: bool = True):
+                               swap_dsize: bool = True, batching: str = "band", accumulate: str = "blocks"):
         """processFiles(mode="halo"): this rank reads only the rows its patch rows touch, runs its share (processMapHalo:
         the zone exchange needs an initialised process group when world > 1) and, with ``gather``, all-gathers the slabs;
-        without it the rows other ranks own stay zero."""
+        without it the rows other ranks own stay zero.  ``batching`` / ``accumulate`` are processMapHalo's."""
         if mode != "halo":
             return super()._process_files_sharded(preprocess, rank, world, mode, gather, swap_dsize)
         from .distributed import all_gather_var_rows
         self._load_rank_rows(preprocess, rank, world, mode, swap_dsize)
-        (m, sd, g), (own_lo, own_hi) = self.processMapHalo(rank=rank, world=world)
+        (m, sd, g), (own_lo, own_hi) = self.processMapHalo(rank=rank, world=world, batching=batching, accumulate=accumulate)
         hp = self.dem_padded_shape[0]
         if world > 1 and gather:
             ys, _ = self.patchGrid()

@@ -275,7 +275,7 @@ class DEMSuperResolution:
         self.image = None
 
     def processFiles(self, preprocess: bool = True, rank: int = 0, world: int = 1, mode: Optional[str] = None,
-                     gather: bool = True, swap_dsize: bool = True) -> None:
+                     gather: bool = True, swap_dsize: bool = True, **sharded) -> None:
         """processMap of the reference on files (process_full_tiles.py:568-587): loadImages -> preprocess ->
         padInputs -> tiles -> rebuildMap -> ``<map>_mean.tiff``, ``<map>_std.tiff``, ``<map>_good.tiff``.
         ``preprocess=False`` skips the low-resolution-DEM synthesis (feed an already pre-processed DEM); ``swap_dsize`` is
@@ -287,10 +287,13 @@ class DEMSuperResolution:
         (input_rows(preprocess=True)), which it pre-processes itself (preprocess(rows=)) — uploads only its tiles' rows,
         runs its tile rows (distributed.process_map_sharded) and, with ``gather`` (needs an initialised process group),
         all-gathers the finished rows; without it the rows of other ranks stay zero in the files written.
-        ``mode="halo"`` is accepted by HaloShardedSuperResolution.processFiles only."""
+        ``mode="halo"`` is accepted by HaloShardedSuperResolution.processFiles only; further keywords (``batching``,
+        ``accumulate``: halo.py) go to the sharded mode that takes them."""
         if mode is not None:
-            mean, std, good = self._process_files_sharded(preprocess, rank, world, mode, gather, swap_dsize)
+            mean, std, good = self._process_files_sharded(preprocess, rank, world, mode, gather, swap_dsize, **sharded)
         else:
+            if sharded:
+                raise TypeError(f"processFiles: {sorted(sharded)} need a sharded mode")
             self.loadImages()
             if preprocess:
                 self.preprocess(swap_dsize=swap_dsize)

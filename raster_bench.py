@@ -76,6 +76,11 @@ def main():
     ap.add_argument("--max-rows", type=int, default=0, help="halo mode: stop after this many patch rows of the shard (0 = all)")
     ap.add_argument("--band-rows", type=int, default=0, help="halo mode: patch rows per band (0 = what fits --band-gib of predictions)")
     ap.add_argument("--band-gib", type=float, default=2.0, help="halo mode: predictions kept at a time, GiB")
+    ap.add_argument("--batching", default="band", choices=("band", "rank"),
+                    help="halo mode: rank = one batch sequence per rank, a band's unfilled tail is carried into the next band "
+                         "(the products do not depend on the bands); band = every band batched on its own")
+    ap.add_argument("--accumulate", default="blocks", choices=("blocks", "band"),
+                    help="halo mode: band = one stitch launch per band instead of one pass per T x T block it touches")
     ap.add_argument("--passes", type=int, default=1, help="run the shard this many times; the last pass is reported")
     ap.add_argument("--dump", default="", help="rank 0 writes the finished products (mean, std, good) to this .npz: the gathered "
                                                "rows with --gather, else its own rows (tests compare them across process counts)")
@@ -154,7 +159,8 @@ def main():
         t0 = time.perf_counter()
         torch.cuda.reset_peak_memory_stats()
         st = hs.haloAccumulate(shard_rank, shard_world, band_rows=args.band_rows or None,
-                               band_bytes=int(args.band_gib * (1 << 30)), max_rows=args.max_rows)
+                               band_bytes=int(args.band_gib * (1 << 30)), max_rows=args.max_rows,
+                               batching=args.batching, accumulate=args.accumulate)
         torch.cuda.synchronize()
         t_acc = time.perf_counter() - t0
         if world > 1:
@@ -180,6 +186,7 @@ def main():
         if args.dump and rank == 0:
             np.savez(args.dump, mean=m.cpu().numpy(), std=sd.cpu().numpy(), good=g.cpu().numpy(), own=np.array([own_lo, own_hi]))
         nv, nc = hs.last_counts_halo
+        stitch_s = hs.bandStitchSeconds()
         tot = torch.tensor([nv, nc], dtype=torch.float64, device="cuda")
         mx = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         if world > 1:
@@ -192,6 +199,9 @@ def main():
                 "shard": [shard_rank, shard_world], "patches": int(tot[0]), "generator_calls": int(tot[1]),
                 "seconds": float(mx[0]), "seconds_accumulate_rank0": t_acc, "seconds_exchange_and_finalize_rank0": t_ex,
                 "band_rows": hs.last_band_rows, "max_rows": args.max_rows,
+                "batching": args.batching, "accumulate": args.accumulate, "bands_rank0": len(stitch_s),
+                "stitch_seconds_per_band_rank0": sum(stitch_s) / max(1, len(stitch_s)),
+                "stitch_seconds_rank0": sum(stitch_s),
                 "peak_torch_allocated_gb_rank0": torch.cuda.max_memory_allocated() / 1e9,
                 "device_memory_in_use_gb_rank0": (total_b - free_b) / 1e9,
                 "patches_per_s": float(tot[0]) / float(mx[0]),
