@@ -239,16 +239,33 @@ _E2M3 = torch.tensor([i / 8 for i in range(8)] + [1 + i / 8 for i in range(8)] +
                      [4 + i / 2 for i in range(8)], dtype=torch.float64)
 
 
-def _e2m3_codes(q: torch.Tensor) -> torch.Tensor:
-    """|q| <= 7.5 (float64) -> 6-bit codes (uint8), round to nearest (ties to the even code, as the hardware converter)."""
+E2M3_TIE_RULES = ("even", "odd", "away", "zero")
+
+
+def _e2m3_codes(q: torch.Tensor, ties: str = "even", with_ties: bool = False):
+    """|q| <= 7.5 (float64) -> 6-bit codes (uint8), round to nearest.  A quotient that sits exactly on the midpoint of two
+    codes goes to the even code (``ties="even"``: msr_f32_to_e2m3, the host side of the weight upload), to the other one
+    ("odd": no converter's rule, the opposite of "even" on every tie), to the larger magnitude ("away") or the smaller
+    ("zero").  The hardware converter v_cvt_scalef32_2xpk16_fp6_f32 rounds ties to EVEN as well: measured on an MI355X by
+    tests/test_gpu_gbr_terms.py::test_tie_rule_of_the_fp6_converter (inputs with 2 % exact midpoints; the isolated cross terms
+    of conv_gb_resident meet their rounding bound under "even" and miss it several hundred times over under the other three).
+    ``with_ties``: also the bool mask of the tie elements and the distance of their two candidate codes in quotient units
+    (float64, zero off the ties)."""
+    if ties not in E2M3_TIE_RULES:
+        raise ValueError(f"_e2m3_codes: ties is one of {E2M3_TIE_RULES}")
     grid = _E2M3.to(q.device)
     a = q.abs().clamp(max=7.5)
-    idx = torch.bucketize(a, (grid[1:] + grid[:-1]) / 2, right=False)
-    # a tie sits exactly on a midpoint: bucketize(right=False) puts it in the lower bucket; RNE wants the even code
     mid = (grid[1:] + grid[:-1]) / 2
-    tie = (idx < 31) & (a == mid[idx.clamp(max=30)])
-    idx = torch.where(tie & (idx % 2 == 1), idx + 1, idx)
-    return (idx.to(torch.uint8) | ((q < 0) & (a > 0)).to(torch.uint8) * 32).to(torch.uint8)
+    idx = torch.bucketize(a, mid, right=False)
+    # a tie sits exactly on a midpoint: bucketize(right=False) puts it in the lower bucket
+    lo = idx.clamp(max=30)
+    tie = (idx < 31) & (a == mid[lo])
+    up = {"even": idx % 2 == 1, "odd": idx % 2 == 0, "away": torch.ones_like(tie), "zero": torch.zeros_like(tie)}[ties]
+    idx = torch.where(tie & up, idx + 1, idx)
+    codes = (idx.to(torch.uint8) | ((q < 0) & (a > 0)).to(torch.uint8) * 32).to(torch.uint8)
+    if not with_ties:
+        return codes
+    return codes, tie, torch.where(tie, grid[lo + 1] - grid[lo], torch.zeros_like(a))
 
 
 def _pack6(codes: torch.Tensor) -> torch.Tensor:
@@ -300,6 +317,40 @@ def f16c6_activation_image(x: torch.Tensor):
     dec = lambda c: torch.where(c >= 32, -_E2M3.to(c.device)[(c & 31).long()], _E2M3.to(c.device)[(c & 31).long()])   # noqa: E731
     img = _f16c6_pack(hi, ch, 127 + E, cl, 127 + E - 11)
     return img, (hi.double(), (dec(ch) * s).reshape(shp), (dec(cl) * s / 2048.0).reshape(shp))
+
+
+def block_e8m0(amax: torch.Tensor) -> torch.Tensor:
+    """csrc/kernels.h msr_block_e8m0_dev bit for bit: fp32 block maxima -> the e8m0 byte (int64) of the block scale.  The
+    device multiplies by float32(1 / 7.5) and lets a non-zero mantissa carry into the exponent; a maximum whose exact
+    quotient sits within an ulp of a power of two may land a binade away from _ceil_log2_over's answer."""
+    a = amax.to(torch.float32)
+    inv = torch.ones((), dtype=torch.float32, device=a.device) / torch.full((), 7.5, dtype=torch.float32, device=a.device)
+    bits = (a * inv).contiguous().view(torch.int32).to(torch.int64) + 0x7FFFFF
+    eb = (bits >> 23) & 0xFF
+    eb = torch.where(a > 0, eb, torch.full_like(eb, 127))
+    return eb.clamp(27, 247)
+
+
+def gbr_embedding_pieces(e: torch.Tensor, ties: str = "even"):
+    """What phase 1 of conv_gb_resident (csrc/conv_gbr.hip) leaves in its LDS planes for the fp32 embedding ``e`` [..., 128]
+    (already relu'd, zero outside the image): hi = f16_rn(e), and per pixel and 32-channel chunk the scale byte
+    eb = block_e8m0(max e), h6 = e2m3(e / 2^(eb - 127)), l6 = e2m3((e - hi) / 2^(eb - 11 - 127)).  Returns a dict of float64
+    tensors shaped like ``e``: hi, h6, l6 (pieces multiplied by their scales), tie_h6 / tie_l6 (zero, or at an element whose
+    quotient is an exact midpoint the distance of its two candidate values: the tie rule of v_cvt_scalef32_2xpk16_fp6_f32
+    decides between them; ``ties`` is the rule used here, see _e2m3_codes), and eb [..., 4] (int64).  The order of a chunk's
+    channels (GBR_PERM) does not enter: a chunk shares one scale."""
+    shp = e.shape
+    n = shp[-1] // 32
+    e = e.to(torch.float32)
+    hi = e.to(torch.float16)
+    lo = (e - hi.float()).double().reshape(shp[:-1] + (n, 32))            # exact in fp32: the kernel's la / lb
+    eb = block_e8m0(e.reshape(shp[:-1] + (n, 32)).amax(-1))
+    sh, sl = _pow2(eb - 127)[..., None], _pow2(eb - 11 - 127)[..., None]
+    ch, th, dh = _e2m3_codes(e.double().reshape(lo.shape) / sh, ties, True)
+    cl, tl, dl = _e2m3_codes(lo / sl, ties, True)
+    dec = lambda c: torch.where(c >= 32, -_E2M3.to(c.device)[(c & 31).long()], _E2M3.to(c.device)[(c & 31).long()])   # noqa: E731
+    return dict(hi=hi.double(), h6=(dec(ch) * sh).reshape(shp), l6=(dec(cl) * sl).reshape(shp), tie_h6=(dh * sh).reshape(shp),
+                tie_l6=(dl * sl).reshape(shp), eb=eb)
 
 
 def f16c6_weight_image(w_kl: torch.Tensor):
@@ -438,16 +489,25 @@ def conv3x3_f16c(ctx: OpContext, x_img: torch.Tensor, w_img: torch.Tensor, wexp:
 GBR_PERM = [8 * (e >> 3) + 4 * (e & 1) + ((e >> 1) & 3) for e in range(32)]   # csrc/conv_gbr.hip: position e <- channel
 
 
-def gbr_weight_image(w_kl: torch.Tensor) -> torch.Tensor:
-    """gamma|beta weights [9][N][128] (kernel layout, spade_layout rows) -> the weight STREAM conv_gb_resident reads: the f16c6
-    image with the input channels of every 32-chunk in the kernel's position order, re-ordered into the order its waves load
-    it: [channel block nt][wave q][tap pair P][column block j][piece][lane] x 16 bytes (csrc/conv_gbr.hip, weight_images.hip
-    gbr_weight_stream).  Returned as float32 storage [9][N][128] (same byte count)."""
-    N = w_kl.shape[1]
-    idx = torch.tensor([32 * c + GBR_PERM[e] for c in range(w_kl.shape[2] // 32) for e in range(32)], device=w_kl.device)
-    img = f16c6_weight_image(w_kl[:, :, idx].contiguous())[0]
+def gbr_channel_order(cin: int = 128, device=None) -> torch.Tensor:
+    """Input channel held by every position of the resident kernel's operands: position 32 c + e <- channel 32 c + GBR_PERM[e]."""
+    return torch.tensor([32 * c + GBR_PERM[e] for c in range(cin // 32) for e in range(32)], device=device)
+
+
+def gbr_weight_perm_image(w_kl: torch.Tensor):
+    """Step 1 of gbr_weight_image: gamma|beta weights [9][N][128] (kernel layout, spade_layout rows) -> (the f16c6 weight image
+    with the input channels of every 32-chunk in the kernel's position order, its de-quantised (hi, h6, l6) parts in that
+    order).  This is the image whose fp16 plane, codes and scale bytes (88: l6, 120: h6) a test may edit before step 2."""
+    return f16c6_weight_image(w_kl[:, :, gbr_channel_order(w_kl.shape[2], w_kl.device)].contiguous())
+
+
+def gbr_weight_stream(img: torch.Tensor) -> torch.Tensor:
+    """Step 2 of gbr_weight_image: the f16c6 weight image [9][N][128] (float32 storage) re-ordered into the order the waves of
+    conv_gb_resident load it: [channel block nt][wave q][tap pair P][column block j][piece][lane] x 16 bytes
+    (csrc/conv_gbr.hip, weight_images.hip gbr_weight_stream).  Same shape and byte count."""
+    N = img.shape[1]
     rec = img.contiguous().view(torch.uint8).reshape(9, N, 4, 128)                 # [tap][row][chunk][128 bytes]
-    dev = w_kl.device
+    dev = img.device
     nt, q, P, j, piece, lane = torch.meshgrid(torch.arange(N // 128), torch.arange(4), torch.arange(18), torch.arange(2),
                                               torch.arange(4), torch.arange(64), indexing="ij")
     px, cg = lane & 15, lane >> 4
@@ -458,6 +518,37 @@ def gbr_weight_image(w_kl: torch.Tensor) -> torch.Tensor:
     byte = off.to(dev)[..., None] + torch.arange(16, device=dev)
     out = rec[tap[..., None], row.to(dev)[..., None], chunk[..., None], byte]        # [..., 16] bytes
     return out.contiguous().reshape(-1).view(torch.float32).reshape(9, N, 128)
+
+
+def gbr_weight_image(w_kl: torch.Tensor) -> torch.Tensor:
+    """gamma|beta weights [9][N][128] (kernel layout, spade_layout rows) -> the weight STREAM conv_gb_resident reads:
+    gbr_weight_stream(gbr_weight_perm_image(w_kl)).  Returned as float32 storage [9][N][128] (same byte count)."""
+    return gbr_weight_stream(gbr_weight_perm_image(w_kl)[0])
+
+
+def f16c6_weight_keep(w_img: torch.Tensor, hi: bool = True, h6: bool = True, l6: bool = True, rows=None, lift: int = 0):
+    """A copy of an f16c6 WEIGHT image [taps][N][Cin] with pieces zeroed: the fp16 plane (bytes 0..63 of a chunk), the l6 codes
+    (64..87) or the h6 codes (96..119); the scale bytes stay.  ``rows``: bool [N], rows to keep at all (the others lose all
+    three pieces).  ``lift``: binades added to both scale bytes (88, 120) of every row, so that a cross term that is handed
+    to a kernel alone comes out on the main term's scale (2^lift times the term, exact).  f16c6_weight_decode of the result
+    is what the kernel then multiplies."""
+    shp = w_img.shape
+    b = w_img.contiguous().view(torch.uint8).reshape(shp[0], shp[1], shp[2] // 32, 128).clone()
+    if not hi:
+        b[..., 0:64] = 0
+    if not l6:
+        b[..., 64:88] = 0
+    if not h6:
+        b[..., 96:120] = 0
+    if rows is not None:
+        drop = ~rows.to(b.device)
+        b[:, drop, :, 0:88] = 0
+        b[:, drop, :, 96:120] = 0
+    if lift:
+        s = b[..., [88, 120]].to(torch.int64) + lift
+        _check_e8m0(s, "f16c6_weight_keep")
+        b[..., 88], b[..., 120] = s[..., 0].to(torch.uint8), s[..., 1].to(torch.uint8)
+    return b.reshape(shp[0], shp[1], -1).view(torch.float32).reshape(shp)
 
 
 def spade_gbr(ctx: OpContext, src: torch.Tensor, we: torch.Tensor, be: torch.Tensor, w_img: torch.Tensor, bias: torch.Tensor,

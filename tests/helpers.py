@@ -255,3 +255,149 @@ def later_round_mask(B, r, N, n_cu, walk=True, pick=None, new_block=False):
                 continue
             mask[tmi // (ty * ty), (tmi // ty) % ty, tmi % ty, tn] = True
     return mask
+
+
+# ---- conv_gb_resident (csrc/conv_gbr.hip): work decomposition, exact-embedding inputs, term references ------------------------
+def gbr_ranges(B, r, N):
+    """Host restatement of conv_gbr_ranges (csrc/conv_gbr.hip, MSR_GBR unset) -> (the planner's answer, 0 = not a layer for
+    the resident kernel; what the test entries msr_op_spade_gbr* launch with: the entry falls back to 1)."""
+    if r < 16 or (r & (r - 1)) or N % 128:
+        return 0, 1
+    tiles_p, tiles_n = B * (r // 16) * (r // 16), N // 128
+    ranges = 1
+    while tiles_p * ranges < 256 and ranges * 2 <= tiles_n and tiles_n % (ranges * 2) == 0:
+        ranges *= 2
+    if tiles_p * ranges < 128 or (tiles_n // ranges < 2 and tiles_p * ranges < 256 and r > 16):
+        return 0, 1
+    return ranges, ranges
+
+
+def gbr_work(B, r, N, n_cu):
+    """Host restatement of launch_conv_gbr + the item loop of conv_gb_resident for a launch through the test entries on a device
+    with ``n_cu`` compute units: dict(ranges, nr, items, grid, slots, per_xcd (items of each XCD), rounds (int [items]: how many
+    items the item's workgroup took before it), later (bool [B, r // 16, r // 16, N // 128]: the (pixel tile, channel block)
+    pairs computed by an item of round >= 1), rng (int [items]), tile (int [items, 3]: b, ty, tx))."""
+    t = r // 16
+    tiles_p, tiles_n = B * t * t, N // 128
+    ranges = gbr_ranges(B, r, N)[1]
+    nr, items = tiles_n // ranges, tiles_p * ranges
+    n_cu = max(n_cu & ~7, 8)
+    grid = (items + 7) & ~7 if items < n_cu else n_cu
+    sr = persistent_item_rounds(items, n_cu)
+    item = np.arange(items)
+    rng, tmi = item // tiles_p, item % tiles_p
+    tile = np.stack([tmi // (t * t), (tmi // t) % t, tmi % t], 1)
+    later = np.zeros((B, t, t, tiles_n), bool)
+    for i in np.nonzero(sr[:, 1] >= 1)[0]:
+        later[tile[i, 0], tile[i, 1], tile[i, 2], rng[i] * nr:(rng[i] + 1) * nr] = True
+    per_xcd = [(items >> 3) + (1 if x < (items & 7) else 0) for x in range(8)]
+    return dict(ranges=ranges, nr=nr, items=items, grid=grid, slots=grid >> 3, per_xcd=per_xcd, rounds=sr[:, 1], later=later,
+                rng=rng, tile=tile)
+
+
+def gbr_exact_inputs(B, S, r, N, seed, w_scale=0.25, bias_scale=0.25, m_lo=2.0 ** -6, shift=0):
+    """Inputs of one SPADE layer for which the operands of conv_gb_resident's sweep are known bit for bit (host tensors):
+      we    [3, 3, 2, 128]: non-zero only at the centre tap of mask channel 0, fp16 values with 2^-3 <= |we| < 1 (normal)
+      be    zero
+      src   [B, S, S, 2]: channel 0 fp16 values with m_lo <= |m| <= 0.5 (uniform in value, random sign; m_lo >= 2^-6), channel 1 arbitrary
+    so that phase 1 computes e = relu(we[ch] * m[pixel]) as ONE exact 22-bit product, whatever its accumulation order, and
+      w     [9][N][128] kernel-layout gamma|beta weights (spade_layout rows), randn * w_scale * logspace(-1.5, 1.5, N) over the
+            columns, bias [N] = randn * bias_scale * the column's scale.
+    -> dict(src, we, be, w, bias, mask [B, r, r] (channel 0 at the resize offsets), e [B, r, r, 128] fp32, exact; x
+    [B, r >> shift, r >> shift, N / 2] = 3 + 2 randn with its per-channel mean and std)."""
+    import torch
+    g = torch.Generator(device="cpu").manual_seed(seed)
+
+    def f16_values(shape, e_lo, e_hi):       # sign * (1 + k / 1024) * 2^e, e_lo <= e < e_hi: 11 significant bits
+        k = torch.randint(0, 1024, shape, generator=g).double()
+        e = torch.randint(e_lo, e_hi, shape, generator=g).double()
+        s = torch.randint(0, 2, shape, generator=g).double() * 2 - 1
+        return (s * (1 + k / 1024) * torch.pow(2.0, e)).float()
+    we = torch.zeros((3, 3, 2, 128))
+    we[1, 1, 0] = f16_values((128,), -3, 0)
+    src = torch.empty((B, S, S, 2))
+    sign = torch.randint(0, 2, (B, S, S), generator=g).float() * 2 - 1
+    src[..., 0] = sign * (m_lo + (0.5 - m_lo) * torch.rand((B, S, S), generator=g)).half().float()        # uniform in value
+    src[..., 1] = torch.rand((B, S, S), generator=g) - 0.5
+    ls = torch.logspace(-1.5, 1.5, N)
+    w = torch.randn((9, N, 128), generator=g) * w_scale * ls[None, :, None]
+    bias = torch.randn(N, generator=g) * bias_scale * ls
+    assert m_lo >= 2.0 ** -6 and float(src[..., 0].abs().min()) >= 2.0 ** -6 and float(src[..., 0].abs().max()) <= 0.5
+    f = S // r
+    mask = src[:, f // 2::f, f // 2::f, 0][:, :r, :r].contiguous()
+    e = torch.relu(we[1, 1, 0][None, None, None, :].double() * mask[..., None].double())
+    assert torch.equal(e.float().double(), e) and torch.equal(we.half().float(), we) and torch.equal(src[..., 0].half().float(), src[..., 0])
+    # the normalised tensor of the epilogue, as test_spade_layer_resident_kernel draws it (drawn last: the rest does not move)
+    x = 3 + 2 * torch.randn((B, r >> shift, r >> shift, N // 2), generator=g)
+    mean = x.mean((0, 1, 2)).contiguous()
+    std = torch.sqrt(x.var((0, 1, 2), unbiased=False) + 1e-5).contiguous()
+    return dict(src=src, we=we, be=torch.zeros(128), w=w, bias=bias, mask=mask, e=e.float(), x=x, mean=mean, std=std)
+
+
+def gbr_x_parts(pieces, order):
+    """ops.gbr_embedding_pieces -> the zero-bordered (hi, h6, l6) operands of f16c_terms, channels in the kernel's position
+    ``order`` (ops.gbr_channel_order), and the zero-bordered tie distances (0, tie_h6, tie_l6) in the same form."""
+    import torch
+    pad = lambda t: pad_hw(t[..., order])       # noqa: E731
+    zero = torch.zeros_like(pieces["hi"])
+    return (tuple(pad(pieces[k]) for k in ("hi", "h6", "l6")), (pad(zero), pad(pieces["tie_h6"]), pad(pieces["tie_l6"])))
+
+
+GBR_SLOPE = float(np.float32(0.2))
+
+
+def gbr_epilogue(gb, rows, bias, nk=None, widen=None):
+    """The SPADE epilogue on gamma|beta columns ``gb`` [B, r, r, len(rows)] of GEMM rows ``rows`` (all gamma rows or all beta
+    rows): leaky_relu(gb + bias[rows]) for beta rows (nk None), leaky_relu((gb + bias[rows]) * nk) for gamma rows, slope =
+    float32(0.2), in gb's dtype.  ``widen``: a per-element allowance on gb; returns (out, the allowance on out): |nk| times
+    it, and the slope times that where the whole interval is negative (leaky relu is linear there, 1-Lipschitz elsewhere)."""
+    import torch
+    v = gb + bias[rows].to(gb.dtype)
+    if nk is not None:
+        v = v * nk.to(gb.dtype)
+    out = torch.where(v >= 0, v, v * torch.tensor(GBR_SLOPE, dtype=gb.dtype, device=gb.device))
+    if widen is None:
+        return out
+    wv = widen if nk is None else widen * nk.to(widen.dtype).abs()
+    return out, torch.where(v + wv < 0, wv * GBR_SLOPE, wv)
+
+
+def spade_rows(C):
+    """GEMM rows of the gamma columns of output channels 0..C-1 (ops.spade_layout: 32 gamma | 32 beta; beta = + 32)."""
+    import torch
+    c = torch.arange(C)
+    return (c // 32) * 64 + c % 32
+
+
+def gbr_spade(gam, bet, bias_g, bias_b, xn, widen=None):
+    """The whole SPADE epilogue in the operands' dtype: leaky_relu((gam + bias_g) * xn + bet + bias_b), slope = float32(0.2).
+    ``widen`` = (allowance on gam, allowance on bet): returns (out, allowance on out) as gbr_epilogue does."""
+    import torch
+    dt = gam.dtype
+    v = (gam + bias_g.to(dt)) * xn.to(dt) + bet + bias_b.to(dt)
+    out = torch.where(v >= 0, v, v * torch.tensor(GBR_SLOPE, dtype=dt, device=v.device))
+    if widen is None:
+        return out
+    wv = widen[0] * xn.to(dt).abs() + widen[1]
+    return out, torch.where(v + wv < 0, wv * GBR_SLOPE, wv)
+
+
+def gbr_term_figures(y, ref, ref32, widen=None):
+    """The per-channel bound of tests/test_gpu_gbr_terms.py for one run.  y: the kernel's hi + lo8; ref: the float64 evaluation
+    of the same terms; ref32: the same in plain fp32 (torch); widen: per-element tie allowance (None: none).
+      bound[c] = (2^-14 + 4 * rel_linf_per_channel(ref32, ref)[c]) * max|ref[..., c]|     (f16c image + K-length allowance)
+    -> dict(err: rel_linf_per_channel(y, ref); share: per channel, the largest |y - ref| / bound; share_wide: the largest
+    |y - ref| / (bound + widen); beyond: per channel, the fraction of elements with |y - ref| > bound + widen;
+    allowance: 4 * the fp32 figure per channel)."""
+    import torch
+    y, ref = torch.as_tensor(y).double(), torch.as_tensor(ref).double()
+    C = ref.shape[-1]
+    rng = ref.abs().reshape(-1, C).amax(0)
+    allow = 4 * torch.as_tensor(rel_linf_per_channel(ref32, ref), device=ref.device)
+    bound = (2.0 ** -14 + allow) * rng
+    err = (y.to(ref.device) - ref).abs().reshape(-1, C)
+    lim = bound[None, :] + (widen.double().reshape(-1, C) if widen is not None else 0)
+    tiny = 1e-300
+    return dict(err=rel_linf_per_channel(y, ref), share=(err / bound.clamp_min(tiny)[None, :]).amax(0).cpu().numpy(),
+                share_wide=(err / lim.clamp_min(tiny)).amax(0).cpu().numpy(), beyond=(err > lim).double().mean(0).cpu().numpy(),
+                allowance=allow.cpu().numpy(), range=rng.cpu().numpy())
