@@ -481,15 +481,23 @@ int msr_debug_moment_forms(msr_handle* h, char* out, int64_t cap);
  * "kind=head_gather in=ws.gen.head.partial out=output B= r=", behind a conv line with epi=5 whose mean names gen.head.wfrag) |
  * moments | moments_slabs | direct; in / wt / wexp / bias / aux
  * / mean / std / out name the op's tensors as msr_debug_tensor knows them ("input", "eps", "output": the call's own tensors,
- * "-": none); conv and gbr lines carry prec, tile, ksplit, wt_frag, no_cross, epi, out_split, ranges (work items per pixel tile
+ * "-": none); conv and gbr lines carry prec, kernel (the kernel the form names: generic | bvgpr | halo | halo16 | pp | sw on conv
+ * lines, gbr on gbr lines), tile, ksplit, wt_frag, no_cross, epi, out_split, ranges (work items per pixel tile
  * of the resident kernel, else 0) and img, the weight image msr_load_weight built (F32, BF16, BF16_FRAG, F16, FP8, F16C, F16C6,
  * GBR); smallcin and norm_act lines carry out_split.  Needs a plan (after the first msr_forward or msr_forward_flops).
  * NUL-terminated; MSR_ERR_INVALID when cap is too small. */
 int msr_debug_conv_forms(msr_handle* h, char* out, int64_t cap);
 /* Debug, read-only: the kernel a whole-tile (no K ranges) f16c launch of msr_op_conv3x3_f16c / of the plan goes to under this
- * process's MSR_F16C_SW, by the launcher's own rule: 1 = the stream kernel (conv_sw.hip), 0 = the ping-pong kernel.
+ * process's MSR_F16C_SW, by the rule that fills the forms' kernel: 1 = the stream kernel (conv_sw.hip), 0 = the ping-pong kernel.
  * cin in channels, epilogue 0 bias | 1 residual | 2 SPADE, out_mode as msr_op_conv3x3_f16c (0, 1, 4, 5). */
 int msr_debug_f16c_kernel(int32_t cin, int32_t epilogue, int32_t out_mode);
+/* Debug, read-only, needs NO device: the form table msr_create would build for cfg (cfg->device is not looked at) under this
+ * process's environment switches, as text.  Rejects what msr_create rejects (MSR_ERR_INVALID, msr_last_error(NULL)).  One line
+ * "<layer> prec= kernel= tile= ksplit= wt_frag= no_cross= img=" per conv (enc.ds2..5, gen.rb<i>.spade_<j>.gb, gen.rb<i>.conv_<j>;
+ * pix2pix: p2p.down2..8, p2p.up1..7; kernel as in msr_debug_conv_forms, gbr for a gamma|beta conv that conv_gb_resident runs),
+ * one line "gen.rb<i>.spade_<j> gbr= ranges= h_split= hslots= a_split= aslots=" per SPADE layer, a last line "head_fused=0|1".
+ * NUL-terminated; MSR_ERR_INVALID when cap is too small (16 KB is enough). */
+int msr_debug_form_table(const msr_config* cfg, char* out, int64_t cap);
 /* ---- activation-range scan ------------------------------------------------------------------------ */
 /* The f16c family (MSR_FLAG_F16C, _F16_MAIN, _FP8, _GB_F16X2) stores the inputs of the big convs in narrow pieces with finite
  * ranges; tests/test_gpu_conv_kernel.py::test_f16c_saturation_regimes states the three regimes of one activation a:

@@ -184,6 +184,52 @@ static int upload_conv_weight(msr_handle* h, const std::string& key, const float
     return upload(h, key + ".wexp", reinterpret_cast<const float*>(wexp.data()), wexp.size());
 }
 
+// The half of msr_create that touches no device: validates cfg and fills the handle's configuration (all that fill_forms reads).
+int msr::configure(msr_handle* h, const msr_config* cfg) {
+    const int S = cfg->image_size, B = cfg->batch_size;
+    if (cfg->variant < MSR_GAUGAN || cfg->variant > MSR_PIX2PIX)
+        return fail(nullptr, MSR_ERR_INVALID, "unknown variant %d", cfg->variant);
+    if (cfg->variant == MSR_PIX2PIX) {
+        if (S != 256) return fail(nullptr, MSR_ERR_INVALID, "pix2pix input is fixed to 256x256 (pix2pix.py:7), got %d", S);
+    } else {
+        if (S < 64 || (S & (S - 1)))
+            return fail(nullptr, MSR_ERR_INVALID, "image_size must be a power of two >= 64, got %d", S);
+        if (cfg->latent_dim <= 0 || cfg->latent_dim % 4)
+            return fail(nullptr, MSR_ERR_INVALID, "latent_dim must be a positive multiple of 4, got %d", cfg->latent_dim);
+    }
+    if (B < 1 || B > 16) return fail(nullptr, MSR_ERR_INVALID, "batch_size must be in [1,16], got %d", B);
+    h->cfg = *cfg;
+    h->S = S; h->B = B; h->L = cfg->latent_dim; h->variant = cfg->variant;
+    h->prec = (cfg->flags & MSR_FLAG_BF16X3) ? PREC_BF16X3 : PREC_F32;
+    h->gb_f16x2 = h->prec == PREC_BF16X3 && (cfg->flags & MSR_FLAG_GB_F16X2);
+    if ((cfg->flags & MSR_FLAG_GB_F16X2) && !(cfg->flags & MSR_FLAG_BF16X3))
+        return fail(nullptr, MSR_ERR_INVALID, "MSR_FLAG_GB_F16X2 needs MSR_FLAG_BF16X3");
+    if ((cfg->flags & MSR_FLAG_FP8) && (!(cfg->flags & MSR_FLAG_BF16X3) || (cfg->flags & MSR_FLAG_GB_F16X2)))
+        return fail(nullptr, MSR_ERR_INVALID, "MSR_FLAG_FP8 goes with MSR_FLAG_BF16X3 alone (the layers it does not cover run bf16x3)");
+    h->fp8 = (cfg->flags & MSR_FLAG_FP8) && cfg->variant != MSR_PIX2PIX;
+    if ((cfg->flags & MSR_FLAG_F16C) && (!(cfg->flags & MSR_FLAG_BF16X3) || (cfg->flags & (MSR_FLAG_GB_F16X2 | MSR_FLAG_FP8))))
+        return fail(nullptr, MSR_ERR_INVALID, "MSR_FLAG_F16C goes with MSR_FLAG_BF16X3 alone (the layers it does not cover run bf16x3)");
+    h->f16c = (cfg->flags & MSR_FLAG_F16C) && cfg->variant != MSR_PIX2PIX;
+    if ((cfg->flags & MSR_FLAG_F16_MAIN) && !(cfg->flags & MSR_FLAG_F16C))
+        return fail(nullptr, MSR_ERR_INVALID, "MSR_FLAG_F16_MAIN modifies MSR_FLAG_F16C");
+    h->f16m = h->f16c && (cfg->flags & MSR_FLAG_F16_MAIN);
+    if ((cfg->flags & MSR_FLAG_CROSS_FP6) && (!(cfg->flags & MSR_FLAG_F16C) || (cfg->flags & MSR_FLAG_F16_MAIN)))
+        return fail(nullptr, MSR_ERR_INVALID, "MSR_FLAG_CROSS_FP6 modifies MSR_FLAG_F16C and does not go with MSR_FLAG_F16_MAIN (which computes no cross terms)");
+    h->cross6 = h->f16c && (cfg->flags & MSR_FLAG_CROSS_FP6);
+    if (cfg->flags & MSR_FLAG_FUSED_HEAD) {
+        if (!(cfg->flags & MSR_FLAG_F16C))
+            return fail(nullptr, MSR_ERR_INVALID, "MSR_FLAG_FUSED_HEAD needs MSR_FLAG_F16C (the head epilogue exists in the f16c stream kernel)");
+        if (cfg->flags & (MSR_FLAG_F16_MAIN | MSR_FLAG_CROSS_FP6))
+            return fail(nullptr, MSR_ERR_INVALID, "MSR_FLAG_FUSED_HEAD does not go with MSR_FLAG_F16_MAIN or MSR_FLAG_CROSS_FP6 (they run "
+                        "other instantiations of the stream kernel, which have no head epilogue)");
+        if (cfg->variant == MSR_PIX2PIX)
+            return fail(nullptr, MSR_ERR_INVALID, "MSR_FLAG_FUSED_HEAD serves the SPADE head only, not variant pix2pix");
+        h->fused_head = true;
+    }
+    if (cfg->variant == MSR_PIX2PIX) { h->prec = PREC_F32; h->gb_f16x2 = false; }   // the parity config runs on the fp32 MFMA
+    return MSR_OK;
+}
+
 // ================================================================================================
 extern "C" {
 
@@ -223,18 +269,8 @@ const char* msr_last_error(const msr_handle* h) { return h ? h->err.c_str() : g_
 int msr_create(const msr_config* cfg, msr_handle** out) {
     if (!cfg || !out) return fail(nullptr, MSR_ERR_INVALID, "msr_create: null argument");
     *out = nullptr;
-    const int S = cfg->image_size, B = cfg->batch_size;
-    if (cfg->variant < MSR_GAUGAN || cfg->variant > MSR_PIX2PIX)
-        return fail(nullptr, MSR_ERR_INVALID, "unknown variant %d", cfg->variant);
-    if (cfg->variant == MSR_PIX2PIX) {
-        if (S != 256) return fail(nullptr, MSR_ERR_INVALID, "pix2pix input is fixed to 256x256 (pix2pix.py:7), got %d", S);
-    } else {
-        if (S < 64 || (S & (S - 1)))
-            return fail(nullptr, MSR_ERR_INVALID, "image_size must be a power of two >= 64, got %d", S);
-        if (cfg->latent_dim <= 0 || cfg->latent_dim % 4)
-            return fail(nullptr, MSR_ERR_INVALID, "latent_dim must be a positive multiple of 4, got %d", cfg->latent_dim);
-    }
-    if (B < 1 || B > 16) return fail(nullptr, MSR_ERR_INVALID, "batch_size must be in [1,16], got %d", B);
+    auto h = std::make_unique<msr_handle>();
+    if (int rc = configure(h.get(), cfg)) return rc;
     int ndev = 0;
     if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0)
         return fail(nullptr, MSR_ERR_DEVICE, "no HIP device visible: libmoonsr_hip has no CPU fallback");
@@ -254,36 +290,6 @@ int msr_create(const msr_config* cfg, msr_handle** out) {
 #endif
     if (conv_igemm_init() != hipSuccess || conv_gbr_init() != hipSuccess)
         return fail(nullptr, MSR_ERR_DEVICE, "could not set the dynamic-LDS attribute of the conv kernels");
-    auto h = std::make_unique<msr_handle>();
-    h->cfg = *cfg;
-    h->S = S; h->B = B; h->L = cfg->latent_dim; h->variant = cfg->variant;
-    h->prec = (cfg->flags & MSR_FLAG_BF16X3) ? PREC_BF16X3 : PREC_F32;
-    h->gb_f16x2 = h->prec == PREC_BF16X3 && (cfg->flags & MSR_FLAG_GB_F16X2);
-    if ((cfg->flags & MSR_FLAG_GB_F16X2) && !(cfg->flags & MSR_FLAG_BF16X3))
-        return fail(nullptr, MSR_ERR_INVALID, "MSR_FLAG_GB_F16X2 needs MSR_FLAG_BF16X3");
-    if ((cfg->flags & MSR_FLAG_FP8) && (!(cfg->flags & MSR_FLAG_BF16X3) || (cfg->flags & MSR_FLAG_GB_F16X2)))
-        return fail(nullptr, MSR_ERR_INVALID, "MSR_FLAG_FP8 goes with MSR_FLAG_BF16X3 alone (the layers it does not cover run bf16x3)");
-    h->fp8 = (cfg->flags & MSR_FLAG_FP8) && cfg->variant != MSR_PIX2PIX;
-    if ((cfg->flags & MSR_FLAG_F16C) && (!(cfg->flags & MSR_FLAG_BF16X3) || (cfg->flags & (MSR_FLAG_GB_F16X2 | MSR_FLAG_FP8))))
-        return fail(nullptr, MSR_ERR_INVALID, "MSR_FLAG_F16C goes with MSR_FLAG_BF16X3 alone (the layers it does not cover run bf16x3)");
-    h->f16c = (cfg->flags & MSR_FLAG_F16C) && cfg->variant != MSR_PIX2PIX;
-    if ((cfg->flags & MSR_FLAG_F16_MAIN) && !(cfg->flags & MSR_FLAG_F16C))
-        return fail(nullptr, MSR_ERR_INVALID, "MSR_FLAG_F16_MAIN modifies MSR_FLAG_F16C");
-    h->f16m = h->f16c && (cfg->flags & MSR_FLAG_F16_MAIN);
-    if ((cfg->flags & MSR_FLAG_CROSS_FP6) && (!(cfg->flags & MSR_FLAG_F16C) || (cfg->flags & MSR_FLAG_F16_MAIN)))
-        return fail(nullptr, MSR_ERR_INVALID, "MSR_FLAG_CROSS_FP6 modifies MSR_FLAG_F16C and does not go with MSR_FLAG_F16_MAIN (which computes no cross terms)");
-    h->cross6 = h->f16c && (cfg->flags & MSR_FLAG_CROSS_FP6);
-    if (cfg->flags & MSR_FLAG_FUSED_HEAD) {
-        if (!(cfg->flags & MSR_FLAG_F16C))
-            return fail(nullptr, MSR_ERR_INVALID, "MSR_FLAG_FUSED_HEAD needs MSR_FLAG_F16C (the head epilogue exists in the f16c stream kernel)");
-        if (cfg->flags & (MSR_FLAG_F16_MAIN | MSR_FLAG_CROSS_FP6))
-            return fail(nullptr, MSR_ERR_INVALID, "MSR_FLAG_FUSED_HEAD does not go with MSR_FLAG_F16_MAIN or MSR_FLAG_CROSS_FP6 (they run "
-                        "other instantiations of the stream kernel, which have no head epilogue)");
-        if (cfg->variant == MSR_PIX2PIX)
-            return fail(nullptr, MSR_ERR_INVALID, "MSR_FLAG_FUSED_HEAD serves the SPADE head only, not variant pix2pix");
-        h->fused_head = true;
-    }
-    if (cfg->variant == MSR_PIX2PIX) { h->prec = PREC_F32; h->gb_f16x2 = false; }   // the parity config runs on the fp32 MFMA
     build_specs(h.get());
     fill_forms(h.get());
     *out = h.release();

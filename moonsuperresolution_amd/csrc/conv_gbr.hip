@@ -719,21 +719,6 @@ hipError_t conv_gbr_init() {
                                hipFuncAttributeMaxDynamicSharedMemorySize, (int)GB_LDS);
 }
 
-// Work decomposition: a work item = one 16 x 16 pixel tile x `nr` channel blocks; the N / 128 blocks of a pixel tile are cut
-// into the fewest ranges (a power of two) that give every CU an item.  Returns 0 if the layer is not one for this kernel.
-int conv_gbr_ranges(int B, int r, int N) {
-    static const bool off = env_int("MSR_GBR", 1) == 0;
-    if (off || r < 16 || (r & (r - 1)) || N % 128) return 0;
-    const int tiles_p = B * (r / 16) * (r / 16), tiles_n = N / 128;
-    int ranges = 1;
-    while (tiles_p * ranges < 256 && ranges * 2 <= tiles_n && tiles_n % (ranges * 2) == 0) ranges *= 2;
-    if (tiles_p * ranges < 128) return 0;               // too few items even at one block per item
-    // one block per item on half of the CUs: still ahead of the ping-pong K ranges + split-K epilogue + embedding launch at
-    // r = 16 (26 against 38 us at B = 8), not at higher resolution where those launches fill the chip
-    if (tiles_n / ranges < 2 && tiles_p * ranges < 256 && r > 16) return 0;
-    return ranges;
-}
-
 hipError_t launch_conv_gbr(const GbrParams& p, int ranges, hipStream_t s) {
     if (ranges < 1 || p.r < 16 || (p.r & (p.r - 1)) || p.N % 128 || (p.N / 128) % ranges || (p.out_split != OUT_F16C && p.out_split != OUT_F16C6) || !p.src || !p.we16 || !p.be || !p.wt || !p.aux || !p.mean || !p.stdv || !p.out)
         return hipErrorInvalidValue;

@@ -1,16 +1,15 @@
 // conv_igemm — the front door of the NHWC implicit-GEMM convolutions for gfx950: tile geometry, the tile and K-split pickers,
-// the LDS-attribute setup and the precision / tile dispatch.  The kernels live one per unit (conv_generic, conv_bvgpr,
-// conv_halo, conv_pp, conv_sw; split-K pass and moment slabs in conv_splitk), what they share in conv_common.h and
-// conv_epilogue.h.
+// the LDS-attribute setup and the switch from a form's kernel to its launcher (launch_conv).  The kernels live one per unit
+// (conv_generic, conv_bvgpr, conv_halo, conv_pp, conv_sw; split-K pass and moment slabs in conv_splitk), what they share in
+// conv_common.h and conv_epilogue.h.
 #include "conv_common.h"
 
 namespace msr {
 
 void conv_walk_pick(int tiles_m, int tiles_n, int* walk_pb, int* walk_nb) {
-    static const bool off = env_int("MSR_TILE_WALK", 1) == 0;
     *walk_pb = 1;
     *walk_nb = tiles_n;
-    if (!off && tiles_n > 4 && tiles_n % 4 == 0 && tiles_m % 8 == 0) { *walk_pb = 8; *walk_nb = 4; }
+    if (switches().tile_walk && tiles_n > 4 && tiles_n % 4 == 0 && tiles_m % 8 == 0) { *walk_pb = 8; *walk_nb = 4; }
 }
 void conv_walk(TileGeom& g) { conv_walk_pick(g.tiles_x * g.tiles_y * g.tiles_b, g.tiles_n, &g.walk_pb, &g.walk_nb); }
 
@@ -100,17 +99,16 @@ int conv_pick_ksplit(int M, int N, int ksteps, int tile, int prec) {
     return ks;
 }
 
-hipError_t launch_conv_igemm(const ConvParams& p, int epilogue, int tile, hipStream_t s) {
-    if (p.prec == PREC_F16C6) return tile == TILE_256x128_PP ? launch_conv_f16c_sw(p, epilogue, s) : hipErrorInvalidValue;
-    if (p.prec == PREC_F16X2 || p.prec == PREC_FP8 || p.prec == PREC_F16C)
-        return tile == TILE_256x128_PP ? launch_pp(p, epilogue, s) : hipErrorInvalidValue;
-    if (p.prec == PREC_BF16X3) {
-        if (tile == TILE_256x128_PP) return launch_pp(p, epilogue, s);
-        if (tile == TILE_128x128_HALO) return launch_halo(p, epilogue, 0, s);
-        if (tile == TILE_128x128_HALO16) return launch_halo(p, epilogue, 1, s);
-        if (p.wt_frag) return launch_bvgpr(p, epilogue, tile, s);
+hipError_t launch_conv(const ConvParams& p, int epilogue, int kernel, int tile, hipStream_t s) {
+    switch (kernel) {
+        case KERNEL_GENERIC: return launch_generic(p, epilogue, tile, s);
+        case KERNEL_BVGPR: return launch_bvgpr(p, epilogue, tile, s);
+        case KERNEL_HALO: return launch_halo(p, epilogue, 0, s);
+        case KERNEL_HALO16: return launch_halo(p, epilogue, 1, s);
+        case KERNEL_PP: return launch_pp(p, epilogue, s);
+        case KERNEL_SW: return launch_conv_f16c_sw(p, epilogue, s);
     }
-    return launch_generic(p, epilogue, tile, s);      // fp32, and split-bf16 with the LDS-staged weight image
+    return hipErrorInvalidValue;                      // conv_kernel_for's -1: no kernel has the form
 }
 
 }  // namespace msr

@@ -503,14 +503,6 @@ static hipError_t launch_pp_epi(const ConvParams& p, const TileGeom& g, int epi,
     return hipGetLastError();
 }
 
-// conv_sw.hip (one software-pipelined wave per SIMD) takes the long-K main convs; the gamma|beta convs stay here, where
-// a second wave on the SIMD hides their SPADE epilogue.  MSR_F16C_SW = 0: everything here, 2: everything there (A/B).
-bool f16c_whole_tile_on_stream(int Cin, int epi, int out_split) {
-    static const int sw_mode = env_int("MSR_F16C_SW", 1);
-    return Cin % 128 == 0 && !(epi == EPI_SPADE && out_split == OUT_F16C6) &&     // (the fp6 image is written by this kernel's epilogue only)
-           (sw_mode == 2 || (sw_mode == 1 && epi != EPI_SPADE));
-}
-
 hipError_t launch_pp(const ConvParams& p, int epi, hipStream_t s) {
     TileGeom g;
     if (!make_geom(p, 256, 128, 32, g)) return hipErrorInvalidValue;
@@ -541,15 +533,9 @@ hipError_t launch_pp(const ConvParams& p, int epi, hipStream_t s) {
         conv_igemm_bf16x3_pp<EPI_SPADE, PP_F16X2><<<grid, 512, PP_LDS, s>>>(p, g);
         return hipGetLastError();
     }
-    if (p.prec == PREC_F16C) {
-        if (!p.wexp) return hipErrorInvalidValue;
-        if (f16c_whole_tile_on_stream(p.Cin, epi, p.out_split)) return launch_conv_f16c_sw(p, epi, s);
-        return launch_pp_epi<PP_F16C>(p, g, epi, grid, s);
-    }
-    if (p.prec == PREC_FP8) {
-        if (!p.wexp) return hipErrorInvalidValue;
-        return one ? launch_pp_epi<PP_FP8, true>(p, g, epi, grid, s) : launch_pp_epi<PP_FP8>(p, g, epi, grid, s);
-    }
+    if ((p.prec == PREC_F16C || p.prec == PREC_FP8) && !p.wexp) return hipErrorInvalidValue;
+    if (p.prec == PREC_F16C) return launch_pp_epi<PP_F16C>(p, g, epi, grid, s);
+    if (p.prec == PREC_FP8) return one ? launch_pp_epi<PP_FP8, true>(p, g, epi, grid, s) : launch_pp_epi<PP_FP8>(p, g, epi, grid, s);
     return launch_pp_epi<PP_BF16X3>(p, g, epi, grid, s);
 }
 

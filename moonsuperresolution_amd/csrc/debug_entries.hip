@@ -16,6 +16,9 @@ void msr::range_fill(msr_range_stat* o, const std::string& tensor, int format, i
     o->n_nonfinite = (int64_t)r.n_nonfinite;
 }
 
+static const char* const kImg[] = {"F32", "BF16", "BF16_FRAG", "F16", "FP8", "F16C", "F16C6", "GBR"};       // WeightImage
+static const char* const kKernel[] = {"generic", "bvgpr", "halo", "halo16", "pp", "sw"};                     // ConvKernel
+
 extern "C" {
 
 int msr_debug_tensor(msr_handle* h, const char* name, float* host_out, int64_t count) {
@@ -69,7 +72,6 @@ int msr_debug_conv_forms(msr_handle* h, char* out, int64_t cap) {
         const char* nm = name_of(h, ptr);
         return nm ? nm : "?";
     };
-    static const char* kImg[] = {"F32", "BF16", "BF16_FRAG", "F16", "FP8", "F16C", "F16C6", "GBR"};
     auto img_of = [&](const std::string& key) -> const char* {
         auto it = h->dev_img.find(key);
         return it == h->dev_img.end() ? "?" : kImg[it->second];
@@ -81,11 +83,11 @@ int msr_debug_conv_forms(msr_handle* h, char* out, int64_t cap) {
             case OP_CONV: {
                 const ConvParams& c = op.conv;
                 const std::string wt = tensor_of(c.wt);
-                snprintf(b, sizeof b, "kind=conv in=%s wt=%s wexp=%s bias=%s aux=%s mean=%s std=%s out=%s prec=%d tile=%d ksplit=%d "
+                snprintf(b, sizeof b, "kind=conv in=%s wt=%s wexp=%s bias=%s aux=%s mean=%s std=%s out=%s prec=%d kernel=%s tile=%d ksplit=%d "
                          "wt_frag=%d no_cross=%d epi=%d out_split=%d ranges=0 img=%s B=%d r=%d cin=%d N=%d stride=%d aux_shift=%d "
                          "stat_slabs=%d mom=%s\n", tensor_of(c.in).c_str(), wt.c_str(), tensor_of(c.wexp).c_str(),
                          tensor_of(c.bias).c_str(), tensor_of(c.aux).c_str(), tensor_of(c.mean).c_str(), tensor_of(c.stdv).c_str(),
-                         tensor_of(c.out).c_str(), c.prec, op.tile, c.ksplit, c.wt_frag, c.no_cross, op.epi, c.out_split,
+                         tensor_of(c.out).c_str(), c.prec, op.kernel >= 0 ? kKernel[op.kernel] : "none", op.tile, c.ksplit, c.wt_frag, c.no_cross, op.epi, c.out_split,
                          img_of(wt), c.B, c.Hout, c.Cin, c.N, c.stride, c.aux_shift, op.stat_slabs, tensor_of(c.mom_mean).c_str());
                 break;
             }
@@ -93,11 +95,11 @@ int msr_debug_conv_forms(msr_handle* h, char* out, int64_t cap) {
                 const GbrParams& q = op.gbr;
                 const std::string wt = tensor_of(q.wt);
                 snprintf(b, sizeof b, "kind=gbr in=input wt=%s embed=%s embed16=%s embed_bias=%s bias=%s aux=%s mean=%s std=%s out=%s "
-                         "prec=%d tile=%d ksplit=1 wt_frag=0 no_cross=%d epi=%d out_split=%d ranges=%d img=%s B=%d r=%d cin=128 N=%d "
+                         "prec=%d kernel=gbr tile=%d ksplit=1 wt_frag=0 no_cross=%d epi=%d out_split=%d ranges=%d img=%s B=%d r=%d cin=128 N=%d "
                          "stride=1 aux_shift=%d\n", wt.c_str(), tensor_of(q.we).c_str(), tensor_of(q.we16).c_str(),
                          tensor_of(q.be).c_str(), tensor_of(q.bias).c_str(), tensor_of(q.aux).c_str(), tensor_of(q.mean).c_str(),
                          tensor_of(q.stdv).c_str(), tensor_of(q.out).c_str(), (int)PREC_F16C6, (int)TILE_256x128_PP, q.no_cross,
-                         (int)EPI_SPADE, q.out_split, conv_gbr_ranges(q.B, q.r, q.N), img_of(wt), q.B, q.r, q.N, q.aux_shift);
+                         (int)EPI_SPADE, q.out_split, op.gbr_ranges, img_of(wt), q.B, q.r, q.N, q.aux_shift);
                 break;
             }
             case OP_SMALLCIN: {
@@ -149,7 +151,55 @@ int msr_debug_conv_forms(msr_handle* h, char* out, int64_t cap) {
 }
 
 int msr_debug_f16c_kernel(int32_t cin, int32_t epilogue, int32_t out_mode) {
-    return f16c_whole_tile_on_stream(cin, epilogue, epilogue == EPI_SPADE ? out_mode : OUT_F32) ? 1 : 0;
+    return conv_kernel_for(PREC_F16C, TILE_256x128_PP, 1, 0, cin, epilogue, epilogue == EPI_SPADE ? out_mode : OUT_F32) == KERNEL_SW;
+}
+
+int msr_debug_form_table(const msr_config* cfg, char* out, int64_t cap) {
+    if (!cfg || !out || cap < 1) return fail(nullptr, MSR_ERR_INVALID, "msr_debug_form_table: null argument");
+    msr_handle h;
+    int rc = configure(&h, cfg);
+    if (rc) return rc;
+    fill_forms(&h);
+    std::string txt;
+    char b[256];
+    auto conv_line = [&](const char* name, const ConvForm& f, bool gbr = false) {
+        snprintf(b, sizeof b, "%s prec=%d kernel=%s tile=%d ksplit=%d wt_frag=%d no_cross=%d img=%s\n", name, f.prec,
+                 gbr ? "gbr" : f.kernel >= 0 ? kKernel[f.kernel] : "none", f.tile, f.ksplit, f.wt_frag, f.no_cross, kImg[f.img]);
+        txt += b;
+    };
+    char n[96];
+    if (h.variant == MSR_PIX2PIX) {      // the conv_form calls of plan_pix2pix
+        for (int i = 2; i <= 8; ++i) {
+            snprintf(n, sizeof n, "p2p.down%d", i);
+            conv_line(n, conv_form(h.B, 256 >> i, kP2PDown[i - 1], 2, EPI_AFFINE, PREC_F32, kP2PDown[i - 2], 16));
+        }
+        for (int i = 1; i <= 7; ++i) {   // input: the 1 x 1 bottleneck, then the concat buffer [up_(i-1) | down_(9-i)]
+            const int cin = i == 1 ? kP2PDown[7] : kP2PUp[i - 2] + kP2PDown[8 - i];
+            snprintf(n, sizeof n, "p2p.up%d", i);
+            conv_line(n, conv_form(h.B, 1 << (i - 1), kP2PUp[i - 1], 1, EPI_AFFINE, PREC_F32, cin, 4));
+        }
+    } else {
+        for (int i = 2; i <= 5; ++i) {
+            snprintf(n, sizeof n, "enc.ds%d", i);
+            conv_line(n, h.enc_forms[i]);
+        }
+        int cin = 1024;
+        for (int i = 1; i <= 6; cin = kGenFilters[i - 1], ++i)
+            for (int j = 1; j <= (kGenFilters[i - 1] != cin ? 3 : 2); ++j) {
+                const SpadeForm& s = h.spade_forms[i][j];
+                snprintf(n, sizeof n, "gen.rb%d.spade_%d.gb", i, j);
+                conv_line(n, s.gb, s.ranges > 0);
+                snprintf(b, sizeof b, "gen.rb%d.spade_%d gbr=%d ranges=%d h_split=%d hslots=%d a_split=%d aslots=%d\n", i, j,
+                         s.ranges > 0 ? 1 : 0, s.ranges, s.h_split, s.hslots, s.a_split, s.aslots);
+                txt += b;
+                snprintf(n, sizeof n, "gen.rb%d.conv_%d", i, j);
+                conv_line(n, s.cv);
+            }
+    }
+    txt += head_fused_form(&h) ? "head_fused=1\n" : "head_fused=0\n";
+    if ((int64_t)txt.size() + 1 > cap) return fail(nullptr, MSR_ERR_INVALID, "msr_debug_form_table: %zu bytes needed", txt.size() + 1);
+    memcpy(out, txt.c_str(), txt.size() + 1);
+    return MSR_OK;
 }
 
 int msr_range_scan(msr_handle* h, void* stream) {

@@ -1,39 +1,73 @@
-// forms.hip — the form table: which kernel runs every conv layer of the generator and which weight image that kernel reads
-// (conv_form, spade_form, pp_ksplit), fixed by the handle's batch, size and flags.  msr_load_weight and the planner both read
-// it, so a layer's weights are always in the layout its launch expects.
+// forms.hip — the form table: which kernel runs every conv layer of the generator and which weight image that kernel reads,
+// fixed by the handle's batch, size and flags.  msr_load_weight and the planner both read it, so a layer's weights are always in
+// the layout its launch expects.  The ONE unit that chooses a kernel (conv_kernel_for, conv_gbr_ranges) and reads the switches.
 #include "host.h"
 
 namespace msr {
+
+const Switches& switches() {
+    auto on = [](const char* name) { return env_int(name, 1) != 0; };
+    static const int sw = env_int("MSR_F16C_SW", 1);     // fp6 is opt-in, and the A/B dispatches (0, 2) switch it off
+    static const Switches s{on("MSR_PP_KSPLIT"), on("MSR_F16C_KSPLIT"), env_int("MSR_F16C_FP6", 0) == 1 && sw == 1, on("MSR_GBR"),
+                            on("MSR_TILE_WALK"), on("MSR_FUSE_MOMENTS"), on("MSR_SMALLCIN_TILED"), sw};
+    return s;
+}
+
+int conv_kernel_for(int prec, int tile, int ksplit, int wt_frag, int cin, int epi, int out_split) {
+    const bool pp = tile == TILE_256x128_PP;
+    const int sw = switches().f16c_sw;
+    if (epi == EPI_RES_HEAD) return KERNEL_SW;                // the head epilogue exists in the stream kernel only
+    if (prec == PREC_F32) return KERNEL_GENERIC;
+    if (prec == PREC_BF16X3)                                  // by tile; else B fragments in VGPRs or the LDS-staged weight image
+        return pp ? KERNEL_PP : tile == TILE_128x128_HALO ? KERNEL_HALO : tile == TILE_128x128_HALO16 ? KERNEL_HALO16
+                  : wt_frag ? KERNEL_BVGPR : KERNEL_GENERIC;
+    if (!pp || prec < PREC_F16X2 || prec > PREC_F16C6) return -1;   // the quantised forms exist on the 256 x 128 tile only
+    if (prec == PREC_F16C6) return KERNEL_SW;
+    if (prec != PREC_F16C || ksplit > 1) return KERNEL_PP;    // F16X2, FP8; f16c K ranges (+ split-K pass)
+    // f16c whole tiles: conv_sw.hip takes the long-K main convs; the gamma|beta convs stay on the ping-pong kernel, where a second
+    // wave on the SIMD hides their SPADE epilogue (and which alone writes the fp6 image).  MSR_F16C_SW = 0: all there, 2: all here.
+    const bool stream = cin % 128 == 0 && !(epi == EPI_SPADE && out_split == OUT_F16C6) && (sw == 2 || (sw == 1 && epi != EPI_SPADE));
+    return stream ? KERNEL_SW : KERNEL_PP;
+}
+
+// Work decomposition of conv_gb_resident: a work item = one 16 x 16 pixel tile x `nr` channel blocks; the N / 128 blocks of a pixel
+// tile are cut into the fewest ranges (a power of two) that give every CU an item.  0 = the layer is not one for that kernel.
+int conv_gbr_ranges(int B, int r, int N) {
+    if (!switches().gbr || r < 16 || (r & (r - 1)) || N % 128) return 0;
+    const int tiles_p = B * (r / 16) * (r / 16), tiles_n = N / 128;
+    int ranges = 1;
+    while (tiles_p * ranges < 256 && ranges * 2 <= tiles_n && tiles_n % (ranges * 2) == 0) ranges *= 2;
+    if (tiles_p * ranges < 128) return 0;               // too few items even at one block per item
+    // one block per item on half of the CUs: still ahead of the ping-pong K ranges + split-K epilogue + embedding launch at
+    // r = 16 (26 against 38 us at B = 8), not at higher resolution where those launches fill the chip
+    if (tiles_n / ranges < 2 && tiles_p * ranges < 256 && r > 16) return 0;
+    return ranges;
+}
 
 // K split of the persistent ping-pong kernel for layers with fewer 16 x 16 x 128 tiles than CUs: whole chunk pairs
 // per range, a power of two, as many ranges as it takes to give every CU a work item.  0 = the layer is not one for
 // that kernel (it needs stride 1, r >= 16, Cin % 64 == 0, an input below the 2 GiB buffer-descriptor range and, split
 // or not, at least `min_items` work items — below that the small-tile split-K kernels are faster).
 static int pp_ksplit(int B, int rout, int N, int stride, int cin, long min_items = 128) {
-    static const bool off = env_int("MSR_PP_KSPLIT", 1) == 0;
     if (stride != 1 || rout < 16 || cin % 64 || N % 128) return 0;
     if ((size_t)B * (rout + 2) * (rout + 2) * cin * sizeof(float) >= ((size_t)1 << 31)) return 0;
     const long tiles = (long)B * (rout / 16) * (rout / 16) * (N / 128);
     if (tiles >= 256) return 1;
-    if (off) return 0;
+    if (!switches().pp_ksplit) return 0;
     const int pairs = cin / 64;
     int ks = 1;
     while (tiles * ks * 2 <= 256 && pairs % (ks * 2) == 0) ks *= 2;
     return tiles * ks >= min_items ? ks : 0;
 }
 
-// A conv form; its weight image follows from the precision (and, under bf16x3, from the fragment order).
-ConvForm make_form(int prec, int tile, int ksplit, int wt_frag, int no_cross) {
+// A conv form.  Its kernel follows from the rule above (cin: float slots per pixel of its input; out_split: the image an
+// EPI_SPADE epilogue writes), its weight image from the precision (and, under bf16x3, from the fragment order).
+ConvForm make_form(int prec, int tile, int ksplit, int cin, int epi, int out_split, int wt_frag, int no_cross) {
     ConvForm f;
     f.prec = prec; f.tile = tile; f.ksplit = ksplit; f.wt_frag = wt_frag; f.no_cross = no_cross;
-    switch (prec) {
-        case PREC_BF16X3: f.img = wt_frag ? IMG_BF16_FRAG : IMG_BF16; break;
-        case PREC_F16X2: f.img = IMG_F16; break;
-        case PREC_FP8: f.img = IMG_FP8; break;
-        case PREC_F16C: f.img = IMG_F16C; break;
-        case PREC_F16C6: f.img = IMG_F16C6; break;
-        default: f.img = IMG_F32;
-    }
+    f.kernel = conv_kernel_for(prec, tile, ksplit, wt_frag, cin, epi, out_split);
+    static const WeightImage kImage[] = {IMG_F32, IMG_BF16, IMG_F16, IMG_FP8, IMG_F16C, IMG_F16C6};   // by ConvPrecision
+    f.img = prec == PREC_BF16X3 && wt_frag ? IMG_BF16_FRAG : kImage[prec];
     return f;
 }
 
@@ -61,20 +95,13 @@ ConvForm conv_form(int B, int rout, int N, int stride, int epi, int prec, int ci
             ksplit = 1;
         }
     }
-    return make_form(prec, tile, ksplit > 0 ? ksplit : conv_pick_ksplit(M, N, ksteps, tile, prec), wt_frag);
+    return make_form(prec, tile, ksplit > 0 ? ksplit : conv_pick_ksplit(M, N, ksteps, tile, prec), cin, epi, OUT_F32, wt_frag);
 }
 
-// out_split of a producer whose output feeds a conv in `prec`: the operand image that conv reads
-static int split_for(int prec) {
-    switch (prec) {
-        case PREC_BF16X3: return OUT_BF16X3;
-        case PREC_F16X2: return OUT_F16X2;
-        case PREC_FP8: return OUT_BF8;
-        case PREC_F16C: return OUT_F16C;
-        case PREC_F16C6: return OUT_F16C6;
-        default: return OUT_F32;
-    }
-}
+// out_split of a producer whose output feeds a conv in `prec`: the operand image that conv reads (kernels.h: the OutFormat of
+// the same number)
+static int split_for(int prec) { return prec; }
+static_assert(OUT_BF16X3 == PREC_BF16X3 && OUT_F16X2 == PREC_F16X2 && OUT_BF8 == PREC_FP8 && OUT_F16C == PREC_F16C && OUT_F16C6 == PREC_F16C6, "");
 
 // Form of the SPADE layer that normalises C channels at resolution r, and of the conv C -> cout (epilogue epi) it feeds.
 // Under the quantised modes a conv takes the quantised form when it runs the persistent ping-pong kernel, and a consumer
@@ -98,41 +125,40 @@ static int split_for(int prec) {
 //  * MSR_FLAG_GB_F16X2: a gamma|beta conv that runs the ping-pong kernel on whole tiles takes 2-term fp16 products (the
 //    K-split launches run the 3-term form).
 static SpadeForm spade_form(const msr_handle* h, int r, int C, int cout, int epi) {
-    static const bool f16c_ks_off = env_int("MSR_F16C_KSPLIT", 1) == 0;
-    static const bool fp6_on = env_int("MSR_F16C_FP6", 0) == 1 && env_int("MSR_F16C_SW", 1) == 1;
-    const int B = h->B;
+    const Switches& sw = switches();
+    const int B = h->B, PP = TILE_256x128_PP;
     auto fills = [&](int N) { return r >= 16 && N % 128 == 0 && (long)B * (r / 16) * (r / 16) * (N / 128) >= 256; };
-    auto f16c_pp = [&](int N, int cin) { return f16c_ks_off ? fills(N) : pp_ksplit(B, r, N, 1, cin) >= 1; };
+    auto f16c_pp = [&](int N, int cin) { return sw.f16c_ksplit ? pp_ksplit(B, r, N, 1, cin) >= 1 : fills(N); };
     const bool gb8 = h->fp8 && fills(2 * C), cv8 = gb8 && fills(cout);
     const bool gbc = h->f16c && f16c_pp(2 * C, 128), cvc = gbc && C % 64 == 0 && f16c_pp(cout, C);
-    static const bool sw_on = env_int("MSR_F16C_SW", 1) == 1;      // the f16c6 consumer is the stream kernel
-    const bool cv6 = cvc && (fp6_on || (h->cross6 && sw_on)) && C % 128 == 0 && fills(cout) && fills(2 * C);
     SpadeForm s;
-    s.gbr = cvc && (!cv6 || h->cross6) && conv_gbr_ranges(B, r, 2 * C) > 0;
+    s.hslots = gb8 ? fp8_pad(128) / 4 : 128;
+    s.aslots = cv8 ? fp8_pad(C) / 4 : C;
+    // The consumer first: its precision is the image the gamma|beta epilogue writes, and that conv's kernel depends on it.
+    // The f16 mode asks for no cross terms on whole tiles, the stream kernel's form: a K-range launch runs the ping-pong
+    // kernel, which has no such form and computes them (and so do whole tiles under MSR_F16C_SW=0: DESIGN.md, open follow-up).
+    const int ks = pp_ksplit(B, r, cout, 1, C);
+    const ConvForm cvf = make_form(PREC_F16C, PP, ks, C, epi, OUT_F32, 0, h->f16m && ks == 1);
+    // the f16c6 consumer is the stream kernel, and only under the default dispatch (MSR_F16C_SW=1)
+    const bool cv6 = cvc && (sw.f16c_fp6 || (h->cross6 && sw.f16c_sw == 1)) && cvf.kernel == KERNEL_SW && fills(cout) && fills(2 * C);
+    if (cv8) s.cv = make_form(PREC_FP8, PP, 1, s.aslots, epi);
+    else if (cv6) s.cv = make_form(PREC_F16C6, PP, 1, C, epi);
+    else if (cvc) s.cv = cvf;
+    else s.cv = conv_form(B, r, cout, 1, epi, h->prec, C);
+    s.a_split = split_for(s.cv.prec);
+    s.ranges = cvc && (!cv6 || h->cross6) ? conv_gbr_ranges(B, r, 2 * C) : 0;
     if (gb8) {
-        s.gb = make_form(PREC_FP8, TILE_256x128_PP, 1);
-    } else if (s.gbr) {
-        s.gb = make_form(PREC_F16C6, TILE_256x128_PP, 1, 0, h->f16m);
+        s.gb = make_form(PREC_FP8, PP, 1, s.hslots, EPI_SPADE, s.a_split);
+    } else if (s.ranges > 0) {
+        s.gb = make_form(PREC_F16C6, PP, 1, 128, EPI_SPADE, s.a_split, 0, h->f16m);   // (its kernel is conv_gb_resident, not .kernel)
         s.gb.img = IMG_GBR;
     } else if (gbc) {
-        s.gb = make_form(PREC_F16C, TILE_256x128_PP, pp_ksplit(B, r, 2 * C, 1, 128));   // > 1: K ranges
+        s.gb = make_form(PREC_F16C, PP, pp_ksplit(B, r, 2 * C, 1, 128), 128, EPI_SPADE, s.a_split);   // > 1: K ranges
     } else {
         s.gb = conv_form(B, r, 2 * C, 1, EPI_SPADE, h->prec, 128);
-        if (h->gb_f16x2 && s.gb.tile == TILE_256x128_PP && s.gb.ksplit == 1) s.gb = make_form(PREC_F16X2, TILE_256x128_PP, 1);
+        if (h->gb_f16x2 && s.gb.kernel == KERNEL_PP && s.gb.ksplit == 1) s.gb = make_form(PREC_F16X2, PP, 1, 128, EPI_SPADE, s.a_split);
     }
-    if (cv8) s.cv = make_form(PREC_FP8, TILE_256x128_PP, 1);
-    else if (cv6) s.cv = make_form(PREC_F16C6, TILE_256x128_PP, 1);
-    else if (cvc) {
-        // the f16 mode leaves the cross terms out on the stream kernel (whole tiles) only: a K-range launch runs the
-        // ping-pong kernel, which has no such form and computes them
-        const int ks = pp_ksplit(B, r, cout, 1, C);
-        s.cv = make_form(PREC_F16C, TILE_256x128_PP, ks, 0, h->f16m && ks == 1);
-    }
-    else s.cv = conv_form(B, r, cout, 1, epi, h->prec, C);
     s.h_split = split_for(s.gb.prec);
-    s.hslots = gb8 ? fp8_pad(128) / 4 : 128;
-    s.a_split = split_for(s.cv.prec);
-    s.aslots = cv8 ? fp8_pad(C) / 4 : C;
     return s;
 }
 
@@ -155,11 +181,10 @@ void fill_forms(msr_handle* h) {
 // takes it when it runs there on whole tiles in the plain f16c form.  Anywhere else (K ranges on the ping-pong kernel at small
 // shapes, MSR_F16C_SW other than 1) the plan keeps the separate head: a fallback, not an error.
 bool head_fused_form(const msr_handle* h) {
-    static const bool sw_on = env_int("MSR_F16C_SW", 1) == 1;
-    if (!h->fused_head || h->variant == MSR_PIX2PIX || !sw_on) return false;
+    if (!h->fused_head || h->variant == MSR_PIX2PIX || switches().f16c_sw != 1) return false;
     const ConvForm& cv = h->spade_forms[6][2].cv;
     const int r = h->S / 2;
-    return cv.prec == PREC_F16C && cv.tile == TILE_256x128_PP && cv.ksplit == 1 && !cv.no_cross && kGenFilters[5] == 128 &&
+    return cv.kernel == KERNEL_SW && cv.prec == PREC_F16C && cv.ksplit == 1 && !cv.no_cross && kGenFilters[5] == 128 &&
            r >= 16 && (r & (r - 1)) == 0;
 }
 

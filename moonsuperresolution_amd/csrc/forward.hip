@@ -90,8 +90,7 @@ static int launch_all(msr_handle* h, const float* in_dev, const float* eps_dev, 
                 cp.partial = h->conv_partial;
                 cp.mom_partial = h->mom_partial;
                 cp.stat_partial = op.stat_slabs > 0 ? h->stat_ws : nullptr;
-                // the head epilogue exists in the stream kernel only: no dispatch that could send it elsewhere
-                e = op.epi == EPI_RES_HEAD ? launch_conv_f16c_sw(cp, op.epi, s) : launch_conv_igemm(cp, op.epi, op.tile, s);
+                e = launch_conv(cp, op.epi, op.kernel, op.tile, s);
                 break;
             }
             case OP_SMALLCIN: {
@@ -134,7 +133,7 @@ static int launch_all(msr_handle* h, const float* in_dev, const float* eps_dev, 
                 fam = FAM_CONV;
                 GbrParams q = op.gbr;
                 q.src = in_dev;
-                e = launch_conv_gbr(q, conv_gbr_ranges(q.B, q.r, q.N), s);
+                e = launch_conv_gbr(q, op.gbr_ranges, s);
                 break;
             }
             case OP_DIRECT: {

@@ -57,10 +57,11 @@ struct Op {
     hipEvent_t done = nullptr;        // recorded on the auxiliary stream after an on_aux op
     hipEvent_t wait = nullptr;        // the main stream waits for this before launching the op
     int aux_group = -1;               // on_aux ops and their consumers: one event / one wait per group
-    ConvParams conv{}; int epi = 0, tile = 0;
+    ConvParams conv{}; int epi = 0, tile = 0, kernel = KERNEL_GENERIC;   // the form's ConvKernel and tile geometry
     int stat_slabs = 0;               // > 0: the conv's epilogue also writes partial output moments (fused)
     SmallCinParams sc{};
-    GbrParams gbr{};                  // OP_GBR: mask embedding + gamma|beta conv + SPADE epilogue in one launch (conv_gbr.hip)
+    GbrParams gbr{}; int gbr_ranges = 0;   // OP_GBR: mask embedding + gamma|beta conv + SPADE epilogue in one launch (conv_gbr.hip)
+                                           // in the SpadeForm's `ranges` work items per pixel tile
     struct { const float* x; int G, P, C; float eps; float* mean; float* stdv; } mom{};
     NormActParams na{};
     struct { const float* x; const float* W; const float* bias; float* y; int B, K, N; } dense{};
@@ -84,17 +85,19 @@ enum WeightImage {
     IMG_GBR,         // the weight stream of conv_gb_resident (gbr_weight_stream)
 };
 
-// Form of one conv layer: the kernel that runs it and the weight image that kernel reads.  msr_load_weight and the planner
-// both take it from the handle's form table (fill_forms), so a layer's weights are always in the layout its launch expects.
+// Form of one conv layer: the kernel that runs it (a ConvKernel, chosen once by conv_kernel_for; launch_conv switches on it) and
+// the weight image that kernel reads.  msr_load_weight and the planner both take it from the handle's form table (fill_forms),
+// so a layer's weights are always in the layout its launch expects.
 struct ConvForm {
-    int prec = PREC_F32, tile = TILE_64x64, ksplit = 1, wt_frag = 0;
+    int prec = PREC_F32, tile = TILE_64x64, ksplit = 1, wt_frag = 0, kernel = KERNEL_GENERIC;
     int no_cross = 0;                 // f16 mode: the stream / resident kernels leave the cross terms out
     WeightImage img = IMG_F32;
 };
 
 // Form of one SPADE layer of the generator and of the conv it feeds (gen.rbI.spade_J -> gen.rbI.conv_J)
 struct SpadeForm {
-    bool gbr = false;                 // conv_gb_resident: embedding + gamma|beta conv + SPADE epilogue in one launch
+    int ranges = 0;                   // > 0: conv_gb_resident (embedding + gamma|beta conv + SPADE epilogue in one launch), in
+                                      // that many work items per pixel tile (conv_gbr_ranges)
     int h_split = 0, hslots = 128;    // mask embedding (not run under gbr): out_split, float slots per pixel of its output
     ConvForm gb;                      // gamma|beta conv
     int a_split = 0, aslots = 0;      // the format the gamma|beta conv writes for the consumer, float slots per pixel
@@ -182,6 +185,7 @@ namespace msr {
 
 // ---- api.hip: errors and the handle's device buffers ----
 int fail(msr_handle* h, int code, const char* fmt, ...);   // h == nullptr: the error of msr_create
+int configure(msr_handle* h, const msr_config* cfg);       // msr_create's device-free half: validates cfg, fills h's configuration
 
 #define HIPCHK(h, call)                                                                                     \
     do {                                                                                                    \
@@ -216,7 +220,7 @@ std::vector<float> build_head_wfrag(const float* k44c);       // gen.head.wfrag:
 int fp8_pad(int cin);
 
 // ---- forms.hip ----
-ConvForm make_form(int prec, int tile, int ksplit, int wt_frag = 0, int no_cross = 0);
+ConvForm make_form(int prec, int tile, int ksplit, int cin, int epi, int out_split = OUT_F32, int wt_frag = 0, int no_cross = 0);
 ConvForm conv_form(int B, int rout, int N, int stride, int epi, int prec, int cin, int taps = 9);
 void fill_forms(msr_handle* h);
 // MSR_FLAG_FUSED_HEAD is set and gen.rb6.conv_2 runs the whole-tile stream-kernel form the head epilogue exists for

@@ -18,12 +18,16 @@
 
 namespace msr {
 
-// Integer value of an environment switch (std::atoi of its text), `unset` when it is not set.  Callers keep the result in
-// a static const, so every switch is read once per process.
+// Integer value of an environment variable (std::atoi of its text), `unset` when it is not set.
 inline int env_int(const char* name, int unset) {
     const char* v = std::getenv(name);
     return v ? std::atoi(v) : unset;
 }
+
+// The behaviour switches (INTEGRATION.md's table), read from the environment once per process by switches() (forms.hip), their
+// one reader.  Unset = on; f16c_fp6 (MSR_F16C_FP6=1, opt-in) counts only while f16c_sw (MSR_F16C_SW's value, unset = 1) is 1.
+struct Switches { bool pp_ksplit, f16c_ksplit, f16c_fp6, gbr, tile_walk, fuse_moments, smallcin_tiled; int f16c_sw; };
+const Switches& switches();
 
 // ---------------------------------------------------------------------------------------------
 // conv_igemm_f32: NHWC implicit-GEMM convolution on v_mfma_f32_32x32x2_f32 (exact fp32).
@@ -84,7 +88,6 @@ struct ConvParams {
     int no_cross = 0;             // PREC_F16C on conv_igemm_f16c_sw only: 1 = leave the cross terms out ("f16" mode)
 };
 hipError_t launch_splitk_epilogue_mom(const ConvParams& p, int epi, hipStream_t s);
-int moments_chunks(int G, int P);
 
 // Split-bf16 operand format ("bf16x3"): tensors keep their fp32 size and addressing, but every aligned group of
 // 32 channels (128 bytes) holds [32 x hi bf16 | 32 x lo bf16] with hi = bf16_rn(v), lo = bf16_rn(v - hi).
@@ -333,23 +336,25 @@ struct GbrParams {
     int no_cross = 0;             // 1 = leave the fp6 cross terms out ("f16" mode)
 };
 hipError_t conv_gbr_init();
-// > 0: the layer runs conv_gb_resident with the channel blocks of a pixel tile cut into that many work items; 0: not a layer
-// for it (MSR_GBR=0 switches the kernel off: A/B runs)
+// forms.hip, the planner's rule.  > 0: the layer runs conv_gb_resident with the channel blocks of a pixel tile cut into that
+// many work items; 0: not a layer for it (MSR_GBR=0 switches the kernel off: A/B runs)
 int conv_gbr_ranges(int B, int r, int N);
-// ranges: work items per pixel tile (a divisor of N / 128); the planner passes conv_gbr_ranges()
+// ranges: work items per pixel tile (a divisor of N / 128); the plan passes the SpadeForm's (conv_gbr_ranges)
 hipError_t launch_conv_gbr(const GbrParams& p, int ranges, hipStream_t s);
 // host: HWIO [3][3][2][128] fp32 -> GbrParams.we16 image (4096 floats of storage)
 void conv_gbr_embed_image(const float* we_hwio, float* out4096);
 
 hipError_t conv_igemm_init();   // sets dynamic-LDS attributes once
-// conv_sw.hip: PREC_F16C whole-tile launches as one software-pipelined wave per SIMD.  launch_conv_igemm sends it the
-// long-K main convs (bias / residual epilogues, Cin % 128 == 0); MSR_F16C_SW = 0 keeps everything on the ping-pong kernel,
-// 2 sends the gamma|beta convs there too (A/B runs)
+// The kernel that runs a conv, one launcher each; a conv's form names it (host.h ConvForm.kernel), `tile` stays the tile geometry
+// of the generic and bvgpr kernels.  conv_kernel_for (forms.hip) is the ONE place that chooses (cin: float slots per pixel;
+// out_split: the image an EPI_SPADE epilogue writes): conv_sw.hip (one software-pipelined wave per SIMD) takes PREC_F16C6, the head
+// epilogue and the whole-tile PREC_F16C main convs (MSR_F16C_SW: 0 = none of those, 2 = the gamma|beta convs too).  -1: no kernel.
+enum ConvKernel : int { KERNEL_GENERIC = 0, KERNEL_BVGPR, KERNEL_HALO, KERNEL_HALO16, KERNEL_PP, KERNEL_SW };
+int conv_kernel_for(int prec, int tile, int ksplit, int wt_frag, int cin, int epilogue, int out_split);
 hipError_t conv_sw_init();
 hipError_t launch_conv_f16c_sw(const ConvParams& p, int epilogue, hipStream_t s);
-// launch_pp's rule for a whole-tile PREC_F16C launch under the process's MSR_F16C_SW: true = the stream kernel takes it
-bool f16c_whole_tile_on_stream(int Cin, int epilogue, int out_split);
-hipError_t launch_conv_igemm(const ConvParams& p, int epilogue, int tile, hipStream_t s);
+// conv_igemm.hip: a plain switch on `kernel`; a launcher that has no instantiation for the form returns hipErrorInvalidValue
+hipError_t launch_conv(const ConvParams& p, int epilogue, int kernel, int tile, hipStream_t s);
 // picks the tile and the K split for a problem size (fills the chip for the low-resolution layers)
 int conv_pick_tile(int M, int N, int epilogue, int prec, int ksteps = 0);
 int conv_pick_ksplit(int M, int N, int ksteps, int tile, int prec = PREC_F32);

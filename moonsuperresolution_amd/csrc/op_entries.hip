@@ -44,10 +44,11 @@ static int op_conv_impl(msr_handle* h, const float* in_dev, const float* wt_dev,
         if (tile & 0x80) op.conv.prec = PREC_F16X2;            // operands are split-fp16 words (ping-pong tile only)
         op.conv.wt_frag = (tile & 0x40) ? 1 : 0;
         op.conv.ksplit = (tile >> 8) > 0 ? (tile >> 8) : 1;    // explicit tile: explicit split (default none)
+        op.kernel = conv_kernel_for(op.conv.prec, op.tile, op.conv.ksplit, op.conv.wt_frag, Cin, epilogue, op.conv.out_split);
     }
     int rc = bind_conv_entry(h, op, out_dev, out_padded, epilogue == EPI_SPADE ? N / 2 : N, aux_dev, aux_shift, mean_dev, std_dev);
     if (rc) return rc;
-    hipError_t e = launch_conv_igemm(op.conv, epilogue, op.tile, (hipStream_t)stream);
+    hipError_t e = launch_conv(op.conv, epilogue, op.kernel, op.tile, (hipStream_t)stream);
     if (e != hipSuccess) return fail(h, MSR_ERR_INVALID, "conv launch rejected (shape not tileable?): %s", hipGetErrorString(e));
     return MSR_OK;
 }
@@ -97,16 +98,17 @@ int msr_op_conv3x3_f16c(msr_handle* h, const float* in_dev, const float* wt_dev,
         return fail(h, MSR_ERR_INVALID, "msr_op_conv3x3_f16c: no-cross takes whole-tile bias / residual launches with Cin %% 128 == 0");
     HIPCHK(h, hipSetDevice(h->cfg.device));
     Padded in; in.base = const_cast<float*>(in_dev); in.r = rout; in.C = Cin;
+    const int out_split = epilogue == EPI_SPADE ? out_mode : OUT_F32;
     Op op = conv_op(in, Cin, wt_dev, bias_dev, B, rout, N, 1, epilogue,
-                    make_form(wexp_dev ? PREC_F16C : PREC_F16C6, TILE_256x128_PP, ksplit > 1 ? ksplit : 1, 0, no_cross));
+                    make_form(wexp_dev ? PREC_F16C : PREC_F16C6, TILE_256x128_PP, ksplit > 1 ? ksplit : 1, Cin, epilogue, out_split, 0, no_cross));
+    // no-cross is the stream kernel's form alone, whatever the rule says: under MSR_F16C_SW = 0 it names the ping-pong kernel,
+    // which has no such form and would silently compute the cross terms
+    if (no_cross) op.kernel = KERNEL_SW;
     op.conv.wexp = wexp_dev;
-    op.conv.out_split = epilogue == EPI_SPADE ? out_mode : OUT_F32;
+    op.conv.out_split = out_split;
     int rc = bind_conv_entry(h, op, out_dev, out_padded, epilogue == EPI_SPADE ? N / 2 : N, aux_dev, aux_shift, mean_dev, std_dev);
     if (rc) return rc;
-    // no-cross goes to the stream kernel directly: launch_pp's MSR_F16C_SW = 0 would send it to the ping-pong kernel, which has
-    // no such form and would silently compute the cross terms
-    hipError_t e = no_cross ? launch_conv_f16c_sw(op.conv, epilogue, (hipStream_t)stream)
-                            : launch_conv_igemm(op.conv, epilogue, op.tile, (hipStream_t)stream);
+    hipError_t e = launch_conv(op.conv, epilogue, op.kernel, op.tile, (hipStream_t)stream);
     if (e != hipSuccess) return fail(h, MSR_ERR_INVALID, "f16c conv launch rejected: %s", hipGetErrorString(e));
     return MSR_OK;
 }
@@ -124,7 +126,7 @@ int msr_op_conv3x3_f16c_head(msr_handle* h, const float* in_dev, const float* wt
     HIPCHK(h, hipSetDevice(h->cfg.device));
     hipStream_t s = (hipStream_t)stream;
     Padded in; in.base = const_cast<float*>(in_dev); in.r = rout; in.C = Cin;
-    Op op = conv_op(in, Cin, wt_dev, bias_dev, B, rout, N, 1, EPI_RES_HEAD, make_form(PREC_F16C, TILE_256x128_PP, 1));
+    Op op = conv_op(in, Cin, wt_dev, bias_dev, B, rout, N, 1, EPI_RES_HEAD, make_form(PREC_F16C, TILE_256x128_PP, 1, Cin, EPI_RES_HEAD));
     op.conv.wexp = wexp_dev;
     const std::vector<float> wfrag = build_head_wfrag(head_kernel_host);
     float *wd = nullptr, *pd = partial_dev;
@@ -137,7 +139,7 @@ int msr_op_conv3x3_f16c_head(msr_handle* h, const float* in_dev, const float* wt
         set_out_dense(op.conv, pd, rout, rout, 32);
         set_aux_dense(op.conv, aux_dev, rout >> aux_shift, N, aux_shift);
         op.conv.mean = wd;
-        e = launch_conv_f16c_sw(op.conv, EPI_RES_HEAD, s);
+        e = launch_conv(op.conv, EPI_RES_HEAD, op.kernel, op.tile, s);
         rejected = e != hipSuccess;
     }
     if (e == hipSuccess) e = launch_head_gather(pd, head_bias, out_dev, B, rout, s);
@@ -328,14 +330,14 @@ int msr_op_conv3x3_fp8(msr_handle* h, const void* in_dev, const void* wt_dev, co
     HIPCHK(h, hipSetDevice(h->cfg.device));
     Padded in; in.base = const_cast<float*>(static_cast<const float*>(in_dev)); in.r = rout; in.C = Cpad / 4;
     Op op = conv_op(in, Cpad, static_cast<const float*>(wt_dev), bias_dev, B, rout, N, 1, epilogue,
-                    make_form(PREC_FP8, TILE_256x128_PP, 1));
+                    make_form(PREC_FP8, TILE_256x128_PP, 1, Cpad / 4, epilogue, epilogue == EPI_SPADE ? out_mode : OUT_F32));
     op.conv.wexp = wexp_dev;
     op.conv.out_split = epilogue == EPI_SPADE ? out_mode : OUT_F32;
     const int Cout = epilogue == EPI_SPADE ? N / 2 : N;
     int rc = bind_conv_entry(h, op, out_dev, out_padded, out_mode == OUT_BF8 ? fp8_pad(Cout) / 4 : Cout, aux_dev, aux_shift, mean_dev,
                              std_dev);
     if (rc) return rc;
-    hipError_t e = launch_conv_igemm(op.conv, epilogue, op.tile, (hipStream_t)stream);
+    hipError_t e = launch_conv(op.conv, epilogue, op.kernel, op.tile, (hipStream_t)stream);
     if (e != hipSuccess) return fail(h, MSR_ERR_INVALID, "fp8 conv launch rejected: %s", hipGetErrorString(e));
     return MSR_OK;
 }

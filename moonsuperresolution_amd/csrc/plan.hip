@@ -14,7 +14,7 @@ static int alloc_padded(msr_handle* h, const std::string& key, int r, int C, Pad
 // output format (out_split) is the caller's: a SPADE output feeds a conv whose form decides it.
 Op conv_op(const Padded& in, int cin, const float* wt, const float* bias, int B, int rout, int N, int stride, int epi,
            const ConvForm& f) {
-    Op op; op.type = OP_CONV; op.epi = epi; op.tile = f.tile;
+    Op op; op.type = OP_CONV; op.epi = epi; op.tile = f.tile; op.kernel = f.kernel;
     ConvParams& c = op.conv;
     c.in = stride == 1 ? in.base : in.base + in.interior();
     c.wt = wt; c.bias = bias;
@@ -37,10 +37,9 @@ static Op moments_op(const float* x, int G, int P, int C, float eps, float* mean
 
 // A split-K conv whose output feeds a normalisation takes the moments in its own epilogue (splitk_epilogue_mom_kernel).
 static bool fuse_moments_into_splitk(Op& cv, int G, float eps, float* mean, float* stdv) {
-    if (cv.type != OP_CONV || cv.conv.ksplit <= 1 || (cv.epi != EPI_BIAS && cv.epi != EPI_RES) || cv.conv.N % 32)
+    if (cv.type != OP_CONV || cv.conv.ksplit <= 1 || (cv.epi != EPI_BIAS && cv.epi != EPI_RES) || cv.conv.N % 32 ||
+        !switches().fuse_moments)
         return false;
-    static const bool off = env_int("MSR_FUSE_MOMENTS", 1) == 0;
-    if (off) return false;
     cv.conv.mom_mean = mean; cv.conv.mom_std = stdv; cv.conv.mom_eps = eps; cv.conv.mom_G = G;
     return true;
 }
@@ -164,10 +163,10 @@ static int plan_spade(msr_handle* h) {
             Padded hb, ab;
             int rc2;
             snprintf(k, sizeof k, "ws.gen.rb%d.a%d", i, j); rc2 = alloc_padded(h, k, r, sf.aslots, &ab); if (rc2) return rc2;
-            if (sf.gbr) {
+            if (sf.ranges > 0) {
                 // conv_gb_resident: the embedding never exists in HBM (no mask-embedding launch, no h buffer); one launch
                 // does resize + embedding + gamma|beta conv + SPADE epilogue and writes the consumer's f16c image
-                Op g; g.type = OP_GBR; g.src_is_input = true;
+                Op g; g.type = OP_GBR; g.src_is_input = true; g.gbr_ranges = sf.ranges;
                 GbrParams& q = g.gbr;
                 snprintf(k, sizeof k, "gen.rb%d.spade_%d.conv.kernel", i, j); q.we = need(k);
                 snprintf(k, sizeof k, "gen.rb%d.spade_%d.conv.kernel.e16", i, j); q.we16 = need(k);
@@ -332,9 +331,8 @@ static int plan_pix2pix(msr_handle* h) {
         c.B = B; c.Hout = rout; c.Wout = rout; c.Cin = cin; c.N = N; c.KH = K; c.KW = K; c.stride = stride;
         c.in_px = in_px; c.in_py = in_py; c.in_pb = in_pb;
         const ConvForm f = conv_form(B, rout, N, stride, EPI_AFFINE, PREC_F32, cin, K * K);
-        c.prec = f.prec;
-        op.tile = f.tile;
-        c.ksplit = f.ksplit;
+        c.prec = f.prec; c.ksplit = f.ksplit;
+        op.tile = f.tile; op.kernel = f.kernel;
         op.flops = 2.0 * B * rout * rout * (double)cin * N * K * K;
         return op;
     };

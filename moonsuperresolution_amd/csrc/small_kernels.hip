@@ -168,9 +168,8 @@ __global__ void __launch_bounds__(256) conv_smallcin_tiled_kernel(const SmallCin
 
 template <int COUT>
 static hipError_t launch_smallcin_t(const SmallCinParams& p, hipStream_t s) {
-    static const bool tiled_off = env_int("MSR_SMALLCIN_TILED", 1) == 0;
     // (a handful of tiles — the low-resolution embeddings — finish sooner one pixel group per thread)
-    if (p.Hout % 16 == 0 && p.B * (p.Hout / 16) * (p.Hout / 16) >= 64 && !tiled_off) {
+    if (p.Hout % 16 == 0 && p.B * (p.Hout / 16) * (p.Hout / 16) >= 64 && switches().smallcin_tiled) {
         conv_smallcin_tiled_kernel<COUT><<<p.B * (p.Hout / 16) * (p.Hout / 16), 256, 0, s>>>(p);
         return hipGetLastError();
     }

@@ -30,6 +30,20 @@ def parse_conv_forms(text: str) -> list:
     return ops
 
 
+def form_table(image_size: int, batch_size: int, variant: str = "gaugan", flags: int = 0, latent_dim: int = 256) -> dict:
+    """msr_debug_form_table, which needs no GPU: {layer: parse_conv_forms dict of its line} of the form table a handle of this
+    configuration gets under this process's environment switches, plus "head_fused": 0 | 1.  ValueError for a configuration
+    msr_create rejects."""
+    lib = _lib.load()
+    cfg = _lib.MsrConfig(image_size, batch_size, latent_dim, _lib.VARIANT_IDS[variant], 0, flags)
+    buf = C.create_string_buffer(1 << 14)
+    _lib.raise_for(lib, None, lib.msr_debug_form_table(C.byref(cfg), buf, len(buf)), "msr_debug_form_table")
+    lines = buf.value.decode().splitlines()
+    table = {ln.split()[0]: parse_conv_forms(ln.split(None, 1)[1])[0] for ln in lines[:-1]}
+    table["head_fused"] = int(lines[-1].split("=")[1])
+    return table
+
+
 F16_MAX = 65504.0
 
 
@@ -366,7 +380,7 @@ class Generator:
         return dict(line.split(" ") for line in buf.value.decode().splitlines())
 
     def conv_forms(self) -> list:
-        """One dict per planned op, in plan order (msr_debug_conv_forms): kind, tensor names, and for the convs prec, tile,
+        """One dict per planned op, in plan order (msr_debug_conv_forms): kind, tensor names, and for the convs prec, kernel, tile,
         ksplit, wt_frag, no_cross, epi, out_split, ranges and img (the weight image built at upload).  Integers are ints."""
         self.prepare()
         buf = C.create_string_buffer(1 << 18)

@@ -10,6 +10,18 @@ GPU tests a fixed target that does not need the oracle's 100 M-parameter weight 
     spade64_zero.npz        same, second patch all-zero (the zero padding patch of process_full_tiles.py:468-474)
     pix2pix256.npz          pix2pix S=256 B=1 float64 oracle output: checksum + an 8x8 probe grid
     stitch_small.npz        rebuild_tile on tests/helpers.stitch_inputs() (S=64, s=16, T=128): float32 outputs
+
+NOT regenerated here, on purpose: form_table.json pins the form table as commit d303279 computed it — the last commit in which
+the kernel of a layer was decided at launch time (launch_conv_igemm / launch_pp) and predicted by forms.hip — so that the
+refactor that put the kernel into the form could be proved to change no form.  It was written once by a scratch program linked
+against that commit's libmoonsr_hip.so: for S in {64, 128, 256, 512} x B in {1, 2, 3, 4, 8, 12, 16} x the flag sets of the file
+(plus pix2pix at 256) it filled an msr_handle's configuration by hand as msr_create did, called msr::fill_forms,
+msr::head_fused_form and msr::conv_gbr_ranges, printed the text msr_debug_form_table prints now, with the `kernel` word derived
+by restating that commit's dispatch (fp32 -> generic; bf16x3 by tile / wt_frag; F16X2, FP8 -> pp; F16C6 and EPI_RES_HEAD -> sw;
+F16C with K ranges -> pp, whole tiles by msr::f16c_whole_tile_on_stream), and was run once per environment of the file's
+"envs" (the switches are read once per process).  Stored: the SHA-256 of every text, and the text itself under no switch for
+f16c at (64, 2), (128, 3), (256, 16), (512, 8), (512, 12).  A form that changes ON PURPOSE later regenerates the fixture from
+msr_debug_form_table itself (tests/test_forms_host.py run as a script prints the tables of one environment).
 """
 import os
 import sys

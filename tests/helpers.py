@@ -259,7 +259,7 @@ def later_round_mask(B, r, N, n_cu, walk=True, pick=None, new_block=False):
 
 # ---- conv_gb_resident (csrc/conv_gbr.hip): work decomposition, exact-embedding inputs, term references ------------------------
 def gbr_ranges(B, r, N):
-    """Host restatement of conv_gbr_ranges (csrc/conv_gbr.hip, MSR_GBR unset) -> (the planner's answer, 0 = not a layer for
+    """Host restatement of conv_gbr_ranges (csrc/forms.hip, MSR_GBR unset) -> (the planner's answer, 0 = not a layer for
     the resident kernel; what the test entries msr_op_spade_gbr* launch with: the entry falls back to 1)."""
     if r < 16 or (r & (r - 1)) or N % 128:
         return 0, 1

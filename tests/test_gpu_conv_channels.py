@@ -40,14 +40,14 @@ tests/test_conv_channels_host.py gives 2.6e-7 to 4.8e-7; the smallest fault it i
   MSR_F16C_SW = 0 / 2 (child runs): every f16c case reports the figure and the channel of the default dispatch, digit for digit,
     although the other kernel runs (case B on conv_igemm_bf16x3_pp<EPI_BIAS, PP_F16C> under 0, case D on conv_igemm_f16c_sw<EPI_SPADE>
     under 2, seen in a kernel trace): both kernels add a channel's products in the same order.  Every f16c test therefore asks the
-    library which kernel its launch goes to (msr_debug_f16c_kernel: the rule launch_pp dispatches by), checks the answer against the
+    library which kernel its launch goes to (msr_debug_f16c_kernel: conv_kernel_for, the rule that names a form's kernel), checks the answer against the
     meaning of the mode, and the child-run test requires the answers the mode stands for.
 No case needed the fp32-evaluation allowance.
 
 The f16c tests follow the process's MSR_F16C_SW (read once); test_f16c_cases_under_the_other_kernel_dispatch reruns them in a child
 process under MSR_F16C_SW = 0 (everything on the ping-pong kernel) and = 2 (everything with Cin % 128 == 0 on the stream kernel).
 A form the selected kernel does not have is refused by the entry (ValueError) and skipped per case, explicitly.  Cases skipped:
-none under either mode: launch_pp sends a launch the selected kernel has no form for to the other kernel (A: Cin = 64, always
+none under either mode: the rule names the other kernel for a launch the selected kernel has no form for (A: Cin = 64, always
 ping-pong; C and D with ks > 1: always ping-pong K ranges + split-K pass; D out_mode 5: always ping-pong; no_cross and f16c6:
 always the stream kernel), so under each mode every one of A, B, C, D and G runs, which the child-run test asserts."""
 import json
@@ -100,7 +100,7 @@ def _launch(fn, what):
 
 def _kernel(ctx, cin, epi, out_mode=0, ks=1, direct=False):
     """Which kernel a msr_op_conv3x3_f16c launch runs in this process: the library's own answer (msr_debug_f16c_kernel, the
-    rule launch_pp dispatches by) for whole-tile launches, checked against the documented meaning of MSR_F16C_SW (1: bias /
+    rule conv_kernel_for of csrc/forms.hip) for whole-tile launches, checked against the documented meaning of MSR_F16C_SW (1: bias /
     residual launches with Cin % 128 == 0 on the stream kernel; 0: nothing; 2: everything with Cin % 128 == 0 but the f16c6
     image output).  K ranges always run the ping-pong kernel, no_cross and f16c6 launches (``direct``) always the stream kernel."""
     if direct:

@@ -29,7 +29,7 @@ stays bit-identical, the channel changes and meets the bound against the referen
 scale changes leave the whole tensor bit-identical.  Channels 0, 3, 4, 15, 16, 31, 32, 47, 63 of each 64-channel block: every
 wave (wq), lane group (cg) and k of `ch = ((n0 + (wq >> 1) * 64) >> 1) + (wq & 1) * 16 + 4 * cg + k`.
 
-Work decomposition (tests.helpers.gbr_work restates conv_gbr_ranges, the entries' fall-back, persistent_grid, xcd_tile_range):
+Work decomposition (tests.helpers.gbr_work restates conv_gbr_ranges of csrc/forms.hip, the entries' fall-back, persistent_grid, xcd_tile_range):
   (1, 32, 16, 256, 0)   one item, all sides on the border, nr = 4 (the w_nxt chain, the last block's self re-read), items % 8 == 1
   (5, 256, 32, 128, 1)  20 items on 24 workgroups (XCDs with 3 and 2 items), nr = 2, resize factor 8, folded up-sample
   (9, 64, 64, 128, 0)   ranges = 2, 288 items on 256 workgroups: 32 workgroups take a second item

@@ -36,6 +36,10 @@ configuration below needed the allowance: the largest error / bound of a conv's 
 K = 9 x 256), 0.46 in fp32, 0.13 in bf16x3, 0.08 in f16c; the fp32 evaluation's own error at the one site where it was taken (the
 control, K = 1152) is 1.5e-8 absolute, ratio to the bound 2e-4.
 
+Before the sites, the plan's host side is checked line by line (check_plan_against_form_table): every conv and gbr line names the
+kernel the launch-time dispatch used to pick (restated in old_dispatch), a gbr line's ranges are conv_gbr_ranges, and the plan runs
+the forms msr_debug_form_table gives for the same configuration.
+
 Every site's worst error / bound is printed and appended to parity_network_sites.jsonl in the run-record directory (next to
 parity_baseline_configs.jsonl); a copy of one full run is
 profiles/network_sites_parity.jsonl.
@@ -589,10 +593,59 @@ def _expected_op_count(S, B, ops_):
     return 1 + 8 + 2 + 1 + 1 + (15 - n_gbr) * 3 + n_gbr * 2
 
 
+def old_dispatch(lib, op):
+    """The kernel a conv line ran before the form named it: the launch-time dispatch (launch_conv_igemm, launch_pp's forward to
+    the stream kernel by msr_debug_f16c_kernel's rule, the planner's direct launch of the head epilogue), restated from the line."""
+    prec, tile = op["prec"], op["tile"]
+    if op["kind"] == "gbr":
+        return "gbr"
+    if op["epi"] == 5 or prec == PREC_F16C6:
+        return "sw"
+    if prec in (PREC_F16X2, PREC_FP8):
+        return "pp"
+    if prec == PREC_F16C:
+        whole = op["ksplit"] <= 1
+        return "sw" if whole and lib.msr_debug_f16c_kernel(op["cin"], op["epi"], op["out_split"]) else "pp"
+    if prec == PREC_BF16X3:
+        if tile in (TILE_PP, 3, 4):
+            return {TILE_PP: "pp", 3: "halo", 4: "halo16"}[tile]
+        if op["wt_frag"]:
+            return "bvgpr"
+    return "generic"
+
+
+def check_plan_against_form_table(sites):
+    """The plan walk's host-side half: every conv and gbr line names its kernel, the one the old dispatch ran; a gbr line's ranges
+    are conv_gbr_ranges; and the plan runs what msr_debug_form_table says for the same configuration (same process, so the same
+    environment switches): the same layers in the same forms, the same resident-kernel ranges, the same head."""
+    from moonsuperresolution_amd import _lib
+    from moonsuperresolution_amd.generator import form_table
+    from tests.helpers import gbr_ranges
+    table = form_table(sites.S, sites.B, "gaugan", _lib.PRECISION_FLAGS[sites.precision])
+    fields = ("prec", "kernel", "tile", "ksplit", "wt_frag", "no_cross", "img")
+    planned = {}
+    for op in sites.ops:
+        if op["kind"] not in ("conv", "gbr"):
+            continue
+        assert op.get("kernel") in ("generic", "bvgpr", "halo", "halo16", "pp", "sw", "gbr"), op
+        assert op["kernel"] == old_dispatch(sites.gen._lib, op), (op["wt"], op["kernel"], old_dispatch(sites.gen._lib, op))
+        layer = op["wt"][: -len(".kernel")]
+        assert layer not in planned, layer
+        planned[layer] = {k: op[k] for k in fields}
+        if layer.endswith(".gb"):
+            spade = table[layer[: -len(".gb")]]
+            assert (spade["gbr"], spade["ranges"], spade["a_split"]) == (int(op["kind"] == "gbr"), op["ranges"], op["out_split"]), (layer, spade)
+        if op["kind"] == "gbr":
+            assert op["ranges"] == gbr_ranges(op["B"], op["r"], op["N"])[0] > 0, op
+    assert planned == {k: {f: v[f] for f in fields} for k, v in table.items() if k != "head_fused" and "prec" in v}
+    assert table["head_fused"] == int(any(op["kind"] == "head_gather" for op in sites.ops))
+
+
 def _run_config(S, B, precision):
     torch.set_num_threads(min(16, os.cpu_count() or 1))
     sites = Sites(S, B, precision)
     try:
+        check_plan_against_form_table(sites)
         res = sites.run()
         checked = [op for op, _, _ in res]
         assert len(checked) == _expected_op_count(S, B, sites.ops), len(checked)
@@ -714,7 +767,8 @@ def test_conv_forms_dump_parses():
     assert all(isinstance(o[k], int) for o in convs for k in ("prec", "tile", "ksplit", "wt_frag", "no_cross", "epi", "out_split",
                                                              "ranges", "B", "r", "N"))
     assert all(o["img"] in ("F32", "BF16", "BF16_FRAG", "F16", "FP8", "F16C", "F16C6", "GBR") for o in convs)
-    assert all((o["kind"] == "gbr") == (o["img"] == "GBR") == (o["ranges"] > 0) for o in convs)
+    assert all((o["kind"] == "gbr") == (o["img"] == "GBR") == (o["ranges"] > 0) == (o["kernel"] == "gbr") for o in convs)
+    assert all(o["kernel"] in ("generic", "bvgpr", "halo", "halo16", "pp", "sw", "gbr") for o in convs)
     assert {form_of(o) for o in checked} <= REQUIRED_FORMS
     assert ("gbr", PREC_F16C6, TILE_PP, False, 0, 0, 4) in {form_of(o) for o in checked}
     assert all("?" not in o.values() for o in ops_)
