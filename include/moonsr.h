@@ -16,6 +16,17 @@
  *  - `stream` is a hipStream_t passed as void* (NULL = the default stream).  Calls are asynchronous
  *    on that stream; a handle is not re-entrant.
  *  - there is NO CPU fallback: if no gfx950 device is usable msr_create fails with MSR_ERR_DEVICE.
+ *
+ * Non-finite inputs
+ *  A NaN is data, as it is to the reference (IEEE: relu(NaN) = NaN, 0 * NaN = NaN).  For every kernel entry and for
+ *  msr_forward: an output element is NaN exactly where the float64 reference of the same operation is NaN; for an image output
+ *  (split-bf16, split-fp16, f16c, f16c6, bf8) that is its MAIN piece (hi, or the bf8 byte), the cross pieces of a NaN element
+ *  are unspecified.  Every element that does not depend on a NaN input is bit-identical to the same call with 0.0 in the NaN's
+ *  place, cross pieces and block scales of the other channels of a poisoned pixel included (a block scale is the maximum over
+ *  the block's non-NaN elements).  Batch statistics (SPADE) hand one sample's NaN to the whole batch, as the reference's do.
+ *  +-Inf is outside this contract: the f16c family clamps activations to fp16's range (+-65504) by design, so an infinity
+ *  becomes a finite value there (tests/test_gpu_conv_kernel.py::test_f16c_saturation_regimes).
+ *  tests/test_gpu_nonfinite.py pins the contract kernel by kernel.
  */
 #ifndef MOONSR_H
 #define MOONSR_H

@@ -16,7 +16,6 @@ namespace msr {
 template <int WM, int WN, int MT, int NT, int EPI>
 __global__ void __launch_bounds__(WM * WN * 64) __attribute__((amdgpu_waves_per_eu(2, 2)))
 conv_igemm_bf16x3(const ConvParams p, const TileGeom g) {
-    MSR_SATURATING_CONVERSIONS();
     static_assert(NT == 2, "B register sets are written for two n-tiles per wave");
     constexpr int NTHR = WM * WN * 64;
     constexpr int BM = WM * MT * 32;

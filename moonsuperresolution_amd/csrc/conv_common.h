@@ -11,6 +11,43 @@ typedef float f32x16 __attribute__((ext_vector_type(16)));
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef _Float16 f16x8 __attribute__((ext_vector_type(8)));
+
+// MODE.FP16_OVFL on for the converting part of an epilogue only (kernels.h MSR_SATURATING_CONVERSIONS): the accumulators pass
+// through the statement that sets the bit, so everything computed from them follows it; the statement that clears it orders
+// the stores of the converted values before it ("memory"); nothing is scheduled across either.
+__device__ __forceinline__ void msr_saturate_begin(f32x4 (&a)[4][4]) {
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile(MSR_SATURATE_BEGIN_ASM
+                 : "+v"(a[0][0]), "+v"(a[0][1]), "+v"(a[0][2]), "+v"(a[0][3]), "+v"(a[1][0]), "+v"(a[1][1]), "+v"(a[1][2]), "+v"(a[1][3]),
+                   "+v"(a[2][0]), "+v"(a[2][1]), "+v"(a[2][2]), "+v"(a[2][3]), "+v"(a[3][0]), "+v"(a[3][1]), "+v"(a[3][2]), "+v"(a[3][3])
+                 : : "memory");
+}
+__device__ __forceinline__ void msr_saturate_begin(f32x4 (&a)[16][2]) {
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile(MSR_SATURATE_BEGIN_ASM
+                 : "+v"(a[0][0]), "+v"(a[0][1]), "+v"(a[1][0]), "+v"(a[1][1]), "+v"(a[2][0]), "+v"(a[2][1]), "+v"(a[3][0]), "+v"(a[3][1]),
+                   "+v"(a[4][0]), "+v"(a[4][1]), "+v"(a[5][0]), "+v"(a[5][1]), "+v"(a[6][0]), "+v"(a[6][1]), "+v"(a[7][0]), "+v"(a[7][1])
+                 : : "memory");
+    asm volatile("" : "+v"(a[8][0]), "+v"(a[8][1]), "+v"(a[9][0]), "+v"(a[9][1]), "+v"(a[10][0]), "+v"(a[10][1]), "+v"(a[11][0]), "+v"(a[11][1]),
+                      "+v"(a[12][0]), "+v"(a[12][1]), "+v"(a[13][0]), "+v"(a[13][1]), "+v"(a[14][0]), "+v"(a[14][1]), "+v"(a[15][0]), "+v"(a[15][1]));
+}
+// the light form: four values that every conversion of the epilogue depends on (the SPADE epilogue's 1 / sigma)
+__device__ __forceinline__ void msr_saturate_begin(float& a0, float& a1, float& a2, float& a3) {
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile(MSR_SATURATE_BEGIN_ASM : "+v"(a0), "+v"(a1), "+v"(a2), "+v"(a3) : : "memory");
+}
+__device__ __forceinline__ void msr_saturate_begin(f32x4& a0, f32x4& a1) {
+    __builtin_amdgcn_sched_barrier(0);
+    asm volatile(MSR_SATURATE_BEGIN_ASM : "+v"(a0), "+v"(a1) : : "memory");
+}
+__device__ __forceinline__ void msr_saturate_end() {
+    asm volatile(MSR_SATURATE_END_ASM ::: "memory");
+    __builtin_amdgcn_sched_barrier(0);
+}
+__device__ __forceinline__ void msr_saturate_end(f16x8& h, f16x8& l) {      // the converted values are consumed from registers
+    asm volatile(MSR_SATURATE_END_ASM : "+v"(h), "+v"(l) : : "memory");
+    __builtin_amdgcn_sched_barrier(0);
+}
 typedef int i32x8 __attribute__((ext_vector_type(8)));
 typedef int i32x6 __attribute__((ext_vector_type(6)));
 typedef int i32x4 __attribute__((ext_vector_type(4)));

@@ -64,7 +64,7 @@ __global__ void __launch_bounds__(256) conv_direct_kernel(const DirectConvParams
         for (int k = 0; k < 4; ++k) {
             if (p.scale) v[k] *= p.scale[co + k];
             if (p.shift) v[k] += p.shift[co + k];
-            if (p.act == 1) v[k] = fmaxf(v[k], 0.f);
+            if (p.act == 1) v[k] = v[k] <= 0.f ? 0.f : v[k];          // keeps NaN (fmaxf drops it)
             else if (p.act == 2) v[k] = v[k] >= 0.f ? v[k] : v[k] * p.slope;
             else if (p.act == 3) v[k] = tanhf(v[k]);
         }

@@ -97,7 +97,7 @@ __device__ __forceinline__ void conv_epilogue_body(const ConvParams& p, const Ti
                     float v = acc[m][n][r] + cb0[n];
                     if constexpr (EPI == EPI_AFFINE) {
                         v = acc[m][n][r] * cb1[n] + cb0[n];
-                        v = p.act == 1 ? fmaxf(v, 0.f) : (p.act == 2 ? (v >= 0.f ? v : v * p.slope) : v);
+                        v = p.act == 1 ? (v <= 0.f ? 0.f : v) : (p.act == 2 ? (v >= 0.f ? v : v * p.slope) : v);    // relu keeps NaN (fmaxf drops it)
                     }
                     if constexpr (EPI == EPI_RES) v += xin[q][n];
                     if (ok[q]) orow[ccol[n]] = v;
@@ -441,6 +441,9 @@ __device__ __forceinline__ void halo16_epilogue(const ConvParams& p, const TileG
                                                 int lane, int n0, int tx0, int ty0, int b0, float4 (&xin)[4][2],
                                                 float4 (&cv)[8], unsigned* stage = nullptr) {
     const int stat_tile = (b0 * g.tiles_y + (ty0 >> g.th_l)) * g.tiles_x + (tx0 >> g.tw_l);
+    // a narrow output image (fp16 / fp8 / bf8 pieces): the conversions saturate, and only they run with the bit set
+    const bool narrow = EPI == EPI_SPADE && p.out_split > OUT_BF16X3;
+    if (narrow) msr_saturate_begin(acc);
     if constexpr (EPI == EPI_SPADE) {
         if (p.out_split == OUT_F16C6 && stage) halo16_epilogue_spade_f16c_staged<true>(p, acc, wm, wn, lane, n0, tx0, ty0, b0, xin, cv, stage);
         else if (p.out_split == OUT_F16C && stage) halo16_epilogue_spade_f16c_staged<false>(p, acc, wm, wn, lane, n0, tx0, ty0, b0, xin, cv, stage);
@@ -451,6 +454,7 @@ __device__ __forceinline__ void halo16_epilogue(const ConvParams& p, const TileG
     } else {
         halo16_epilogue_body<EPI, false>(p, acc, wm, wn, lane, n0, tx0, ty0, b0, stat_tile, xin, cv);
     }
+    if (narrow) msr_saturate_end();
 }
 
 }  // namespace msr

@@ -76,7 +76,6 @@ template <bool NOX, bool F6OUT = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 conv_gb_resident(const GbrParams p, const GbrGeom g) {
     static_assert(!(NOX && F6OUT), "the f16 mode's consumer reads no cross pieces");
-    MSR_SATURATING_CONVERSIONS();
     constexpr int PH = GB_PH, HW = 18, HP = 324;
     constexpr int PD = GB_PD, PDC = GB_PDC;
     extern __shared__ __attribute__((aligned(16))) char smem[];
@@ -190,6 +189,9 @@ conv_gb_resident(const GbrParams p, const GbrGeom g) {
 #pragma unroll
             for (int u = 0; u < 2; ++u) {
                 const int q = tid + 256 * u;
+                // fp16's range in software (the wave mode saturates only in the epilogue); the ternaries keep a NaN
+                pv[u].x = pv[u].x > 65504.f ? 65504.f : (pv[u].x < -65504.f ? -65504.f : pv[u].x);
+                pv[u].y = pv[u].y > 65504.f ? 65504.f : (pv[u].y < -65504.f ? -65504.f : pv[u].y);
                 const h2p hi2 = {(_Float16)pv[u].x, (_Float16)pv[u].y};
                 const h2p lo2 = {(_Float16)(pv[u].x - (float)hi2[0]), (_Float16)(pv[u].y - (float)hi2[1])};
                 if (q < 400) {
@@ -259,7 +261,12 @@ conv_gb_resident(const GbrParams p, const GbrGeom g) {
         const int hy = (hq * 3641) >> 16, hx = hq - hy * HW;                                     \
         const int y = ty0 - 1 + hy, x = tx0 - 1 + hx;                                            \
         /* relu, the conv's zero padding outside the image (not relu(bias)) and fp16's range (as msr_store_f16c4_dev) in \
-           one v_med3_f32: clamp to [0, top] with top = 0 for a pixel outside the image */     \
+           one v_med3_f32: clamp to [0, top] with top = 0 for a pixel outside the image.  (v_med3_f32 answers 0 for a NaN, \
+           unlike msr_store_f16c4_dev's ternaries.  A NaN mask pixel in the 3 x 3 window makes ALL 128 channels of the pixel \
+           NaN (NaN * w, whatever w), so one test per pixel, before the clamp, decides: inside the image the NaN is put back \
+           into ONE fp16 pair of the pixel's main piece (the embedding is no output: a NaN operand anywhere in the pixel's K row \
+           makes every gamma | beta column of the sweep NaN, which is what the reference has); outside, top = 0 keeps the \
+           conv's zero padding exactly 0) */ \
         const float top = (y >= 0 && y < p.r && x >= 0 && x < p.r) ? 65504.f : 0.f;              \
         float lo[16], hi[16];                                                                    \
         float amax = 0.f;                                                                        \
@@ -280,6 +287,7 @@ conv_gb_resident(const GbrParams p, const GbrGeom g) {
                           "+v"(hi[8]), "+v"(hi[9]), "+v"(hi[10]), "+v"(hi[11]), "+v"(hi[12]), "+v"(hi[13]), "+v"(hi[14]), "+v"(hi[15])); \
         __builtin_amdgcn_sched_barrier(0);                                                       \
         if ((PAIR) == 1) GB_STAMP3()                                                             \
+        const int nanbits = ((lo[0] != lo[0] || hi[0] != hi[0]) && top != 0.f) ? 0x7E007E00 : 0;   \
         _Pragma("unroll") for (int t = 0; t < 16; ++t) {                                         \
             lo[t] = __builtin_amdgcn_fmed3f(lo[t], 0.f, top);                                    \
             hi[t] = __builtin_amdgcn_fmed3f(hi[t], 0.f, top);                                    \
@@ -316,7 +324,10 @@ conv_gb_resident(const GbrParams p, const GbrGeom g) {
         }                                                                                        \
         if (live) {                                                                              \
             char* const fp = smem + (wq * 4 * PH + hp) * 16;                                     \
-            _Pragma("unroll") for (int pc = 0; pc < 4; ++pc) *reinterpret_cast<f16x8*>(fp + pc * PH * 16) = hv[pc]; \
+            i32x4 h0_ = __builtin_bit_cast(i32x4, hv[0]);                                        \
+            h0_[0] |= nanbits;       /* one NaN operand poisons the pixel's whole row of the sweep */ \
+            *reinterpret_cast<i32x4*>(fp) = h0_;                                                 \
+            _Pragma("unroll") for (int pc = 1; pc < 4; ++pc) *reinterpret_cast<f16x8*>(fp + pc * PH * 16) = hv[pc]; \
         }                                                                                        \
         if (!NOX && live) {       /* NOX: the fp6 pieces and their scales are not read: not made */ \
             char* const xpa = smem + GB_F_BYTES + (wq * 2 * PH + hp) * 16;                       \
@@ -498,6 +509,9 @@ conv_gb_resident(const GbrParams p, const GbrGeom g) {
             }
             // ---- SPADE epilogue: acc[i][0] = gamma, acc[i][1] = beta of channels ch .. ch + 3 at pixel (ty0 + i, x) ----
             GB_STAMP2()
+            // the epilogue's fp16 / fp8 conversions saturate; the sweep's MFMAs never see the bit.  Every converted value is a
+            // function of 1 / sigma (nk below), so sigma is what passes through the statement that sets it
+            msr_saturate_begin(sq4.x, sq4.y, sq4.z, sq4.w);
             if constexpr (F6OUT) {
                 // ---- the f16c6 image: per pixel and 32-channel chunk 32 x fp16 | 32 x h6 + scale | 32 x l6 + scale ----
                 // The block scale 2^E >= max|v| / 7.5 is taken over the chunk's 32 channels: 4 lanes (px + 16 cg) of this wave
@@ -529,7 +543,7 @@ conv_gb_resident(const GbrParams p, const GbrGeom g) {
                         const float nk = __builtin_fmaf(xq[k], A[k], Bc[k]);
                         const float t = __builtin_fmaf(acc[i][0][k], nk, acc[i][1][k]);
                         const float u = fmaxf(t, t * p.slope);
-                        v[k] = __builtin_amdgcn_fmed3f(u, -65504.f, 65504.f);
+                        v[k] = u != u ? u : __builtin_amdgcn_fmed3f(u, -65504.f, 65504.f);      // v_med3_f32 alone turns NaN into -65504
                     }
                     vv[i] = make_float4(v[0], v[1], v[2], v[3]);
                     float m = fmaxf(fmaxf(fabsf(v[0]), fabsf(v[1])), fmaxf(fabsf(v[2]), fabsf(v[3])));   // NaN: dropped here, kept in the fp16 piece
@@ -629,15 +643,18 @@ conv_gb_resident(const GbrParams p, const GbrGeom g) {
                     if (i < 16) {
                         char* const line = stage + px * GB_LINE;
                         const float xq[4] = {xin[i].x, xin[i].y, xin[i].z, xin[i].w};
-                        float v[4];
+                        float v[4], uu[4];
 #pragma unroll
                         for (int k = 0; k < 4; ++k) {
                             const float nk = __builtin_fmaf(xq[k], A[k], Bc[k]);
                             const float t = __builtin_fmaf(acc[i][0][k], nk, acc[i][1][k]);
                             const float u = fmaxf(t, t * p.slope);                // leaky relu, 0 <= slope <= 1 (checked on the host)
-                            v[k] = __builtin_amdgcn_fmed3f(u, -65504.f, 65504.f);
+                            uu[k] = u;
+                            v[k] = __builtin_amdgcn_fmed3f(u, -65504.f, 65504.f);  // the cross pieces' operand (a NaN becomes -65504 here)
                         }
-                        const h2 a = {(_Float16)v[0], (_Float16)v[1]}, b = {(_Float16)v[2], (_Float16)v[3]};
+                        // the main piece from the unclamped value: the conversion saturates by itself (MSR_SATURATING_CONVERSIONS: the
+                        // same bits as converting the clamped one) and keeps a NaN, which v_med3_f32 does not
+                        const h2 a = {(_Float16)uu[0], (_Float16)uu[1]}, b = {(_Float16)uu[2], (_Float16)uu[3]};
                         unsigned h8 = 0;
                         h8 = __builtin_amdgcn_cvt_pk_fp8_f32(v[0], v[1], h8, false);
                         h8 = __builtin_amdgcn_cvt_pk_fp8_f32(v[2], v[3], h8, true);
@@ -654,6 +671,7 @@ conv_gb_resident(const GbrParams p, const GbrGeom g) {
                     if (i > 0) *reinterpret_cast<uint4*>(obase + (size_t)(ty0 + i - 1) * p.out_py) = q;
                 }
             }
+            msr_saturate_end();
             GB_STAMP2()
         }
         GB_STAMP()

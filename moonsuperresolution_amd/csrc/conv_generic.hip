@@ -34,7 +34,6 @@ __device__ __forceinline__ void stage_store(float* dst, const float4& v) {
 template <int WM, int WN, int MT, int NT, int BKC, int EPI, int PREC>
 __global__ void __launch_bounds__(WM * WN * 64) __attribute__((amdgpu_waves_per_eu(2, BKC == 16 ? 3 : 2)))
 conv_igemm(const ConvParams p, const TileGeom g) {
-    MSR_SATURATING_CONVERSIONS();
     static_assert(PREC == PREC_F32 || BKC == 32, "the split-bf16 path uses the 32-channel K-step");
     constexpr int NTHR = WM * WN * 64;
     constexpr int BM = WM * MT * 32;

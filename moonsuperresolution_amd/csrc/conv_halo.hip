@@ -16,7 +16,6 @@ namespace msr {
 template <int EPI, int SH>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(2, 2)))
 conv_igemm_bf16x3_halo(const ConvParams p, const TileGeom g) {
-    MSR_SATURATING_CONVERSIONS();
     constexpr int WM = 2, WN = 2, MT = 2, NT = 2;
     constexpr int NTHR = 256, BM = 128, BN = 128, BKC = 32, BKP = SH ? 40 : 36;
     constexpr int TH = 8, TW = 16, HH = TH + 2, HW = TW + 2, HP = HH * HW;   // 180 halo pixels

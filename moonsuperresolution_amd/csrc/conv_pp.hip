@@ -47,7 +47,6 @@ enum PpMode : int { PP_BF16X3 = 0, PP_F16X2 = 1, PP_FP8 = 2, PP_F16C = 3 };
 template <int EPI, int MODE, bool ONE = false>
 __global__ void __launch_bounds__(512) __attribute__((amdgpu_waves_per_eu(2, 2)))
 conv_igemm_bf16x3_pp(const ConvParams p, const TileGeom g) {
-    MSR_SATURATING_CONVERSIONS();
     constexpr bool F16X2 = MODE == PP_F16X2;
     constexpr int NTHR = 512, BN = 128, BKC = 32, BKP = 40;
     constexpr int TH = 16, TW = 16, HW = TW + 2, HP = (TH + 2) * HW;          // 324 halo pixels

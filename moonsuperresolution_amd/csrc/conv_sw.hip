@@ -153,7 +153,11 @@ template <int EPI>
 __device__ __forceinline__ void sw_epilogue(const ConvParams& p, const SwGeom& g, f32x4 (&acc)[16][2], int wq, int lane,
                                             int n0, int tx0, int ty0, int b0) {
     if constexpr (EPI == EPI_SPADE) {
-        if (p.out_split == OUT_F16C) sw_epilogue_body<EPI, OUT_F16C>(p, g, acc, wq, lane, n0, tx0, ty0, b0);
+        if (p.out_split == OUT_F16C) {
+            msr_saturate_begin(acc);                                   // fp16 / fp8 pieces: the conversions saturate
+            sw_epilogue_body<EPI, OUT_F16C>(p, g, acc, wq, lane, n0, tx0, ty0, b0);
+            msr_saturate_end();
+        }
         else if (p.out_split == OUT_BF16X3) sw_epilogue_body<EPI, OUT_BF16X3>(p, g, acc, wq, lane, n0, tx0, ty0, b0);
         else sw_epilogue_body<EPI, OUT_F32>(p, g, acc, wq, lane, n0, tx0, ty0, b0);
     } else {
@@ -222,6 +226,7 @@ __device__ __forceinline__ void sw_epilogue_head(const ConvParams& p, f32x4 (&ac
             for (int ii = 0; ii < 4; ++ii) {
                 const int i = g8 * 8 + i4 + ii;
                 f16x8 ah, al;
+                msr_saturate_begin(acc[i][0], acc[i][1]);               // a_hi saturates at 65504; the MFMAs below run without the bit
 #pragma unroll
                 for (int j = 0; j < 2; ++j) {
                     const float rq[4] = {res[ii][j].x, res[ii][j].y, res[ii][j].z, res[ii][j].w};
@@ -234,6 +239,7 @@ __device__ __forceinline__ void sw_epilogue_head(const ConvParams& p, f32x4 (&ac
                         al[4 * j + k] = (_Float16)(a - (float)hi);
                     }
                 }
+                msr_saturate_end(ah, al);
                 f32x4 d0 = {0.f, 0.f, 0.f, 0.f}, d1 = {0.f, 0.f, 0.f, 0.f};
                 d0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, wh0), ah, d0, 0, 0, 0);
                 d1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(__builtin_bit_cast(f16x8, wh1), ah, d1, 0, 0, 0);
@@ -285,7 +291,6 @@ __device__ __forceinline__ void sw_epilogue_head(const ConvParams& p, f32x4 (&ac
 template <int EPI, bool F6 = false, bool NOX = false>
 __global__ void __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(1, 1)))
 conv_igemm_f16c_sw(const ConvParams p, const SwGeom g) {
-    MSR_SATURATING_CONVERSIONS();
     constexpr int HW = SW_HW, HP = SW_HP, BKP = SW_BKP, HPB = SW_HPB;
     constexpr int NTHR = 256, BKC = 32;
     constexpr int H_ITEMS = (HP * 8 + NTHR - 1) / NTHR;                // 11 16-byte items per thread and chunk

@@ -140,9 +140,12 @@ enum OutFormat : int {
     OUT_F16C6 = 5,    // f16c6 chunk image
 };
 
-__host__ __device__ inline unsigned msr_bf16_rn(float v) {   // round-to-nearest-even, finite inputs
+// round-to-nearest-even.  A NaN stays a NaN of its sign (quiet bit set, high payload kept): the rounding increment alone would
+// carry a payload in the low 16 bits into the exponent or the sign (0x7f800001 -> infinity, 0x7fffffff -> -0)
+__host__ __device__ inline unsigned msr_bf16_rn(float v) {
     union { float f; unsigned u; } c;
     c.f = v;
+    if (v != v) return (c.u >> 16) | 0x40u;
     return (c.u + 0x7FFFu + ((c.u >> 16) & 1u)) >> 16;
 }
 __host__ __device__ inline void msr_split_bf16(float v, unsigned& hi, unsigned& lo) {
@@ -257,12 +260,22 @@ __device__ inline int msr_block_e8m0_dev(float amax) {
 // saturated piece costs accuracy (tests/test_gpu_conv_kernel.py::test_f16c_saturation_regimes); a NaN piece poisons the tile.
 // MODE is per-wave state, initialised at wave launch: nothing outlives the kernel.
 #define MSR_SATURATING_CONVERSIONS() asm volatile("s_setreg_imm32_b32 hwreg(HW_REG_MODE, 23, 1), 1")
+// The bit is not free for a kernel that also multiplies on the matrix pipe: with it set, the 16-bit and 8-bit MFMAs read a NaN
+// operand as a finite number (measured on an MI355X: a NaN activation of a bf16x3 / f16c / fp8 conv came out as an ordinary
+// value, while the fp32 MFMA and the same MFMAs in the default mode return NaN; tests/test_gpu_nonfinite.py).  A kernel that
+// issues MFMAs therefore never runs them with the bit set: it brackets the converting part of its epilogue with
+// MSR_SATURATE_BEGIN / MSR_SATURATE_END (conv_common.h msr_saturate_begin / _end tie the accumulators to the first, so that
+// every conversion follows it; the converted values reach memory, or are tied, before the second; scheduling barriers keep
+// the neighbouring MFMAs outside).  Kernels without MFMAs keep MSR_SATURATING_CONVERSIONS() as their first statement.
+#define MSR_SATURATE_BEGIN_ASM "s_setreg_imm32_b32 hwreg(HW_REG_MODE, 23, 1), 1\n\ts_nop 3"
+#define MSR_SATURATE_END_ASM "s_setreg_imm32_b32 hwreg(HW_REG_MODE, 23, 1), 0\n\ts_nop 3"
 
 // Device: 4 consecutive channels c..c+3 (c % 4 == 0) of one pixel into the pixel's f16c chunk image (PREC_F16C above).
 __device__ inline void msr_store_f16c4_dev(float* pixel, int c, float v0, float v1, float v2, float v3) {
     typedef _Float16 h2 __attribute__((ext_vector_type(2)));
     // fp16's range, not fp32's: a value beyond 65504 saturates (finite, wrong) instead of turning the conv into infinities;
-    // NaN passes through (fminf / fmaxf would drop it, the ternaries keep it)
+    // NaN passes through (fminf / fmaxf / v_med3_f32 would drop it, the ternaries keep it; every clamp and relu of the
+    // kernels keeps it the same way: tests/test_gpu_nonfinite.py)
     v0 = v0 > 65504.f ? 65504.f : (v0 < -65504.f ? -65504.f : v0);
     v1 = v1 > 65504.f ? 65504.f : (v1 < -65504.f ? -65504.f : v1);
     v2 = v2 > 65504.f ? 65504.f : (v2 < -65504.f ? -65504.f : v2);

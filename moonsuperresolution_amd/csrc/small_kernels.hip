@@ -73,7 +73,8 @@ __global__ void __launch_bounds__(256) conv_smallcin_kernel(const SmallCinParams
                 }
             }
             if (p.act == 1) {
-                acc.x = fmaxf(acc.x, 0.f); acc.y = fmaxf(acc.y, 0.f); acc.z = fmaxf(acc.z, 0.f); acc.w = fmaxf(acc.w, 0.f);
+                // relu as a comparison: fmaxf(NaN, 0) is 0, and a NaN is data that the reference keeps
+                acc.x = acc.x <= 0.f ? 0.f : acc.x; acc.y = acc.y <= 0.f ? 0.f : acc.y; acc.z = acc.z <= 0.f ? 0.f : acc.z; acc.w = acc.w <= 0.f ? 0.f : acc.w;
             } else if (p.act == 2) {
                 acc.x = acc.x >= 0.f ? acc.x : acc.x * p.slope; acc.y = acc.y >= 0.f ? acc.y : acc.y * p.slope;
                 acc.z = acc.z >= 0.f ? acc.z : acc.z * p.slope; acc.w = acc.w >= 0.f ? acc.w : acc.w * p.slope;
@@ -147,7 +148,8 @@ __global__ void __launch_bounds__(256) conv_smallcin_tiled_kernel(const SmallCin
                 }
             }
             if (p.act == 1) {
-                acc.x = fmaxf(acc.x, 0.f); acc.y = fmaxf(acc.y, 0.f); acc.z = fmaxf(acc.z, 0.f); acc.w = fmaxf(acc.w, 0.f);
+                // relu as a comparison: fmaxf(NaN, 0) is 0, and a NaN is data that the reference keeps
+                acc.x = acc.x <= 0.f ? 0.f : acc.x; acc.y = acc.y <= 0.f ? 0.f : acc.y; acc.z = acc.z <= 0.f ? 0.f : acc.z; acc.w = acc.w <= 0.f ? 0.f : acc.w;
             } else if (p.act == 2) {
                 acc.x = acc.x >= 0.f ? acc.x : acc.x * p.slope; acc.y = acc.y >= 0.f ? acc.y : acc.y * p.slope;
                 acc.z = acc.z >= 0.f ? acc.z : acc.z * p.slope; acc.w = acc.w >= 0.f ? acc.w : acc.w * p.slope;
@@ -614,9 +616,10 @@ hipError_t launch_latent(const float* mv, const float* eps, float* z, int B, int
 // pixels are zero) and every thread accumulates its 25 live taps from there; the tap weights are wave-uniform
 // (scalar loads).  HBM-bound: the half-resolution tensor is read once (x 324/256 for the halo).
 // ------------------------------------------------------------------------------------------------
+template <bool TR>       // TR: the transposed conv + tanh of pix2pix (no tap at offset +1 for parity 0)
 __global__ void __launch_bounds__(256) head_kernel(const float* __restrict__ x, const float* __restrict__ weff,
                                                    float bias, float* __restrict__ out, int B, int r, int C,
-                                                   float slope, int tanh_out, int x_py, int x_pb) {
+                                                   float slope, int x_py, int x_pb) {
     constexpr int HW = 18, HP = HW * HW, CH = 16, PITCH = CH + 4;
     __shared__ __attribute__((aligned(16))) float tile[HP * PITCH];
     const int tx = threadIdx.x & 15, ty = threadIdx.x >> 4;
@@ -674,16 +677,21 @@ __global__ void __launch_bounds__(256) head_kernel(const float* __restrict__ x, 
                     const float* w01 = wc + (size_t)((1 * 3 + dy) * 3 + dx) * C + sg * 4;
                     const float* w10 = wc + (size_t)((2 * 3 + dy) * 3 + dx) * C + sg * 4;
                     const float* w11 = wc + (size_t)((3 * 3 + dy) * 3 + dx) * C + sg * 4;
-                    o00 = fmaf(v.w, w00[3], fmaf(v.z, w00[2], fmaf(v.y, w00[1], fmaf(v.x, w00[0], o00))));
-                    if (dx > 0) o01 = fmaf(v.w, w01[3], fmaf(v.z, w01[2], fmaf(v.y, w01[1], fmaf(v.x, w01[0], o01))));
-                    if (dy > 0) o10 = fmaf(v.w, w10[3], fmaf(v.z, w10[2], fmaf(v.y, w10[1], fmaf(v.x, w10[0], o10))));
+                    // the transposed conv has no tap at offset +1 for parity 0 (head_weff_transpose leaves those weights zero):
+                    // not read, or 0 * NaN would hand a neighbour's NaN to an output that does not depend on it.  For finite
+                    // data the skipped products are exact zeros: same bits.
+                    constexpr bool TRc = TR;
+                    const bool y2 = !(TRc && dy == 2), x2 = !(TRc && dx == 2);
+                    if (y2 && x2) o00 = fmaf(v.w, w00[3], fmaf(v.z, w00[2], fmaf(v.y, w00[1], fmaf(v.x, w00[0], o00))));
+                    if (dx > 0 && y2) o01 = fmaf(v.w, w01[3], fmaf(v.z, w01[2], fmaf(v.y, w01[1], fmaf(v.x, w01[0], o01))));
+                    if (dy > 0 && x2) o10 = fmaf(v.w, w10[3], fmaf(v.z, w10[2], fmaf(v.y, w10[1], fmaf(v.x, w10[0], o10))));
                     if (dy > 0 && dx > 0)
                         o11 = fmaf(v.w, w11[3], fmaf(v.z, w11[2], fmaf(v.y, w11[1], fmaf(v.x, w11[0], o11))));
                 }
             }
     }
     o00 += bias; o01 += bias; o10 += bias; o11 += bias;
-    if (tanh_out) { o00 = tanhf(o00); o01 = tanhf(o01); o10 = tanhf(o10); o11 = tanhf(o11); }
+    if (TR) { o00 = tanhf(o00); o01 = tanhf(o01); o10 = tanhf(o10); o11 = tanhf(o11); }
     const int S2 = 2 * r;
     float* ob = out + ((size_t)b * S2 + 2 * (ty0 + ty)) * S2 + 2 * (tx0 + tx);
     *reinterpret_cast<float2*>(ob) = make_float2(o00, o01);
@@ -695,7 +703,8 @@ hipError_t launch_head(const float* x, const float* weff, float bias, float* out
     if (x_py <= 0) { x_py = r * C; x_pb = r * r * C; }
     if (r % 16 || C % 16) return hipErrorInvalidValue;
     const int blocks = B * (r / 16) * (r / 16);
-    head_kernel<<<blocks, 256, 0, s>>>(x, weff, bias, out, B, r, C, slope, tanh_out, x_py, x_pb);
+    if (tanh_out) head_kernel<true><<<blocks, 256, 0, s>>>(x, weff, bias, out, B, r, C, slope, x_py, x_pb);
+    else head_kernel<false><<<blocks, 256, 0, s>>>(x, weff, bias, out, B, r, C, slope, x_py, x_pb);
     return hipGetLastError();
 }
 

@@ -310,7 +310,9 @@ def f16c6_activation_image(x: torch.Tensor):
     hi = x.to(torch.float16)
     lo = (x - hi.float()).double()
     xb = x.double().reshape(shp[:-1] + (n, 32))
-    E = _ceil_log2_over(xb.abs().amax(-1), 7.5).clamp(-100, 120)
+    # a NaN element is left out of its block's maximum (as the kernels' fmaxf does): it is NaN in hi, its 6-bit codes are free,
+    # and the other 31 channels keep the bytes they would have had beside a zero
+    E = _ceil_log2_over(torch.where(xb.isnan(), torch.zeros_like(xb), xb.abs()).amax(-1), 7.5).clamp(-100, 120)
     s = _pow2(E)[..., None]
     ch = _e2m3_codes(xb / s)
     cl = _e2m3_codes(lo.reshape(xb.shape) / (s / 2048.0))

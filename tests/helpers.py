@@ -401,3 +401,72 @@ def gbr_term_figures(y, ref, ref32, widen=None):
     return dict(err=rel_linf_per_channel(y, ref), share=(err / bound.clamp_min(tiny)[None, :]).amax(0).cpu().numpy(),
                 share_wide=(err / lim.clamp_min(tiny)).amax(0).cpu().numpy(), beyond=(err > lim).double().mean(0).cpu().numpy(),
                 allowance=allow.cpu().numpy(), range=rng.cpu().numpy())
+
+
+# ---- NaN as data: one checker for every kernel (tests/test_nonfinite_host.py, tests/test_gpu_nonfinite.py) ------------------------
+def _np(t):
+    return t.detach().cpu().numpy() if hasattr(t, "detach") else np.asarray(t)
+
+
+def _bits(a):
+    a = np.ascontiguousarray(a)
+    return a.view({1: np.uint8, 2: np.uint16, 4: np.uint32, 8: np.uint64}[a.dtype.itemsize])
+
+
+def check_nan_contract(out, ref, clean, bound, err_fn, what="", exempt=None, raw=None):
+    """The NaN contract of one launch whose input holds planted NaN elements (include/moonsr.h "Non-finite inputs").
+      out    the kernel's output; for an image output the decoded MAIN piece (hi of the split / f16c formats, the bf8 byte)
+      ref    the float64 reference of the same operation on the same input (torch follows IEEE: a NaN reaches every element
+             that depends on it, so isnan(ref) is the plants' dependency footprint)
+      clean  the output of the same launch with the planted elements replaced by 0.0
+      bound, err_fn   the value bound of the kernel's own test: err_fn(out, ref) with the elements whose reference is not
+             finite set to 0 in both (denominators over the finite reference elements only) must be <= bound everywhere
+             (both may be arrays)
+      exempt the reason why this case may leave fewer than half of its reference elements finite (None: it may not)
+      raw    (out bytes, clean bytes, bool mask): further storage (cross pieces, scale bytes) that must be bit-identical where
+             the mask is set
+    Rules, in this order: 4 (cap, on the reference alone), 1 (mask: isnan(out) == isnan(ref) element by element), 2 (no spread:
+    outside the footprint ``out`` is ``clean`` bit for bit), 3 (value).  An AssertionError names the first offending element.
+    Returns dict(n_nan_ref, n_total, worst, bound): worst = the largest err_fn / bound share's numerator, bound its bound."""
+    out, ref, clean = _np(out), _np(ref).astype(np.float64), _np(clean)
+    assert out.shape == ref.shape == clean.shape, (what, out.shape, ref.shape, clean.shape)
+    nan_ref = np.isnan(ref)
+    finite = np.isfinite(ref)
+    assert not (~finite & ~nan_ref).any(), f"{what}: the reference holds an infinity (out of scope: choose other inputs)"
+    assert nan_ref.any(), f"{what}: the reference holds no NaN: nothing was planted where it matters"
+    if exempt is None:
+        assert 2 * int(finite.sum()) >= ref.size, f"{what}: only {int(finite.sum())} of {ref.size} reference elements are finite"
+    nan_out = np.isnan(out.astype(np.float64))
+    lost, extra = nan_ref & ~nan_out, nan_out & ~nan_ref
+    if lost.any():
+        at = tuple(int(v) for v in np.argwhere(lost)[0])
+        raise AssertionError(f"{what}: lost NaN at {at}: the kernel wrote {out[at]!r} where the reference is NaN "
+                             f"({int(lost.sum())} of {int(nan_ref.sum())} lost)")
+    if extra.any():
+        at = tuple(int(v) for v in np.argwhere(extra)[0])
+        raise AssertionError(f"{what}: spread NaN at {at}: the kernel wrote NaN where the reference is {ref[at]!r} "
+                             f"({int(extra.sum())} too many)")
+    diff = (_bits(out) != _bits(clean)) & finite
+    if diff.any():
+        at = tuple(int(v) for v in np.argwhere(diff)[0])
+        raise AssertionError(f"{what}: changed bits outside the footprint at {at}: {out[at]!r} with the NaN planted, {clean[at]!r} "
+                             f"with 0.0 in its place ({int(diff.sum())} elements)")
+    if raw is not None:
+        ro, rc, keep = _bits(_np(raw[0])), _bits(_np(raw[1])), _np(raw[2]).astype(bool)
+        rd = (ro != rc) & keep
+        if rd.any():
+            at = tuple(int(v) for v in np.argwhere(rd)[0])
+            raise AssertionError(f"{what}: changed stored bits outside the footprint at {at}: {ro[at]:#x} against {rc[at]:#x} "
+                                 f"({int(rd.sum())} storage units)")
+    err = np.asarray(err_fn(np.where(finite, out.astype(np.float64), 0.0), np.where(finite, ref, 0.0)), np.float64)
+    lim = np.nan_to_num(np.asarray(bound, np.float64), nan=0.0)
+    over = err > lim
+    if over.any():
+        at = tuple(int(v) for v in np.argwhere(over)[0]) if over.ndim else ()
+        raise AssertionError(f"{what}: finite part beyond its bound at {at}: {float(err[at]) if over.ndim else float(err):.3e} > "
+                             f"{float(np.broadcast_to(lim, err.shape)[at]) if over.ndim else float(lim):.3e}")
+    share = err / np.maximum(lim, 1e-300)
+    k = int(np.argmax(share)) if share.ndim else 0
+    worst = float(err.reshape(-1)[k]) if err.ndim else float(err)
+    return dict(n_nan_ref=int(nan_ref.sum()), n_total=int(ref.size), worst=worst,
+                bound=float(np.broadcast_to(lim, err.shape).reshape(-1)[k]) if err.ndim else float(lim))
