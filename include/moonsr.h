@@ -335,6 +335,26 @@ int msr_resize_cubic_rows(msr_handle* h, const float* src_dev, int32_t src_row0,
  * Both return the number of bytes produced, or -1 on a malformed stream / too small output buffer. */
 int64_t msr_lzw_decode(const uint8_t* in, int64_t n_in, uint8_t* out, int64_t n_out);
 int64_t msr_lzw_encode(const uint8_t* in, int64_t n_in, uint8_t* out, int64_t cap);
+/* The stream both encoders write, byte for byte the same for the same input bytes: ClearCode (256) first; codes MSB-first,
+ * 9 to 12 bits wide; first free code 258; the width grows one code early, when the next free code reaches 512 / 1024 /
+ * 2048; a ClearCode and a fresh table when it reaches 4095; after the last code the next free code advances once more (the
+ * decoder adds an entry for it) with the same width rule, then EndOfInformation (257); the last byte is padded with zero
+ * bits.  An empty input is ClearCode, EndOfInformation.  Matching is greedy longest-match, so the stream is canonical.
+ *
+ * TIFF LZW of n_strips independent strips in DEVICE memory, one launch (csrc/geotiff_codec.hip; geotiff.py
+ * write_geotiff(encoder="device")).  Strip i is src_len[i] bytes at src_dev + src_off[i]; its stream goes to
+ * dst_dev + dst_off[i], and dst_len[i] is the stream's byte count, or -1 when that exceeds dst_cap[i] (or src_len[i] < 0).
+ * No byte at or beyond dst_off[i] + dst_cap[i] is written; the slots must not overlap.  All five arrays are device memory.
+ * sample_bytes 0: the bytes are encoded as they are.  1, 2 or 4: the TIFF horizontal predictor (PREDICTOR=2) is applied on
+ * the fly to little-endian samples of that width, restarting every row_bytes (a positive multiple of sample_bytes): a strip
+ * holds whole rows, the first sample of a row passes through, the others become u[j] - u[j-1] modulo the sample width.
+ * src is not modified.  h may be NULL (the codec keeps no handle state; errors then go to msr_last_error(NULL)).
+ * MSR_ERR_INVALID before any launch for a null pointer, n_strips < 0, a sample_bytes outside {0, 1, 2, 4} or a row_bytes that
+ * is not a positive multiple of a non-zero sample_bytes.  Asynchronous on `stream`; no allocation. */
+int msr_lzw_encode_strips(msr_handle* h, const uint8_t* src_dev, const int64_t* src_off_dev, const int32_t* src_len_dev,
+                          int32_t n_strips, int32_t sample_bytes, int32_t row_bytes,
+                          uint8_t* dst_dev, const int64_t* dst_off_dev, const int32_t* dst_cap_dev, int32_t* dst_len_dev,
+                          void* stream);
 
 /* ---- measurement ----------------------------------------------------------------------------- */
 typedef struct {

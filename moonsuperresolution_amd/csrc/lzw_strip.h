@@ -1,0 +1,175 @@
+// lzw_strip.h — the TIFF 6.0 LZW encoder of ONE strip, with the horizontal predictor fused into its input fetch, as one
+// __host__ __device__ function: the kernel of geotiff_codec.hip runs it with the 64 lanes of a one-wave workgroup, a host
+// program can run it with one "lane" (nlanes = 1) under a sanitizer against msr_lzw_encode (host_codecs.cpp).
+//
+// The stream is byte for byte msr_lzw_encode's for the same (differenced) bytes: ClearCode first, MSB-first codes of 9..12
+// bits, the width grows when `next` reaches 512 / 1024 / 2048, Clear when it reaches 4095, one more ++next (and width bump)
+// before EndOfInformation, zero padding of the last byte; the empty strip is Clear, EOI.  Greedy longest match is canonical,
+// so only the dictionary's data structure differs: an open-addressing hash of (prefix code << 8 | byte) -> code.
+//
+// The automaton is serial, so every lane runs it on the same values (the state is wave-uniform and lives in registers; the
+// dictionary, the differenced input chunk and the output bytes live in the workspace, LDS on the device).  The lanes
+// share the work that is parallel: fetching and differencing 256 input bytes, clearing the table, storing the output.
+//
+// Every loop is bounded by an argument or a constant, never by table contents: the input loop by n, a probe by
+// LZW_SLOTS, the byte drain of the bit buffer by the 12-bit code width.
+#pragma once
+#include <stdint.h>
+
+#if defined(__HIPCC__)
+#define LZW_HD __host__ __device__
+#else
+#define LZW_HD
+#endif
+
+namespace msr {
+
+constexpr int LZW_SLOTS = 8192;               // hash slots: at most 3837 entries (codes 258..4094) live at once, load <= 0.47
+constexpr int LZW_CHUNK = 256;                // input bytes fetched at a time (a multiple of every sample width)
+constexpr int LZW_STAGE = 512;                // output ring: flushed 256 bytes at a time, a code adds at most 2
+constexpr uint32_t LZW_EMPTY = 0xFFFFFFFFu;   // (key << 12 | code) of no entry: it would need code 4095, which is never given
+
+struct LzwWorkspace {
+    uint32_t tab[LZW_SLOTS];                  // key << 12 | code
+    uint8_t raw[LZW_CHUNK + 4];               // the chunk as read, behind the 4 bytes before it (the previous sample)
+    alignas(4) uint8_t in[LZW_CHUNK];         // the chunk the automaton reads (four bytes at a time): differenced if a
+                                              // predictor is asked for
+    uint8_t stage[LZW_STAGE];                 // output bytes not stored yet, at position & (LZW_STAGE - 1)
+};
+
+// A value every lane holds alike (it was read from one LDS address by all of them), declared so: on the device the automaton's
+// state then lives in scalar registers and its branches are scalar, instead of 64 lanes repeating the same vector arithmetic.
+LZW_HD inline uint32_t lzw_uniform(uint32_t v) {
+#if defined(__HIP_DEVICE_COMPILE__)
+    return (uint32_t)__builtin_amdgcn_readfirstlane((int)v);
+#else
+    return v;
+#endif
+}
+
+LZW_HD inline void lzw_sync() {
+#if defined(__HIP_DEVICE_COMPILE__)
+    __syncthreads();
+#endif
+}
+
+// Bytes [base, base + LZW_CHUNK) of the strip into ws->in, zero past n.  sample_bytes 1 / 2 / 4: every sample but the
+// first of a row of row_bytes becomes u[j] - u[j-1] modulo the sample width (little-endian); 0: the bytes as they are.
+LZW_HD inline void lzw_fetch(LzwWorkspace* ws, const uint8_t* src, int32_t n, int64_t base, int32_t sample_bytes,
+                             int32_t row_bytes, int lane, int nlanes) {
+    for (int i = lane; i < LZW_CHUNK + 4; i += nlanes) {
+        const int64_t p = base + i - 4;
+        ws->raw[i] = (p >= 0 && p < n) ? src[p] : (uint8_t)0;
+    }
+    lzw_sync();
+    for (int i = lane; i < LZW_CHUNK; i += nlanes) {
+        const uint8_t* r = ws->raw + 4 + i;
+        uint8_t v = r[0];
+        if (sample_bytes > 0) {
+            const int32_t col = (int32_t)((uint32_t)(base + i) % (uint32_t)row_bytes);   // base + i < 2^31 + LZW_CHUNK
+            const int32_t k = col & (sample_bytes - 1);         // byte of the sample; samples never straddle a chunk
+            if (col - k > 0) {
+                uint32_t cur = 0, prev = 0;
+                for (int b = 0; b <= k; ++b) {                  // the borrow only travels upwards: bytes 0..k decide byte k
+                    cur |= (uint32_t)r[b - k] << (8 * b);
+                    prev |= (uint32_t)r[b - k - sample_bytes] << (8 * b);
+                }
+                v = (uint8_t)((cur - prev) >> (8 * k));
+            }
+        }
+        ws->in[i] = v;
+    }
+    lzw_sync();
+}
+
+LZW_HD inline void lzw_clear(LzwWorkspace* ws, int lane, int nlanes) {
+    for (int i = lane; i < LZW_SLOTS; i += nlanes) ws->tab[i] = LZW_EMPTY;
+    lzw_sync();
+}
+
+// Output bytes [from, to) of the ring to dst, those below cap only.
+LZW_HD inline void lzw_store(const LzwWorkspace* ws, uint8_t* dst, int64_t from, int64_t to, int64_t cap, int lane, int nlanes) {
+    lzw_sync();
+    for (int64_t i = from + lane; i < to; i += nlanes)
+        if (i < cap) dst[i] = ws->stage[i & (LZW_STAGE - 1)];
+    lzw_sync();
+}
+
+// Encodes the n bytes at src (n >= 0) to dst[0 .. cap).  Returns the stream's byte count, or -1 when it exceeds cap; no
+// byte at or beyond dst + cap is written either way.  Every lane of the nlanes that call it together gets the same result.
+LZW_HD inline int32_t lzw_encode_strip(LzwWorkspace* ws, const uint8_t* src, int32_t n, int32_t sample_bytes, int32_t row_bytes,
+                                       uint8_t* dst, int32_t cap, int lane, int nlanes) {
+    uint64_t bitbuf = 0;
+    int nbits = 0, width = 9, next = 258;
+    int64_t op = 0, stored = 0;                // bytes produced / bytes handed to lzw_store
+    const int64_t capl = cap > 0 ? cap : 0;
+
+    // a code of `width` bits behind the pending bits; whole bytes go to the ring (at most 2: nbits < 8 before)
+#define LZW_PUT(code)                                                                        \
+    do {                                                                                     \
+        bitbuf = (bitbuf << width) | (uint32_t)(code);                                       \
+        nbits += width;                                                                      \
+        for (int q_ = 0; q_ < 2 && nbits >= 8; ++q_) {                                       \
+            ws->stage[op & (LZW_STAGE - 1)] = (uint8_t)(bitbuf >> (nbits - 8));               \
+            ++op;                                                                            \
+            nbits -= 8;                                                                      \
+        }                                                                                    \
+        if (op - stored >= 256) {                                                            \
+            lzw_store(ws, dst, stored, stored + 256, capl, lane, nlanes);                    \
+            stored += 256;                                                                   \
+        }                                                                                    \
+    } while (0)
+
+    lzw_clear(ws, lane, nlanes);
+    LZW_PUT(256);
+    int cur = 0;
+    bool overflow = false;
+    for (int64_t base = 0; base < n && !overflow; base += LZW_CHUNK) {
+        lzw_fetch(ws, src, n, base, sample_bytes, row_bytes, lane, nlanes);
+        const int m = n - base < LZW_CHUNK ? (int)(n - base) : LZW_CHUNK;
+        const uint32_t* in32 = reinterpret_cast<const uint32_t*>(ws->in);
+        uint32_t word = lzw_uniform(in32[0]);
+        int i = 0;
+        if (base == 0) cur = (int)(word & 0xFF), i = 1;
+        for (; i < m; ++i) {
+            if ((i & 3) == 0) word = lzw_uniform(in32[i >> 2]);
+            const uint32_t c = (word >> (8 * (i & 3))) & 0xFF;
+            const uint32_t key = ((uint32_t)cur << 8) | c;
+            uint32_t h = (key * 2654435761u) >> 19;            // 13 bits
+            uint32_t slot = LZW_EMPTY;
+            for (int t = 0; t < LZW_SLOTS; ++t) {
+                slot = lzw_uniform(ws->tab[h]);
+                if (slot == LZW_EMPTY || (slot >> 12) == key) break;
+                h = (h + 1) & (LZW_SLOTS - 1);
+            }
+            if (slot != LZW_EMPTY && (slot >> 12) == key) { cur = (int)(slot & 0xFFF); continue; }
+            LZW_PUT(cur);
+            if (slot == LZW_EMPTY) ws->tab[h] = (key << 12) | (uint32_t)next;   // (a full table cannot happen: load <= 0.47)
+            ++next;
+            if (next == 512 || next == 1024 || next == 2048) ++width;
+            if (next == 4095) {
+                LZW_PUT(256);
+                lzw_clear(ws, lane, nlanes);
+                next = 258;
+                width = 9;
+            }
+            cur = (int)c;
+        }
+        overflow = op > capl;                  // the result is decided; what follows would only be dropped
+    }
+    if (n > 0) {
+        LZW_PUT(cur);
+        ++next;
+        if (next == 512 || next == 1024 || next == 2048) ++width;
+    }
+    LZW_PUT(257);
+    if (nbits) {
+        ws->stage[op & (LZW_STAGE - 1)] = (uint8_t)((bitbuf << (8 - nbits)) & 0xFF);
+        ++op;
+    }
+    lzw_store(ws, dst, stored, op, capl, lane, nlanes);
+#undef LZW_PUT
+    return op > capl ? -1 : (int32_t)op;
+}
+
+}  // namespace msr

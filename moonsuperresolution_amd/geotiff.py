@@ -12,7 +12,8 @@ and ``_good.tiff`` (UInt16) as LZW GeoTIFFs with ``PREDICTOR=2`` and a nodata ta
   ``rows=(r0, r1)`` reads a row window and decodes only the strips / tiles that intersect it; ``read_info`` returns the
   metadata (shape included) from the header alone — what a rank of a sharded run needs to read only its own rows.
 * write: single band, little-endian, strips, LZW + horizontal predictor (or none / deflate), classic TIFF or BigTIFF
-  chosen by size, GDAL_NODATA tag, and the GeoTIFF georeferencing tags of the input **passed through verbatim**
+  chosen by size; the strips are differenced and LZW-encoded on the host (default) or, ``encoder="device"``, on the GPU
+  (csrc/geotiff_codec.hip) with the same bytes out, GDAL_NODATA tag, and the GeoTIFF georeferencing tags of the input **passed through verbatim**
   (ModelPixelScale 33550, ModelTiepoint 33922, ModelTransformation 34264, GeoKeyDirectory 34735, GeoDoubleParams
   34736, GeoAsciiParams 34737, GDAL_METADATA 42112) — the output keeps the input's geotransform and projection
   byte for byte, which is what ``saveGTiff`` does with ``SetGeoTransform`` / ``SetProjection``.
@@ -245,10 +246,154 @@ def _cumsum_stride(b: np.ndarray, stride: int) -> np.ndarray:
 
 
 # ---- writing ------------------------------------------------------------------------------------------------------------
+def _rows_per_strip(rows: int, row_bytes: int) -> int:
+    """Strips are whole rows, at most 64 KiB of them (one row where a row is longer)."""
+    return max(1, min(rows, (1 << 16) // max(row_bytes, 1)))
+
+
+def _host_strips(arr: np.ndarray, dt: np.dtype, rps: int, comp: int, predictor: int) -> list:
+    """The strips of ``arr`` encoded on the host: NumPy differencing, then msr_lzw_encode / zlib / nothing."""
+    rows = arr.shape[0]
+    strips = []
+    for s in range(-(-rows // rps)):
+        blk = arr[s * rps:(s + 1) * rps]
+        if predictor == 2:
+            u = blk.view(np.dtype(f"<u{dt.itemsize}"))
+            d = u.copy()
+            d[:, 1:] = u[:, 1:] - u[:, :-1]
+            blk = d
+        raw = np.ascontiguousarray(blk)
+        strips.append(raw.tobytes() if comp == 1 else lzw_encode(raw) if comp == 5 else zlib.compress(raw.tobytes(), 6))
+    return strips
+
+
+def plan_bands(rows: int, row_bytes: int, rps: int, band_bytes: int) -> list:
+    """Cut the strips of a raster (``rps`` rows of ``row_bytes`` each, the last one shorter) into bands for the device
+    encoder: ``[(s0, s1), ...]``, consecutive half-open strip ranges that cover every strip once.  A band is whole strips
+    and holds at most ``band_bytes`` of raw data, unless a single strip is larger than that (then it is that strip)."""
+    n_strips = -(-rows // rps)
+    per_band = max(1, int(band_bytes) // max(rps * row_bytes, 1))
+    return [(s0, min(s0 + per_band, n_strips)) for s0 in range(0, n_strips, per_band)]
+
+
+def _torch_device(device):
+    """The CUDA device of the device encoder, or the RuntimeError of a machine without one."""
+    import torch
+    if not torch.cuda.is_available():
+        raise RuntimeError("moonsuperresolution_amd needs a HIP device (MI355X / gfx950) for encoder='device'; there is no "
+                           "CPU fallback (encoder='host' is the host codec)")
+    if device is None:
+        return torch.device("cuda", torch.cuda.current_device())
+    return torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
+
+
+def _encode_strips_device(buf, offsets, lengths, sample_bytes: int, row_bytes: int, stream=None):
+    """One msr_lzw_encode_strips launch on ``buf``'s device: (dst, dst_off, dst_len) with dst / dst_len device tensors (the
+    slots of capacity n + n // 2 + 1024 at dst_off, a host int64 array; dst_len int32, -1 = the slot was too small).
+    Asynchronous on ``stream`` (default: the current stream); the tensors it returns keep the inputs of the launch alive."""
+    import torch
+    lib = _lib.load()
+    if not (isinstance(buf, torch.Tensor) and buf.is_cuda and buf.dtype == torch.uint8 and buf.is_contiguous()):
+        raise ValueError("lzw_encode_device needs a contiguous uint8 CUDA tensor")
+    off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+    ln = np.ascontiguousarray(lengths, dtype=np.int64).reshape(-1)
+    if off.size != ln.size:
+        raise ValueError("offsets and lengths differ in length")
+    if ln.size and (ln.min() < 0 or off.min() < 0 or int((off + ln).max()) > buf.numel() or ln.max() > (1 << 30)):
+        raise ValueError("a strip lies outside the buffer (or is longer than 2^30 bytes)")
+    cap = ln + ln // 2 + 1024
+    dst_off = np.concatenate(([0], np.cumsum(cap)[:-1])).astype(np.int64) if ln.size else np.zeros(0, np.int64)
+    dev = buf.device
+    with torch.cuda.device(dev):
+        s = torch.cuda.current_stream(dev) if stream is None else stream
+        with torch.cuda.stream(s):
+            table = torch.from_numpy(np.concatenate([off, dst_off])).to(dev)              # int64: src_off | dst_off
+            table32 = torch.from_numpy(np.concatenate([ln, cap]).astype(np.int32)).to(dev)   # int32: src_len | dst_cap
+            n = int(ln.size)
+            dst = torch.empty(max(int(cap.sum()), 1), dtype=torch.uint8, device=dev)
+            dst_len = torch.full((max(n, 1),), -1, dtype=torch.int32, device=dev)
+            rc = lib.msr_lzw_encode_strips(None, buf.data_ptr(), table.data_ptr(), table32.data_ptr(), n, int(sample_bytes),
+                                           int(row_bytes), dst.data_ptr(), table.data_ptr() + 8 * n,
+                                           table32.data_ptr() + 4 * n, dst_len.data_ptr(), C.c_void_p(s.cuda_stream))
+            _lib.raise_for(lib, None, rc, "msr_lzw_encode_strips")
+            for t in (buf, table, table32):
+                t.record_stream(s)
+    return dst, dst_off, dst_len[:n]
+
+
+def _download_strips(dst, dst_off: np.ndarray, dst_len) -> list:
+    """The streams of one launch as bytes: lengths to the host, streams compacted on the device, one copy back."""
+    import torch
+    lens = dst_len.cpu().numpy().astype(np.int64)
+    if (lens < 0).any():
+        raise ValueError(f"LZW encode failed: the stream of strip {int(np.argmax(lens < 0))} does not fit its slot")
+    if not lens.size:
+        return []
+    packed = torch.cat([dst[o:o + l] for o, l in zip(dst_off.tolist(), lens.tolist())]).cpu().numpy().tobytes()
+    ends = np.cumsum(lens).tolist()
+    return [packed[e - l:e] for e, l in zip(ends, lens.tolist())]
+
+
+def lzw_encode_device(buf, offsets, lengths, sample_bytes: int = 0, row_bytes: int = 0, stream=None) -> list:
+    """TIFF LZW streams of the strips ``buf[offsets[i] : offsets[i] + lengths[i]]`` of a uint8 CUDA tensor, encoded on its
+    device in one launch (msr_lzw_encode_strips): byte for byte ``lzw_encode`` of the same bytes.  ``sample_bytes`` 1 / 2 / 4
+    applies the horizontal predictor on the fly to little-endian samples of that width, restarting every ``row_bytes``.
+    ValueError if a stream does not fit its slot of n + n // 2 + 1024 bytes (the host wrapper's rule)."""
+    import torch
+    dst, dst_off, dst_len = _encode_strips_device(buf, offsets, lengths, sample_bytes, row_bytes, stream)
+    if stream is not None:
+        torch.cuda.current_stream(buf.device).wait_stream(stream)
+    return _download_strips(dst, dst_off, dst_len)
+
+
+_TORCH_BITS = {1: "int8", 2: "int16", 4: "int32", 8: "int64"}
+
+
+def _band_bytes_on_device(data, r0: int, r1: int, dt: np.dtype, dev):
+    """Rows [r0, r1) of ``data`` (NumPy array or CUDA tensor) as the little-endian bytes of dtype ``dt`` on ``dev``."""
+    import torch
+    if not isinstance(data, torch.Tensor):
+        return torch.from_numpy(np.ascontiguousarray(data[r0:r1], dtype=dt).view(np.uint8).reshape(-1)).to(dev)
+    t = data[r0:r1].to(dev)
+    if dt.kind == "f":
+        t = t.to(torch.float32 if dt.itemsize == 4 else torch.float64)
+    else:
+        # the integer of dt's width with the same bits: through int64, narrowing wraps modulo 2^bits like NumPy's astype
+        same = not t.dtype.is_floating_point and t.dtype != torch.bool and t.element_size() == dt.itemsize
+        t = t if same else t.to(torch.int64).to(getattr(torch, _TORCH_BITS[dt.itemsize]))
+    return t.contiguous().view(torch.uint8).reshape(-1)
+
+
+def _device_strips(data, dt: np.dtype, rps: int, predictor: int, device, band_bytes: int) -> list:
+    """The strips of ``data`` LZW-encoded on the device, band by band (plan_bands): upload (or convert) a band, one launch,
+    compact, download.  Device memory is bounded by the band: about 2.5 x band_bytes plus 1 KiB per strip."""
+    rows, cols = data.shape
+    row_bytes = cols * dt.itemsize
+    dev = _torch_device(device)
+    strips = []
+    for s0, s1 in plan_bands(rows, row_bytes, rps, band_bytes):
+        r0, r1 = s0 * rps, min(s1 * rps, rows)
+        buf = _band_bytes_on_device(data, r0, r1, dt, dev)
+        starts = np.arange(r0, r1, rps, dtype=np.int64)
+        lengths = (np.minimum(starts + rps, r1) - starts) * row_bytes
+        strips += lzw_encode_device(buf, (starts - r0) * row_bytes, lengths, dt.itemsize if predictor == 2 else 0, row_bytes)
+    return strips
+
+
 def write_geotiff(path: str, data: np.ndarray, meta: Optional[dict] = None, nodata: Optional[float] = None,
-                  dtype=np.float32, compress: str = "lzw", predictor: int = 2, bigtiff: Optional[bool] = None) -> None:
+                  dtype=np.float32, compress: str = "lzw", predictor: int = 2, bigtiff: Optional[bool] = None,
+                  encoder: str = "host", device=None, band_bytes: int = 256 << 20) -> None:
     """Write a single-band GeoTIFF the way saveGTiff does (process_full_tiles.py:481-531): LZW, PREDICTOR=2,
-    nodata tag, geotransform / projection taken from ``meta`` (as returned by ``read_geotiff``)."""
+    nodata tag, geotransform / projection taken from ``meta`` (as returned by ``read_geotiff``).
+
+    ``encoder="host"`` (default) differences and encodes the strips on the host.  ``encoder="device"`` does both on the
+    GPU (msr_lzw_encode_strips) and writes the same file byte for byte: ``data`` is a NumPy array or a CUDA tensor (converted
+    to ``dtype`` on the device), ``device`` the HIP device (default: the tensor's, else the current one), and the raster
+    goes through the device in bands of whole strips of at most ``band_bytes`` raw bytes.  LZW only; no CPU fallback."""
+    if encoder not in ("host", "device"):
+        raise ValueError(f"encoder must be 'host' or 'device', got {encoder!r}")
+    if encoder == "device" and compress != "lzw":
+        raise ValueError(f"encoder='device' encodes LZW only, got compress={compress!r}")
     if data.ndim != 2:
         raise ValueError("Data must be a 2-D array (the reference raises for rank != 2 too, process_full_tiles.py:505-519).")
     dt = np.dtype(dtype).newbyteorder("<")
@@ -258,20 +403,22 @@ def write_geotiff(path: str, data: np.ndarray, meta: Optional[dict] = None, noda
     if comp == 1 or dt.itemsize == 8 and predictor == 2:
         predictor = 1
     rows, cols = data.shape
-    arr = np.ascontiguousarray(data, dtype=dt)
     row_bytes = cols * dt.itemsize
-    rps = max(1, min(rows, (1 << 16) // max(row_bytes, 1)))
-    n_strips = -(-rows // rps)
-    strips = []
-    for s in range(n_strips):
-        blk = arr[s * rps:(s + 1) * rps]
-        if predictor == 2:
-            u = blk.view(np.dtype(f"<u{dt.itemsize}"))
-            d = u.copy()
-            d[:, 1:] = u[:, 1:] - u[:, :-1]
-            blk = d
-        raw = np.ascontiguousarray(blk)
-        strips.append(raw.tobytes() if comp == 1 else lzw_encode(raw) if comp == 5 else zlib.compress(raw.tobytes(), 6))
+    rps = _rows_per_strip(rows, row_bytes)
+    if encoder == "device":
+        if device is None and not isinstance(data, np.ndarray) and getattr(data, "is_cuda", False):
+            device = data.device
+        strips = _device_strips(data, dt, rps, predictor, device, band_bytes)
+    else:
+        strips = _host_strips(np.ascontiguousarray(data, dtype=dt), dt, rps, comp, predictor)
+    _write_container(path, strips, rows, cols, dt, rps, comp, predictor, meta, nodata, bigtiff)
+
+
+def _write_container(path: str, strips: list, rows: int, cols: int, dt: np.dtype, rps: int, comp: int, predictor: int,
+                     meta: Optional[dict], nodata: Optional[float], bigtiff: Optional[bool]) -> None:
+    """The TIFF around the encoded strips: header, strips, IFD (strip offsets and byte counts, geo tags, nodata), classic
+    or BigTIFF by size."""
+    n_strips = len(strips)
     total = sum(len(s) for s in strips)
     geo = dict((meta or {}).get("geo", {}))
     big = total + 8 * n_strips * 2 + sum(len(v[2]) for v in geo.values()) + 4096 > 0xFFFF0000

@@ -80,10 +80,15 @@ class DEMSuperResolution:
             and read the records where the next tile's two counts are read (after the last tile: when the run ends), so
             the loop gains no host wait of its own.  A regime other than "parity" is kept in ``self.range_report`` and
             warned about once per run ("warn"), or raises RuntimeError when that tile's records are read ("raise").
+        encoder: "host" (default) or "device" — where saveGTiff differences and LZW-encodes the strips of the files it
+            writes (geotiff.write_geotiff); the files are the same byte for byte.
     """
 
     def __init__(self, config: DSRConfig, model: Callable = lambda x, training=False: x, device: int = 0,
-                 as_implemented: bool = True, pipeline: int = 2, range_check: str = "off") -> None:
+                 as_implemented: bool = True, pipeline: int = 2, range_check: str = "off", encoder: str = "host") -> None:
+        if encoder not in ("host", "device"):
+            raise ValueError(f"encoder must be 'host' or 'device', got {encoder!r}")
+        self.encoder = encoder                       # saveGTiff: who differences and LZW-encodes the strips (geotiff.py)
         if range_check not in ("off", "warn", "raise"):
             raise ValueError(f"range_check must be 'off', 'warn' or 'raise', got {range_check!r}")
         self.range_check = range_check
@@ -223,7 +228,7 @@ class DEMSuperResolution:
         os.makedirs(self.save_path, exist_ok=True)
         geotiff.write_geotiff(os.path.join(self.save_path, self.map_name + "_" + name + ".tiff"), data,
                               getattr(self, "geo_meta", None), nodata=self.no_value, dtype=out_type, compress="lzw",
-                              predictor=2)
+                              predictor=2, encoder=self.encoder, device=self.device)
 
     def preprocess(self, swap_dsize: bool = True, rows: Optional[Tuple[int, int]] = None) -> None:
         """process_full_tiles.py:226-244: in-fill the ortho (stored in ``self.image`` and, as in the reference, never
