@@ -389,6 +389,26 @@ int msr_op_conv3x3(msr_handle* h, const float* in_dev, const float* wt_dev, cons
                    int32_t B, int32_t rout, int32_t Cin, int32_t N, int32_t stride, int32_t epilogue,
                    const float* aux_dev, int32_t aux_shift, const float* mean_dev, const float* std_dev,
                    int32_t out_padded, int32_t tile, void* stream);
+/* Kernel-level entry of the plain fp32 conv with explicit geometry and the affine epilogue (EPI_AFFINE), as the pix2pix plan
+ * launches it: out = act(conv(in, wt) * scale[c] + shift[c]), one conv_igemm_f32 launch (plus the split-K pass for ksplit > 1).
+ *   in_dev    pointer to tap (0, 0), channel 0 of output pixel (0, 0) of sample 0: output (b, y, x) reads, for tap (kh, kw) and
+ *             channel k < Cin, in_dev[b * in_pb + (y * stride + kh) * in_py + (x * stride + kw) * in_px + k].  in_px > Cin reads a
+ *             channel slice of a wider buffer; a caller realises 'same' padding with a zero border, and a parity of a transposed conv
+ *             by advancing in_dev.  Pitches in floats, multiples of 4
+ *   wt_dev    [KH * KW][N][Cin];  scale_dev [N] or NULL (= 1);  shift_dev [N]
+ *   out_dev   output (b, y, x), channel c < N goes to out_dev[out_off + b * out_pb + y * out_py + x * out_px + c]: out_px > N
+ *             writes one half of a concat buffer, out_px = 2 * (channels per pixel) every second pixel.  Nothing else is written
+ *   rout      output side, a power of two;  Cin % 32 == 0;  N % 64 == 0 (% 128 on the 128 x 128 tile);  stride 1 | 2
+ *   act       0 none, 1 relu, 2 leaky_relu(slope)
+ *   tile      -1 auto (the planner's conv_form), else (0 = 128x128 | 1 = 64x64) + 256 * ksplit (0 or 1 = whole K; at most
+ *             KH * KW * Cin / 32 ranges)
+ * A shape the kernel has no instantiation for, a misaligned pointer or pitch, and tensors beyond 2^31 elements are MSR_ERR_INVALID
+ * with a message, checked before anything touches the device: h may be NULL for that (the text is msr_last_error(NULL)); with valid
+ * arguments a NULL handle is MSR_ERR_INVALID too.  Asynchronous on `stream`. */
+int msr_op_conv_affine(msr_handle* h, const float* in_dev, int32_t in_px, int32_t in_py, int32_t in_pb, const float* wt_dev,
+                       const float* scale_dev, const float* shift_dev, float* out_dev, int32_t out_off, int32_t out_px,
+                       int32_t out_py, int32_t out_pb, int32_t B, int32_t rout, int32_t Cin, int32_t N, int32_t KH, int32_t KW,
+                       int32_t stride, int32_t act, float slope, int32_t tile, void* stream);
 /* The same with in_dev / wt_dev holding split-bf16 words (msr_op_split_bf16) and the bf16x3 arithmetic;
  * out_split != 0 (SPADE epilogue only) writes split-bf16 words too.  tile: (0 = 128x128 | 1 = 64x64 | 3, 4 = LDS-halo
  * forms | 5 = persistent ping-pong) + 0x40 (weights in MFMA-fragment order, tiles 0 / 1) + 0x80 (tile 5, SPADE epilogue

@@ -93,6 +93,9 @@ SYMBOLS = [
     ("msr_forward_flops", C.c_int, [_P, C.POINTER(C.c_double)]),
     ("msr_op_conv3x3", C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                  _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, _P]),
+    ("msr_op_conv_affine", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32,
+                                     C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                     C.c_int32, C.c_float, C.c_int32, _P]),
     ("msr_op_conv3x3_bf16x3", C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                         C.c_int32, _P, C.c_int32, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P]),
     ("msr_op_conv3x3_f16c", C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P,

@@ -71,6 +71,62 @@ int msr_op_conv3x3_bf16x3(msr_handle* h, const float* in_dev, const float* wt_de
                         mean_dev, std_dev, out_padded, tile, PREC_BF16X3, out_split, stream);
 }
 
+int msr_op_conv_affine(msr_handle* h, const float* in_dev, int32_t in_px, int32_t in_py, int32_t in_pb, const float* wt_dev,
+                       const float* scale_dev, const float* shift_dev, float* out_dev, int32_t out_off, int32_t out_px,
+                       int32_t out_py, int32_t out_pb, int32_t B, int32_t rout, int32_t Cin, int32_t N, int32_t KH, int32_t KW,
+                       int32_t stride, int32_t act, float slope, int32_t tile, void* stream) {
+    // Everything is checked before the handle or the device is touched (h == nullptr: the message goes to msr_last_error(NULL)),
+    // so that what the kernel has no instantiation for is refused on a machine without a device too.
+    if (!in_dev || !wt_dev || !shift_dev || !out_dev)
+        return fail(h, MSR_ERR_INVALID, "msr_op_conv_affine: null argument (only scale_dev may be NULL)");
+    if (B < 1 || rout < 1 || (rout & (rout - 1)) || KH < 1 || KW < 1 || KH > 8 || KW > 8 || (stride != 1 && stride != 2) || act < 0 ||
+        act > 2)
+        return fail(h, MSR_ERR_INVALID, "msr_op_conv_affine: bad argument (B >= 1, rout a power of two, 1 <= KH, KW <= 8, stride "
+                    "1 | 2, act 0..2): B=%d rout=%d KH=%d KW=%d stride=%d act=%d", B, rout, KH, KW, stride, act);
+    if (tile < -1 || (tile >= 0 && ((tile & 0xFF) > TILE_64x64 || (tile >> 8) > 256)))
+        return fail(h, MSR_ERR_INVALID, "msr_op_conv_affine: tile 0x%x is not -1 or (0 | 1) + 256 * ksplit", tile);
+    if (Cin < 32 || Cin % 32 || N < 64 || N % 64)
+        return fail(h, MSR_ERR_INVALID, "msr_op_conv_affine: Cin = %d must be a multiple of 32 (the K-step) and N = %d of 64", Cin, N);
+    ConvForm f = conv_form(B, rout, N, stride, EPI_AFFINE, PREC_F32, Cin, KH * KW);
+    if (tile >= 0) f = make_form(PREC_F32, tile & 0xFF, (tile >> 8) > 0 ? (tile >> 8) : 1, Cin, EPI_AFFINE);
+    const int steps = KH * KW * (Cin / 32);
+    if (f.tile == TILE_128x128 && N % 128)
+        return fail(h, MSR_ERR_INVALID, "msr_op_conv_affine: the 128 x 128 tile needs N %% 128 == 0 (N = %d)", N);
+    if (f.ksplit < 1 || f.ksplit > steps)      // a K range without a step would still run the kernel's last step
+        return fail(h, MSR_ERR_INVALID, "msr_op_conv_affine: ksplit %d exceeds the %d K-steps of the shape", f.ksplit, steps);
+    // 16-byte loads of the input, float4 stores of the split-K pass; the kernels index with 32-bit offsets
+    if (in_px < Cin || in_px % 4 || in_py % 4 || in_pb % 4 || in_py < 0 || in_pb < 0 || ((uintptr_t)in_dev & 15) || ((uintptr_t)wt_dev & 15))
+        return fail(h, MSR_ERR_INVALID, "msr_op_conv_affine: input pitches (%d, %d, %d) must be multiples of 4 floats with in_px >= Cin, "
+                    "in_dev and wt_dev 16-byte aligned", in_px, in_py, in_pb);
+    if (out_off < 0 || out_px < N || out_px % 4 || out_py % 4 || out_pb % 4 || out_off % 4 || out_py < 0 || out_pb < 0 ||
+        ((uintptr_t)out_dev & 15) || ((uintptr_t)shift_dev & 15) || ((uintptr_t)scale_dev & 15))
+        return fail(h, MSR_ERR_INVALID, "msr_op_conv_affine: output offset and pitches (%d; %d, %d, %d) must be multiples of 4 floats with "
+                    "out_px >= N, out_dev, scale_dev and shift_dev 16-byte aligned", out_off, out_px, out_py, out_pb);
+    const int64_t rin = (int64_t)(rout - 1) * stride + KH, cin_last = (int64_t)(rout - 1) * stride + KW;
+    const int64_t in_span = (int64_t)(B - 1) * in_pb + (rin - 1) * in_py + (cin_last - 1) * in_px + Cin;
+    const int64_t out_span = out_off + (int64_t)(B - 1) * out_pb + (int64_t)(rout - 1) * (out_py + out_px) + N;
+    if (in_span >= ((int64_t)1 << 31) || out_span >= ((int64_t)1 << 31) || (int64_t)KH * KW * N * Cin >= ((int64_t)1 << 31))
+        return fail(h, MSR_ERR_INVALID, "msr_op_conv_affine: the tensors exceed the kernel's 32-bit element offsets");
+    if (!h) return fail(nullptr, MSR_ERR_INVALID, "msr_op_conv_affine: null handle");
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    Op op; op.type = OP_CONV; op.epi = EPI_AFFINE;        // filled as plan_pix2pix's igemm lambda fills it
+    ConvParams& c = op.conv;
+    c.in = in_dev; c.wt = wt_dev; c.bias = shift_dev; c.scale = scale_dev; c.act = act; c.slope = slope;
+    c.B = B; c.Hout = rout; c.Wout = rout; c.Cin = Cin; c.N = N; c.KH = KH; c.KW = KW; c.stride = stride;
+    c.in_px = in_px; c.in_py = in_py; c.in_pb = in_pb;
+    c.prec = f.prec; c.ksplit = f.ksplit;
+    op.tile = f.tile; op.kernel = f.kernel;
+    c.out = out_dev; c.out_off = out_off; c.out_px = out_px; c.out_py = out_py; c.out_pb = out_pb;
+    if (c.ksplit > 1) {
+        int rc = ensure_conv_partial(h, (size_t)c.ksplit * B * rout * rout * N);
+        if (rc) return rc;
+        c.partial = h->conv_partial;
+    }
+    hipError_t e = launch_conv(c, EPI_AFFINE, op.kernel, op.tile, (hipStream_t)stream);
+    if (e != hipSuccess) return fail(h, MSR_ERR_INVALID, "msr_op_conv_affine: launch rejected: %s", hipGetErrorString(e));
+    return MSR_OK;
+}
+
 int msr_op_conv3x3_f16c(msr_handle* h, const float* in_dev, const float* wt_dev, const int32_t* wexp_dev,
                         const float* bias_dev, float* out_dev, int32_t B, int32_t rout, int32_t Cin, int32_t N,
                         int32_t epilogue, const float* aux_dev, int32_t aux_shift, const float* mean_dev,

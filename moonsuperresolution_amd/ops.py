@@ -138,6 +138,24 @@ def conv3x3(ctx: OpContext, x_padded: torch.Tensor, w_kl: torch.Tensor, bias: to
     return out
 
 
+def conv_affine(ctx: Optional[OpContext], x, in_off: int, in_pitch, w_kl, scale, shift, out, out_off: int, out_pitch,
+                B: int, rout: int, cin: int, n: int, k: int, stride: int, act: int = 0, slope: float = 0.0, tile: int = -1):
+    """One msr_op_conv_affine launch on torch's current stream (include/moonsr.h): out = act(conv * scale + shift) with explicit
+    geometry.  ``x`` and ``out`` are the whole buffers; the kernel reads from element ``in_off`` of x with pitches ``in_pitch`` =
+    (px, py, pb) and writes from element ``out_off`` of out with ``out_pitch``, all in floats.  w_kl [k * k][n][cin]; scale may be
+    None.  Tensors may also be plain integer addresses, and ``ctx`` None: the entry validates before it looks at either, which is
+    how the argument checks are tested without a device."""
+    lib = ctx.lib if ctx is not None else _lib.load()
+    h = ctx.h if ctx is not None else None
+    ptr = lambda t: t if t is None or isinstance(t, int) else t.data_ptr()   # noqa: E731
+    stream = torch.cuda.current_stream(x.device).cuda_stream if isinstance(x, torch.Tensor) and x.is_cuda else None
+    rc = lib.msr_op_conv_affine(h, ptr(x) + 4 * in_off, in_pitch[0], in_pitch[1], in_pitch[2], ptr(w_kl), ptr(scale), ptr(shift),
+                                ptr(out), out_off, out_pitch[0], out_pitch[1], out_pitch[2], B, rout, cin, n, k, k, stride, act,
+                                slope, tile, stream)
+    _lib.raise_for(lib, h, rc, "msr_op_conv_affine")
+    return out
+
+
 def fp8_weight_image(w_kl: torch.Tensor):
     """Kernel-layout weights [taps][N][Cin] (fp32) -> (e4m3 bytes [taps][N][Cpad] uint8, wexp [N] int32, dequantised
     fp32 weights) exactly as msr_load_weight quantises them for the fp8 mode: a power-of-two scale per output channel

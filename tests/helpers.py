@@ -470,3 +470,104 @@ def check_nan_contract(out, ref, clean, bound, err_fn, what="", exempt=None, raw
     worst = float(err.reshape(-1)[k]) if err.ndim else float(err)
     return dict(n_nan_ref=int(nan_ref.sum()), n_total=int(ref.size), worst=worst,
                 bound=float(np.broadcast_to(lim, err.shape).reshape(-1)[k]) if err.ndim else float(lim))
+
+
+# ---- the pix2pix convs: EPI_AFFINE (tests/test_gpu_conv_affine.py, tests/test_gpu_pix2pix_sites.py) ------------------------------
+P2P_KMAP = ((3, 1), (2, 0))      # upload_conv_weight, W_P2P_UP (csrc/api.hip): kmap[parity][t] = kernel row of 2 x 2 tap t
+
+
+def p2p_parity_images(k_hwoi):
+    """Python twin of the W_P2P_UP branch of upload_conv_weight (csrc/api.hip): Conv2DTranspose kernel [4, 4, Cout, Cin] -> the
+    four parity images [py * 2 + px][t * 2 + u][Cout][Cin], image (py, px) tap (t, u) = kernel[kmap[py][t]][kmap[px][u]]."""
+    import torch
+    return torch.stack([torch.stack([k_hwoi[P2P_KMAP[py][t], P2P_KMAP[px][u]] for t in range(2) for u in range(2)])
+                        for py in range(2) for px in range(2)]).contiguous()
+
+
+def conv_taps_k(xpad, w_tnk, r, K, stride=1, oy=0, ox=0, dtype=None):
+    """conv_taps for a K x K kernel read as the igemm kernels read it: tap (kh, kw) of output (y, x) is
+    xpad[b, oy + y * stride + kh, ox + x * stride + kw]; w_tnk [K * K][N][C] -> [B, r, r, N] in ``dtype`` (float64)."""
+    import torch
+    dtype = dtype or torch.float64
+    B, C = xpad.shape[0], xpad.shape[3]
+    w = w_tnk.to(dtype)
+    out = torch.empty((B, r, r, w.shape[1]), dtype=dtype, device=xpad.device)
+    for b in range(B):
+        xb = xpad[b].to(dtype)
+        acc = torch.zeros((r * r, w.shape[1]), dtype=dtype, device=xpad.device)
+        for kh in range(K):
+            for kw in range(K):
+                sl = xb[oy + kh: oy + kh + stride * r: stride, ox + kw: ox + kw + stride * r: stride]
+                acc += sl.reshape(r * r, C) @ w[kh * K + kw].T
+        out[b] = acc.reshape(r, r, -1)
+    return out
+
+
+def conv_transpose_scatter(x, k_hwoi, dtype=None):
+    """Conv2DTranspose(4, strides 2, 'same') by its definition, input pixel (i, j) adds x[i, j] . k[kh, kw] to full-output pixel
+    (2 i + kh, 2 j + kw) and 'same' crops one pixel per side: x [B, r, r, Cin], k [4, 4, Cout, Cin] -> [B, 2 r, 2 r, Cout] in
+    ``dtype`` (float64).  No parity decomposition; sixteen matmuls, for the plain fp32 evaluation behind the K-length allowance."""
+    import torch
+    dtype = dtype or torch.float64
+    B, r = x.shape[0], x.shape[1]
+    k = k_hwoi.to(dtype)
+    out = torch.empty((B, 2 * r, 2 * r, k.shape[2]), dtype=dtype, device=x.device)
+    for b in range(B):
+        full = torch.zeros((2 * r + 2, 2 * r + 2, k.shape[2]), dtype=dtype, device=x.device)
+        xb = x[b].to(dtype).reshape(r * r, -1)
+        for kh in range(4):
+            for kw in range(4):
+                full[kh: kh + 2 * r: 2, kw: kw + 2 * r: 2] += (xb @ k[kh, kw].T).reshape(r, r, -1)
+        out[b] = full[1:-1, 1:-1]
+    return out
+
+
+def affine_act(pre, act, slope):
+    """act of EPI_AFFINE on a pre-activation tensor: 0 none, 1 relu, 2 leaky_relu(slope), in pre's dtype."""
+    import torch
+    if act == 1:
+        return torch.relu(pre)
+    if act == 2:
+        return torch.where(pre >= 0, pre, pre * slope)
+    return pre
+
+
+AFFINE_REL = 1e-5       # test_conv_bias's fp32 bound; tests/test_gpu_network_sites.py uses it for fp32 convs
+
+
+def affine_site_check(out, pre, act, slope, out32=None, what="", parity=False):
+    """The value check of one EPI_AFFINE conv, a function of (output, reference): ``out`` [B, H, W, C] what the kernel wrote,
+    ``pre`` the float64 pre-activation reference scale * conv + shift, ``out32`` a plain fp32 torch evaluation of the same terms
+    after the activation (None: no K-length allowance).  With ref = act(pre):
+      tensor        max |out - ref| / max |ref| <= 1e-5
+      per channel   max over pixels |out - ref| <= max(1e-5 * R_c, 4 * E_c), R_c = max over pixels |pre[..., c]| (before the
+                    activation: after a ReLU a channel can be all zero), E_c = max over pixels |out32 - ref| of the channel
+    -> dict(ok, tensor_rel, ratio (the largest error / bound over the channels), channel, index (b, y, x of that channel's worst
+    element), parity ((y & 1, x & 1) of it when ``parity``), message).  The message of a failure names the channel, and the parity
+    for a transposed conv's interleaved output."""
+    import torch
+    out = torch.as_tensor(out).double()
+    pre = torch.as_tensor(pre).double().to(out.device)
+    ref = affine_act(pre, act, slope)
+    C = ref.shape[-1]
+    err = (out - ref).abs()
+    tensor_rel = float(err.max() / ref.abs().max().clamp_min(1e-300))
+    ec = err.reshape(-1, C).amax(0)
+    Rc = pre.abs().reshape(-1, C).amax(0)
+    bound = AFFINE_REL * Rc
+    allow = None
+    if out32 is not None:
+        allow = 4 * (torch.as_tensor(out32).double().to(out.device) - ref).abs().reshape(-1, C).amax(0)
+        bound = torch.maximum(bound, allow)
+    share = ec / bound.clamp_min(1e-300)
+    c = int(torch.argmax(share))
+    flat = int(torch.argmax(err[..., c].reshape(-1)))
+    H, W = ref.shape[1], ref.shape[2]
+    idx = (flat // (H * W), (flat // W) % H, flat % W)
+    res = dict(ok=bool(tensor_rel <= AFFINE_REL and float(share[c]) <= 1.0), tensor_rel=tensor_rel, ratio=float(share[c]), channel=c,
+               index=idx, parity=(idx[1] & 1, idx[2] & 1) if parity else None, range=float(Rc[c]), error=float(ec[c]),
+               allowance=float(allow[c]) if allow is not None else 0.0)
+    res["message"] = (f"{what}: channel {c}" + (f", parity (y & 1, x & 1) = {res['parity']}" if parity else "") +
+                      f", element (b, y, x) = {idx}: |out - ref| = {res['error']:.3e}, {res['ratio']:.3g} x its bound "
+                      f"(1e-5 * R_c = {AFFINE_REL * res['range']:.3e}, 4 * E_c = {res['allowance']:.3e}); tensor rel L-inf {tensor_rel:.3e}")
+    return res

@@ -292,7 +292,11 @@ def test_pix2pix_against_oracle(Generator):
 
 def test_pix2pix_batched_and_repeatable(Generator):
     """B = 3 (not a power of two: the low-resolution MFMA tiles span several images and mask the tail) and a second
-    call on the same handle (the zero borders of the concat buffers must survive a forward)."""
+    call on the same handle (the zero borders of the concat buffers must survive a forward).  At B = 3 every conv of the plan
+    runs split-K on the 64 x 64 tile (msr_debug_form_table: ksplit 4 .. 16), so the tail is masked where the K ranges write
+    their partial sums and splitk_epilogue_kernel finishes every layer: no layer runs whole tiles in the kernel's own epilogue.
+    That epilogue, the 128 x 128 tile and the unsplit layers are checked by tests/test_gpu_conv_affine.py and, at B = 16, by
+    tests/test_gpu_pix2pix_sites.py."""
     from oracle import generator_ref
     w = make_weights("pix2pix", 256, seed=77, bias_scale=0.05)
     x = synthetic_patches(3, 256, 5)

@@ -16,12 +16,15 @@ of the 16 x 16 tile seam (x = 15 in row 3, x = 16 in row r - 4: footprints apart
 output: inside the cap).  Every case appends one line to parity_nonfinite.jsonl in the run-record directory.
 
 What the cases pin, site by site (DESIGN.md "Non-finite inputs"): relu written as a comparison, not fmaxf (conv_smallcin act = 1;
-EPI_AFFINE through the pix2pix network); conv_gb_resident's v_med3_f32 clamps (phase 1: the lattice cases; SPADE epilogue: x /
+EPI_AFFINE in the kernel's own epilogue and in the split-K pass, ReLU and LeakyReLU, through msr_op_conv_affine
+(test_conv_affine), and through the pix2pix network); conv_gb_resident's v_med3_f32 clamps (phase 1: the lattice cases; SPADE epilogue: x /
 mean / std); the transposed head's absent taps (test_head[True]); and MODE.FP16_OVFL: with the bit set the 16-bit and 8-bit
 MFMAs of the MI355X read a NaN operand as a finite number, so no MFMA may run with it set (every case with NaN in a conv's
 activation; for a launch that also converts to a narrow image: NaN in h with out_mode 3 / 4 / 5, the lattice cases, the fused head).
 Network level: the S = 64 generators (bf16x3 kernels and fp32), the smallest shape whose plan has a resident-kernel op and a
-stream-kernel conv in f16c / f16 / fp8 with the range report, pix2pix, and one raster through the tiler."""
+stream-kernel conv in f16c / f16 / fp8 with the range report, pix2pix, and one raster through the tiler.
+Not covered at kernel level: conv_direct_kernel (pix2pix down1), which has no entry; the pix2pix network test runs its one
+planned form."""
 import json
 import os
 import subprocess
@@ -183,6 +186,41 @@ def test_conv_fp32_spade(ctx, where):
         return y[:, 1:-1, 1:-1].numpy()
     key, plants = _spade_plant_sets(B, r, C, shift)[where]
     _check(f"conv3x3 fp32 EPI_SPADE NaN in {where}", run, _spade_ref(shift), d, key, plants, 1e-5)
+
+
+@pytest.mark.parametrize("ks", [1, 4])
+@pytest.mark.parametrize("act", [1, 2])
+@pytest.mark.parametrize("where", ["x", "w"])
+def test_conv_affine(ctx, where, act, ks):
+    """EPI_AFFINE through msr_op_conv_affine, in the kernel's own epilogue (ksplit 1) and in the split-K pass (ksplit 4), ReLU and
+    LeakyReLU(0.3): the 4 x 4 stride-2 B = 3 shape of tests/test_gpu_conv_affine.py (Cin = 64 read as channels [32, 96) of a
+    96-channel buffer, N = 64, rout = 8, 64 x 64 tile).  NaN in the activation (inside the slice), or in one weight row (tap (1, 2)
+    of output channel 37: that whole channel is NaN, 1 / 64 of the output).  Bound 1e-5 (test_conv_bias)."""
+    from moonsuperresolution_amd import ops
+    from oracle import generator_ref
+    from tests.helpers import affine_act, pad_hw
+    B, rout, cin, N, off, ctot = 3, 8, 64, 64, 32, 96
+    g = torch.Generator(device="cpu").manual_seed(990 + act)
+    d = dict(x=torch.randn((B, 2 * rout, 2 * rout, ctot), generator=g), w=torch.randn((4, 4, cin, N), generator=g) / 32,
+             scale=0.5 + 1.5 * torch.rand(N, generator=g), shift=torch.randn(N, generator=g) * 0.75)
+    slope = 0.3 if act == 2 else 0.0
+
+    def run(d):
+        out = torch.zeros((B, rout + 2, rout + 2, N + 32), device="cuda")
+        ct, rin = N + 32, 2 * rout + 2
+        ops.conv_affine(ctx, pad_hw(d["x"]).cuda().contiguous(), off, (ctot, rin * ctot, rin * rin * ctot),
+                        d["w"].reshape(16, cin, N).permute(0, 2, 1).contiguous().cuda(), d["scale"].cuda(), d["shift"].cuda(), out,
+                        (rout + 2) * ct + ct + 32, (ct, (rout + 2) * ct, (rout + 2) * (rout + 2) * ct), B, rout, cin, N, 4, 2, act, slope,
+                        1 + 256 * ks)
+        y = out.cpu()
+        assert float(y[:, 0].abs().max()) == 0 and float(y[:, :, -1].abs().max()) == 0 and float(y[..., :32].abs().max()) == 0
+        return y[:, 1:-1, 1:-1, 32:].numpy()
+
+    def ref(d):
+        pre = generator_ref.conv2d_same(d["x"][..., off:off + cin].double(), d["w"].double(), None, 2) * d["scale"].double() + d["shift"].double()
+        return affine_act(pre, act, slope)
+    plants = [(b, y, x, off + c) for b, y, x, c in _plants(B, 2 * rout, cin)] if where == "x" else [(1, 2, slice(None), 37)]
+    _check(f"conv_affine 4x4 s2 act {act} ksplit {ks} NaN in {where}", run, ref, d, where, plants, 1e-5)
 
 
 # ---- bf16x3 ----------------------------------------------------------------------------------------------------------------------
