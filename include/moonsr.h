@@ -356,6 +356,42 @@ int msr_lzw_encode_strips(msr_handle* h, const uint8_t* src_dev, const int64_t* 
                           uint8_t* dst_dev, const int64_t* dst_off_dev, const int32_t* dst_cap_dev, int32_t* dst_len_dev,
                           void* stream);
 
+/* The reverse: n_strips independent TIFF LZW blocks (strips or tiles) in DEVICE memory decoded in one launch, one block per
+ * one-wave workgroup (csrc/geotiff_codec.hip, csrc/lzw_unstrip.h; geotiff.py read_geotiff(decoder="device")).  Block i is
+ * src_len[i] bytes at src_dev + src_off[i]; its bytes go to dst_dev + dst_off[i], and dst_len[i] is what
+ * msr_lzw_decode(block i, src_len[i], slot i, dst_cap[i]) returns, with the same bytes [0, dst_len[i]), for every input,
+ * well-formed or not.  The stream rules: codes MSB-first, 9 to 12 bits wide; 256 is ClearCode and may come anywhere (twice in a
+ * row, or not at the start); 257 is EndOfInformation, bytes after it are ignored; first free code 258; the width grows when the
+ * next free code reaches 511 / 1023 / 2047; no entry is added once it is 4096 and codes stay 12 bits wide; the first code
+ * after a Clear adds no entry; a code equal to the next free code is the KwKwK case; a code above it, or a code >= 256 right
+ * after a Clear, gives -1; so does an output longer than dst_cap[i] and a negative src_len[i] or dst_cap[i]; a stream that ends
+ * without EndOfInformation gives the bytes produced so far.  In addition, 0 <= dst_len[i] < dst_cap[i] zeroes bytes
+ * [dst_len[i], dst_cap[i]) of the slot.  No byte at or beyond dst_off[i] + dst_cap[i] is written; the slots must not overlap.
+ * All five arrays are device memory.  h may be NULL.  MSR_ERR_INVALID before any launch for a null pointer or n_strips < 0;
+ * n_strips == 0 is MSR_OK without a launch.  Asynchronous on `stream`; no allocation. */
+int msr_lzw_decode_strips(msr_handle* h, const uint8_t* src_dev, const int64_t* src_off_dev, const int32_t* src_len_dev,
+                          int32_t n_strips, uint8_t* dst_dev, const int64_t* dst_off_dev, const int32_t* dst_cap_dev,
+                          int32_t* dst_len_dev, void* stream);
+/* Decoded TIFF blocks in DEVICE memory -> a float32 raster window, one launch: undoes the horizontal predictor, converts and
+ * places.  Block i is block_h rows of block_w little-endian samples (sample_kind 'u' / 'i' / 'f', sample_bytes 1, 2 or 4; float
+ * needs 4) at src_dev + blk_off[i], and its first sample is raster pixel (blk_x0[i], blk_y0[i]).  out_dev is
+ * [out_rows, cols] float32 whose first row is raster row out_row0.  For every block row inside the window: with predictor 2 the
+ * samples become the running sum along the row modulo the sample width (on the unsigned bit pattern, restarting at every block
+ * row: the bits of NumPy's cumsum on the unsigned view), with predictor 1 they are taken as they are; then (float) of the
+ * integer, float32 passing through bit for bit (NaN payloads included); columns [x0, min(x0 + block_w, cols)) are written.
+ * Rows outside the window and columns outside the raster are never written, and block rows outside the window are never
+ * read (a short last strip may end with the raster).  h may be NULL.  MSR_ERR_INVALID before any launch for a null pointer,
+ * n_blocks < 0, an unknown kind or width, a predictor other than 1 or 2, or block_w, block_h, out_rows, cols <= 0 or
+ * out_row0 < 0; n_blocks == 0 is MSR_OK without a launch.  Asynchronous on `stream`; no allocation. */
+int msr_tiff_blocks_to_f32(msr_handle* h, const uint8_t* src_dev, const int64_t* blk_off_dev, const int32_t* blk_x0_dev,
+                           const int32_t* blk_y0_dev, int32_t n_blocks, int32_t block_w, int32_t block_h, int32_t sample_kind,
+                           int32_t sample_bytes, int32_t predictor, float* out_dev, int32_t out_row0, int32_t out_rows,
+                           int32_t cols, void* stream);
+/* HOST code: the automaton msr_lzw_decode_strips runs on the device (csrc/lzw_unstrip.h), run with one lane on host buffers, so
+ * that it can be checked against msr_lzw_decode without a GPU.  The result and the bytes are msr_lzw_decode's, plus the zeroed
+ * tail [result, cap); -1 for a null pointer, a negative argument or one above INT32_MAX. */
+int64_t msr_lzw_decode_strip_host(const uint8_t* in, int64_t n_in, uint8_t* out, int64_t cap);
+
 /* ---- measurement ----------------------------------------------------------------------------- */
 typedef struct {
     char name[48];        /* kernel family, e.g. "conv_igemm_f32" */

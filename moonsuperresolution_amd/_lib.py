@@ -86,6 +86,10 @@ SYMBOLS = [
     ("msr_lzw_decode", C.c_int64, [_P, C.c_int64, _P, C.c_int64]),
     ("msr_lzw_encode", C.c_int64, [_P, C.c_int64, _P, C.c_int64]),
     ("msr_lzw_encode_strips", C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
+    ("msr_lzw_decode_strips", C.c_int, [_P, _P, _P, _P, C.c_int32, _P, _P, _P, _P, _P]),
+    ("msr_tiff_blocks_to_f32", C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
+                                         _P, C.c_int32, C.c_int32, C.c_int32, _P]),
+    ("msr_lzw_decode_strip_host", C.c_int64, [_P, C.c_int64, _P, C.c_int64]),
     ("msr_profile_enable", C.c_int, [_P, C.c_int32]),
     ("msr_profile_reset", C.c_int, [_P]),
     ("msr_profile_read", C.c_int, [_P, C.POINTER(MsrKernelStat), C.c_int32, C.POINTER(C.c_int32)]),

@@ -2,6 +2,7 @@
 // TIFF 6.0 LZW: MSB-first codes of 9..12 bits, ClearCode 256, EndOfInformation 257, first free code 258, the
 // width grows one code EARLY (at 511 / 1023 / 2047 entries), the table is cleared when it holds 4094 entries.
 #include "../../include/moonsr.h"
+#include "lzw_unstrip.h"
 
 #include <cstdint>
 #include <cstring>
@@ -54,6 +55,14 @@ int64_t msr_lzw_decode(const uint8_t* in, int64_t n_in, uint8_t* out, int64_t n_
         if (next == 511 || next == 1023 || next == 2047) ++width;   // early change
     }
     return op;
+}
+
+// The automaton the device decoder runs (lzw_unstrip.h), with one lane on host buffers: the CPU suite checks it against
+// msr_lzw_decode without a GPU.
+int64_t msr_lzw_decode_strip_host(const uint8_t* in, int64_t n_in, uint8_t* out, int64_t cap) {
+    if (!in || !out || n_in < 0 || cap < 0 || n_in > INT32_MAX || cap > INT32_MAX) return -1;
+    static thread_local msr::LzwDecodeWorkspace ws;
+    return msr::lzw_decode_strip(&ws, in, (int32_t)n_in, out, (int32_t)cap, 0, 1);
 }
 
 int64_t msr_lzw_encode(const uint8_t* in, int64_t n_in, uint8_t* out, int64_t cap) {

@@ -11,6 +11,8 @@ and ``_good.tiff`` (UInt16) as LZW GeoTIFFs with ``PREDICTOR=2`` and a nodata ta
   (band 1 is returned, like the reference); the result is float32.
   ``rows=(r0, r1)`` reads a row window and decodes only the strips / tiles that intersect it; ``read_info`` returns the
   metadata (shape included) from the header alone — what a rank of a sharded run needs to read only its own rows.
+  The blocks are decoded on the host (default) or, ``decoder="device"``, LZW files on the GPU (csrc/geotiff_codec.hip:
+  LZW per block, then predictor, conversion and placement) with the same bits out.
 * write: single band, little-endian, strips, LZW + horizontal predictor (or none / deflate), classic TIFF or BigTIFF
   chosen by size; the strips are differenced and LZW-encoded on the host (default) or, ``encoder="device"``, on the GPU
   (csrc/geotiff_codec.hip) with the same bytes out, GDAL_NODATA tag, and the GeoTIFF georeferencing tags of the input **passed through verbatim**
@@ -155,7 +157,8 @@ def read_info(path: str) -> dict:
     return _open(path)[3]
 
 
-def read_geotiff(path: str, band: int = 1, rows: Optional[Tuple[int, int]] = None):
+def read_geotiff(path: str, band: int = 1, rows: Optional[Tuple[int, int]] = None, decoder: str = "host", device=None,
+                 band_bytes: int = 256 << 20, as_tensor: bool = False):
     """Band ``band`` (1-based, like GDAL's GetRasterBand) of a (Geo)TIFF as float32, plus its metadata:
     ``{"geo": {tag: (type, count, raw bytes)}, "nodata": float | None, "dtype": numpy dtype of the file,
     "shape": (rows, cols), "byteorder": "<" | ">", "window": (r0, r1)}``.  Counterpart of loadImages
@@ -164,7 +167,18 @@ def read_geotiff(path: str, band: int = 1, rows: Optional[Tuple[int, int]] = Non
     ``rows=(r0, r1)`` returns only raster rows [r0, r1) as [r1 - r0, cols] — bit for bit the slice of the full read — and
     decodes only the strips / tiles that intersect them (blocks are compressed independently and both predictors run
     along a row, so a block never needs its neighbours).  ``meta["shape"]`` stays the file's shape; ``meta["window"]``
-    is the window returned.  ValueError unless 0 <= r0 < r1 <= rows of the file."""
+    is the window returned.  ValueError unless 0 <= r0 < r1 <= rows of the file.
+
+    ``decoder="host"`` (default) decodes block after block on the host; ``device``, ``band_bytes`` and ``as_tensor`` are not
+    looked at.  ``decoder="device"`` decodes on the GPU with the same bits out (msr_lzw_decode_strips, then
+    msr_tiff_blocks_to_f32 for predictor, conversion and placement): LZW files only, strips or tiles, classic or BigTIFF,
+    predictor 1 or 2, little-endian, 8 / 16 / 32-bit integer or 32-bit float samples, one sample per pixel and block (a
+    single-band file, or a planar one with ``band`` choosing the plane); anything else is a ValueError that names the
+    property, raised before the GPU is touched, and a machine without a GPU is a RuntimeError: there is no fallback.  The
+    blocks go through ``device`` (default: the current one) in bands of whole block rows of at most ``band_bytes``
+    decoded bytes (plan_read_bands).  ``as_tensor=True`` returns the CUDA float32 tensor instead of a NumPy array."""
+    if decoder not in ("host", "device"):
+        raise ValueError(f"decoder must be 'host' or 'device', got {decoder!r}")
     buf, t, bo, meta = _open(path)
 
     def val(tag, default=None):
@@ -197,8 +211,20 @@ def read_geotiff(path: str, band: int = 1, rows: Optional[Tuple[int, int]] = Non
     across, down = -(-cols // bw), -(-rows // bh)
     per_plane = across * down
     chunk_spp = 1 if planar == 2 else spp
-    out = np.empty((r1 - r0, cols), np.float32)
     plane0 = (band - 1) * per_plane if planar == 2 else 0
+    if decoder == "device":
+        what = (f"compression {comp} (only LZW, 5, is decoded)" if comp != 5 else
+                f"predictor {pred} (only 1 and 2 are undone)" if pred not in (1, 2) else
+                "big-endian samples" if bo == ">" else
+                f"{bps}-bit samples" if bps == 64 else
+                f"chunky multi-band blocks ({spp} samples per pixel)" if chunk_spp != 1 else None)
+        if what is not None:
+            raise ValueError(f"{path}: decoder='device' does not read {what}; decoder='host' does")
+        out = _read_blocks_device(buf, offs, cnts, plane0, across, bw, bh, tiled, dt.kind, bps // 8, pred, rows, cols, r0, r1,
+                                  device, band_bytes)
+        meta["window"] = (r0, r1)
+        return (out if as_tensor else out.cpu().numpy()), meta
+    out = np.empty((r1 - r0, cols), np.float32)
     for by in range(r0 // bh, -(-r1 // bh)):          # the block rows that intersect [r0, r1)
         for bx in range(across):
             i = plane0 + by * across + bx
@@ -276,12 +302,12 @@ def plan_bands(rows: int, row_bytes: int, rps: int, band_bytes: int) -> list:
     return [(s0, min(s0 + per_band, n_strips)) for s0 in range(0, n_strips, per_band)]
 
 
-def _torch_device(device):
-    """The CUDA device of the device encoder, or the RuntimeError of a machine without one."""
+def _torch_device(device, what: str = "encoder"):
+    """The CUDA device of the device encoder / decoder, or the RuntimeError of a machine without one."""
     import torch
     if not torch.cuda.is_available():
-        raise RuntimeError("moonsuperresolution_amd needs a HIP device (MI355X / gfx950) for encoder='device'; there is no "
-                           "CPU fallback (encoder='host' is the host codec)")
+        raise RuntimeError(f"moonsuperresolution_amd needs a HIP device (MI355X / gfx950) for {what}='device'; there is no "
+                           f"CPU fallback ({what}='host' is the host codec)")
     if device is None:
         return torch.device("cuda", torch.cuda.current_device())
     return torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
@@ -344,6 +370,119 @@ def lzw_encode_device(buf, offsets, lengths, sample_bytes: int = 0, row_bytes: i
     if stream is not None:
         torch.cuda.current_stream(buf.device).wait_stream(stream)
     return _download_strips(dst, dst_off, dst_len)
+
+
+# ---- reading on the device ------------------------------------------------------------------------------------------
+def plan_read_bands(r0: int, r1: int, block_h: int, block_row_bytes: int, band_bytes: int) -> list:
+    """Cut the block rows (rows of strips or tiles, ``block_h`` raster rows each) that hold raster rows [r0, r1) into bands
+    for the device decoder: ``[(b0, b1), ...]``, consecutive half-open ranges of block rows that cover block rows
+    r0 // block_h .. ceil(r1 / block_h) once and nothing else.  A band holds at most ``band_bytes`` of decoded data at
+    ``block_row_bytes`` a block row, unless a single block row is larger than that (then it is that block row)."""
+    first, last = r0 // block_h, -(-r1 // block_h)
+    per_band = max(1, int(band_bytes) // max(int(block_row_bytes), 1))
+    return [(b0, min(b0 + per_band, last)) for b0 in range(first, last, per_band)]
+
+
+def lzw_decode_device(buf, offsets, lengths, out_sizes, stream=None, check: bool = True):
+    """One msr_lzw_decode_strips launch on ``buf``'s device: the TIFF LZW blocks ``buf[offsets[i] : offsets[i] + lengths[i]]``
+    of a uint8 CUDA tensor decoded into slots of ``out_sizes[i]`` bytes.  Returns (dst, dst_off, dst_len): dst a uint8 device
+    tensor holding the slots at dst_off (a host int64 array; the slots start on 16-byte boundaries), dst_len the int32 device
+    tensor of what msr_lzw_decode returns for each block; a block that decodes short has its tail zeroed, like ``lzw_decode``.
+    Asynchronous on ``stream`` (default: the current stream) with ``check=False``; with ``check=True`` it waits for the
+    lengths and raises ValueError("malformed LZW stream") if one is negative, as the host path does."""
+    import torch
+    lib = _lib.load()
+    if not (isinstance(buf, torch.Tensor) and buf.is_cuda and buf.dtype == torch.uint8 and buf.is_contiguous()):
+        raise ValueError("lzw_decode_device needs a contiguous uint8 CUDA tensor")
+    off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
+    ln = np.ascontiguousarray(lengths, dtype=np.int64).reshape(-1)
+    cap = np.ascontiguousarray(out_sizes, dtype=np.int64).reshape(-1)
+    if not off.size == ln.size == cap.size:
+        raise ValueError("offsets, lengths and out_sizes differ in length")
+    if ln.size and (ln.min() < 0 or off.min() < 0 or int((off + ln).max()) > buf.numel() or ln.max() >= (1 << 31)):
+        raise ValueError("a block lies outside the buffer (or is longer than 2^31 - 1 bytes)")
+    if cap.size and (cap.min() < 0 or cap.max() >= (1 << 31)):
+        raise ValueError("an output size is negative or above 2^31 - 1 bytes")
+    slot = (cap + 15) // 16 * 16
+    dst_off = np.concatenate(([0], np.cumsum(slot)[:-1])).astype(np.int64) if cap.size else np.zeros(0, np.int64)
+    dev = buf.device
+    with torch.cuda.device(dev):
+        s = torch.cuda.current_stream(dev) if stream is None else stream
+        with torch.cuda.stream(s):
+            table = torch.from_numpy(np.concatenate([off, dst_off])).to(dev)                  # int64: src_off | dst_off
+            table32 = torch.from_numpy(np.concatenate([ln, cap]).astype(np.int32)).to(dev)       # int32: src_len | dst_cap
+            n = int(ln.size)
+            dst = torch.empty(max(int(slot.sum()), 1), dtype=torch.uint8, device=dev)
+            dst_len = torch.full((max(n, 1),), -1, dtype=torch.int32, device=dev)
+            rc = lib.msr_lzw_decode_strips(None, buf.data_ptr(), table.data_ptr(), table32.data_ptr(), n, dst.data_ptr(),
+                                           table.data_ptr() + 8 * n, table32.data_ptr() + 4 * n, dst_len.data_ptr(),
+                                           C.c_void_p(s.cuda_stream))
+            _lib.raise_for(lib, None, rc, "msr_lzw_decode_strips")
+            for t in (buf, table, table32):
+                t.record_stream(s)
+    if check:
+        if stream is not None:
+            torch.cuda.current_stream(dev).wait_stream(stream)
+        _check_decoded(dst_len[:n])
+    return dst, dst_off, dst_len[:n]
+
+
+def _check_decoded(dst_len) -> None:
+    """The host path's error for a block msr_lzw_decode rejects (waits for the lengths of the launch)."""
+    if dst_len.numel() and int(dst_len.min().item()) < 0:
+        raise ValueError("malformed LZW stream")
+
+
+def lzw_decode_device_bytes(buf, offsets, lengths, out_sizes, stream=None) -> list:
+    """``lzw_decode_device`` with the decoded blocks as ``bytes`` (each ``out_sizes[i]`` long: ``lzw_decode``'s result)."""
+    dst, dst_off, _ = lzw_decode_device(buf, offsets, lengths, out_sizes, stream)
+    host = dst.cpu().numpy()
+    return [host[o:o + c].tobytes() for o, c in zip(dst_off.tolist(), np.asarray(out_sizes, np.int64).reshape(-1).tolist())]
+
+
+def _read_blocks_device(buf, offs, cnts, plane0: int, across: int, bw: int, bh: int, tiled: bool, kind: str, sb: int,
+                        pred: int, nrows: int, cols: int, r0: int, r1: int, device, band_bytes: int):
+    """Raster rows [r0, r1) as a float32 CUDA tensor, decoded on the device band by band (plan_read_bands): gather the band's
+    compressed blocks from the memory map into one host array, upload once, one decode launch, one placement launch into the
+    [r1 - r0, cols] tensor.  Device memory is the output plus about 2.5 x band_bytes (compressed + decoded blocks)."""
+    import torch
+    lib = _lib.load()
+    dev = _torch_device(device, "decoder")
+    offs, cnts = np.asarray(offs, np.int64), np.asarray(cnts, np.int64)
+    with torch.cuda.device(dev):
+        s = torch.cuda.current_stream(dev)
+        out = torch.empty((r1 - r0, cols), dtype=torch.float32, device=dev)
+        for b0, b1 in plan_read_bands(r0, r1, bh, across * bh * bw * sb, band_bytes):
+            by = np.repeat(np.arange(b0, b1, dtype=np.int64), across)
+            bx = np.tile(np.arange(across, dtype=np.int64), b1 - b0)
+            idx = plane0 + by * across + bx
+            o = offs[idx]
+            c = np.clip(np.minimum(cnts[idx], buf.size - o), 0, None)      # a block that runs past the file's end is cut there
+            h = np.full(idx.size, bh, np.int64) if tiled else np.minimum(bh, nrows - by * bh)
+            lo, hi = int(o.min()), int((o + c).max())
+            total = int(c.sum())
+            # the file's bytes go to pinned memory (the one host copy), from where the upload is one DMA transfer
+            if hi - lo <= total + total // 4 + 4096:                       # the blocks lie (almost) back to back: one copy
+                staged = torch.empty(max(hi - lo, 1), dtype=torch.uint8, pin_memory=True)
+                staged.numpy()[:hi - lo] = buf[lo:hi]
+                src_off = o - lo
+            else:
+                src_off = np.concatenate(([0], np.cumsum(c)[:-1]))
+                staged = torch.empty(max(total, 1), dtype=torch.uint8, pin_memory=True)
+                host = staged.numpy()
+                for so, fo, n in zip(src_off.tolist(), o.tolist(), c.tolist()):
+                    host[so:so + n] = buf[fo:fo + n]
+            src = staged.to(dev, non_blocking=True)
+            dst, dst_off, dst_len = lzw_decode_device(src, src_off, c, h * bw * sb, check=False)
+            n = int(idx.size)
+            blk_off = torch.from_numpy(dst_off).to(dev)
+            origin = torch.from_numpy(np.concatenate([bx * bw, by * bh]).astype(np.int32)).to(dev)      # x0 | y0
+            rc = lib.msr_tiff_blocks_to_f32(None, dst.data_ptr(), blk_off.data_ptr(), origin.data_ptr(), origin.data_ptr() + 4 * n,
+                                            n, int(bw), int(bh), ord(kind), int(sb), int(pred), out.data_ptr(), int(r0),
+                                            int(r1 - r0), int(cols), C.c_void_p(s.cuda_stream))
+            _lib.raise_for(lib, None, rc, "msr_tiff_blocks_to_f32")
+            _check_decoded(dst_len)          # waits for the band: its buffers are free before the next one is gathered
+    return out
 
 
 _TORCH_BITS = {1: "int8", 2: "int16", 4: "int32", 8: "int64"}

@@ -82,13 +82,19 @@ class DEMSuperResolution:
             warned about once per run ("warn"), or raises RuntimeError when that tile's records are read ("raise").
         encoder: "host" (default) or "device" — where saveGTiff differences and LZW-encodes the strips of the files it
             writes (geotiff.write_geotiff); the files are the same byte for byte.
+        decoder: "host" (default) or "device" — where loadImages LZW-decodes the strips / tiles of the two input files and
+            undoes their predictor (geotiff.read_geotiff); the rasters are the same bit for bit.
     """
 
     def __init__(self, config: DSRConfig, model: Callable = lambda x, training=False: x, device: int = 0,
-                 as_implemented: bool = True, pipeline: int = 2, range_check: str = "off", encoder: str = "host") -> None:
+                 as_implemented: bool = True, pipeline: int = 2, range_check: str = "off", encoder: str = "host",
+                 decoder: str = "host") -> None:
         if encoder not in ("host", "device"):
             raise ValueError(f"encoder must be 'host' or 'device', got {encoder!r}")
         self.encoder = encoder                       # saveGTiff: who differences and LZW-encodes the strips (geotiff.py)
+        if decoder not in ("host", "device"):
+            raise ValueError(f"decoder must be 'host' or 'device', got {decoder!r}")
+        self.decoder = decoder                       # loadImages: who LZW-decodes the blocks and undoes the predictor
         if range_check not in ("off", "warn", "raise"):
             raise ValueError(f"range_check must be 'off', 'warn' or 'raise', got {range_check!r}")
         self.range_check = range_check
@@ -196,8 +202,8 @@ class DEMSuperResolution:
             raise ValueError("The path given for the ortho-image does not exist. Provided path is: " + img_path)
         if not os.path.exists(dem_path):
             raise ValueError("The path given for the dem does not exist. Provided path is: " + dem_path)
-        img, img_meta = geotiff.read_geotiff(img_path, band=1, rows=rows)
-        dem, self.geo_meta = geotiff.read_geotiff(dem_path, band=1, rows=rows)
+        img, img_meta = geotiff.read_geotiff(img_path, band=1, rows=rows, decoder=self.decoder, device=self.device)
+        dem, self.geo_meta = geotiff.read_geotiff(dem_path, band=1, rows=rows, decoder=self.decoder, device=self.device)
         self.geo_transform = geotiff.geotransform(self.geo_meta)
         if rows is None:
             self.setImages(img, dem)
