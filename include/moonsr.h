@@ -330,6 +330,51 @@ int msr_resize_cubic_rows(msr_handle* h, const float* src_dev, int32_t src_row0,
                           int32_t cols, float* dst_dev, int32_t dst_row0, int32_t dst_rows, int32_t full_dst_rows,
                           int32_t dst_cols, float no_value, int32_t flags, void* stream);
 
+/* ---- pre-processing: in-filling of small no-data holes (preprocess(infill="device")) ---------------------------------
+ * Fills, in place, the small holes of a float32 grid in DEVICE memory (csrc/infill.hip, csrc/infill_solve.h).  It stands in
+ * for fillNan / interpolateMissingValues of the reference (process_full_tiles.py:184-224) with a stated deviation: the SAME
+ * pixels are filled, with other values (a local thin-plate fill in place of griddata's cubic surface).  The NumPy twin
+ * moonsuperresolution_amd/infill.py::infill_reference defines the result; the kernels equal it bit for bit.
+ *
+ * grid_dev holds rows [row0, row0 + n_rows) of a grid of full_rows x cols.
+ *   hole       a pixel with !(G[p] > no_value); NaN is a hole.  Outside the window there are neither holes nor valid pixels.
+ *   component  an 8-connected set of holes.
+ *   fill set F every hole whose component has fewer than max_area pixels and that lies margin <= row < full_rows - margin,
+ *              margin <= col < cols - margin in whole-grid coordinates and, where the window is cut (row0 > 0, or
+ *              row0 + n_rows < full_rows), at least max_area rows from the cut.
+ *   unknowns   for each component K that meets F: the pixels of K in row-major order.
+ *   centres    K and the 4-neighbours of K; a centre is used iff each of its five stencil pixels is in K or is valid.  Every
+ *              pixel of K is a used centre, so the system below is positive definite.
+ *   equation   per used centre: -4 u(centre) + the sum of u over its four neighbours = 0, valid pixels on the right.
+ *   solution   the least-squares solution, by the normal equations in float64 and a Cholesky factorisation without
+ *              pivoting; csrc/infill_solve.h states the order of every sum.
+ *   result     rounded once to float32 and stored at K ∩ F.  Every other element of the grid keeps its bits.
+ * A window writes, at every row at least max_area rows from its cut edges, the bits the whole grid gets, and nothing at the
+ * other rows.  Only positions relative to a component enter its solution.
+ * preprocess uses (max_area, margin) = (24, 32) on the x1/4 grid and (8, 128) on the ortho: fillNan's border and
+ * max_fill_area, whose tiled census this rule reproduces.
+ * workspace_dev: msr_infill_workspace_bytes(n_rows, cols) bytes of device memory, 8-byte aligned, contents irrelevant
+ * (16 + 8 n_rows ceil(cols / 64) + 4 ceil(n_rows / 2) ceil(cols / 2); -1 for non-positive sizes or more than 2^31 - 1 pixels).
+ * h may be NULL.  MSR_ERR_INVALID, with a message that names the argument, before any launch: a null pointer, non-positive
+ * n_rows / full_rows / cols, max_area outside [2, 32], margin < max_area + 1, a window outside the grid, more than 2^31 - 1
+ * pixels in the window, a workspace that is too small or misaligned.  Asynchronous on `stream`; no allocation. */
+int64_t msr_infill_workspace_bytes(int32_t n_rows, int32_t cols);
+int msr_infill_small_holes(msr_handle* h, float* grid_dev, int32_t row0, int32_t n_rows, int32_t full_rows, int32_t cols,
+                           float no_value, int32_t max_area, int32_t margin, void* workspace_dev, int64_t workspace_bytes,
+                           void* stream);
+/* One stage of msr_infill_small_holes on its own, for timing: stage 1 labels (hole bitmap and component list into the
+ * workspace), stage 2 solves and stores what a stage 1 on the same arguments left there. */
+int msr_debug_infill_stage(msr_handle* h, float* grid_dev, int32_t row0, int32_t n_rows, int32_t full_rows, int32_t cols,
+                           float no_value, int32_t max_area, int32_t margin, void* workspace_dev, int64_t workspace_bytes,
+                           void* stream, int32_t stage);
+/* HOST code: the build-and-solve of ONE component (csrc/infill_solve.h, run with one lane), so that it can be checked against
+ * the twin without a GPU.  grid is rows x cols host float32; (pix_r[i], pix_c[i]), i < n, are the pixels of a whole component
+ * in row-major order, 1 <= n <= 31, none on the grid's outermost pixels; out[i] receives the float32 fill of pixel i.  0, or -1
+ * for a null pointer, an n outside [1, 31], a pixel outside the grid's interior or out of order, or a component wider or
+ * taller than 31. */
+int32_t msr_infill_component_host(const float* grid, int32_t rows, int32_t cols, float no_value, const int32_t* pix_r,
+                                  const int32_t* pix_c, int32_t n, float* out);
+
 /* TIFF 6.0 LZW (compression 5) of HOST buffers, for the GeoTIFF reader / writer (moonsuperresolution_amd/geotiff.py;
  * the reference reads and writes LZW GeoTIFFs through GDAL: process_full_tiles.py:158-182, 481-531).
  * Both return the number of bytes produced, or -1 on a malformed stream / too small output buffer. */

@@ -90,6 +90,12 @@ SYMBOLS = [
     ("msr_tiff_blocks_to_f32", C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                          _P, C.c_int32, C.c_int32, C.c_int32, _P]),
     ("msr_lzw_decode_strip_host", C.c_int64, [_P, C.c_int64, _P, C.c_int64]),
+    ("msr_infill_workspace_bytes", C.c_int64, [C.c_int32, C.c_int32]),
+    ("msr_infill_small_holes", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, _P,
+                                         C.c_int64, _P]),
+    ("msr_debug_infill_stage", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, _P,
+                                         C.c_int64, _P, C.c_int32]),
+    ("msr_infill_component_host", C.c_int32, [_P, C.c_int32, C.c_int32, C.c_float, _P, _P, C.c_int32, _P]),
     ("msr_profile_enable", C.c_int, [_P, C.c_int32]),
     ("msr_profile_reset", C.c_int, [_P]),
     ("msr_profile_read", C.c_int, [_P, C.POINTER(MsrKernelStat), C.c_int32, C.POINTER(C.c_int32)]),

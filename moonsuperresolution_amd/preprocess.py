@@ -7,6 +7,9 @@ also do the no-data <-> NaN marking between the steps; the full-resolution raste
 in-filling stays on the host exactly like the reference: the same ``scipy.interpolate.griddata(method="cubic")`` call on
 each tile that has holes, with ``scipy.ndimage.label`` (8-connected) in place of ``cv2.connectedComponents``.
 
+``infill="device"`` (opt-in, a stated deviation: infill.py) fills the same pixels with a local thin-plate fill on the GPU
+(``msr_infill_small_holes``): the x1/4 grid then never leaves the device between the two area steps, and no SciPy call is made.
+
 Pre-processing is local in rows: the cubic reads 4 rows of the x1/16 grid, each area step 4 source rows, and the in-filling
 works on 256-row tiles of the x1/4 grid.  ``window_plan`` states which rows of each grid a range of output rows depends on,
 and ``preprocess_rows`` computes exactly those from a row window of the input DEM — bit-identical to the same rows of the
@@ -186,10 +189,21 @@ def _fill_rows(band: np.ndarray, row0: int, h4: int, tiles, no_value: float) -> 
     return out
 
 
-def _lowres_rows(lib, handle, device, dem_window: np.ndarray, row0: int, shape: Tuple[int, int], plan, no_value: float
-                 ) -> torch.Tensor:
+INFILL_MODES = ("host", "device")
+ORTHO_AREA, ORTHO_BORDER = 8, 128                    # fillNan's max_fill_area and border on the ortho (process_full_tiles.py:229)
+
+
+def _check_infill(infill: str) -> str:
+    if infill not in INFILL_MODES:
+        raise ValueError(f"infill must be 'host' or 'device', got {infill!r}")
+    return infill
+
+
+def _lowres_rows(lib, handle, device, dem_window: np.ndarray, row0: int, shape: Tuple[int, int], plan, no_value: float,
+                 infill: str = "host") -> torch.Tensor:
     """Rows plan["d16"] of the x1/16 grid (device tensor, no-data as NaN) from a row window of the input DEM that holds
-    plan["dem"]: area on the d4 band, host in-filling of the plan's tiles, area on the in-filled rows."""
+    plan["dem"]: area on the d4 band, in-filling (host: of the plan's tiles; device: in place on the band, whose rows
+    plan["fill"] lie 32 rows from its cut edges and so take the whole grid's bits), area on the in-filled rows."""
     H = int(shape[0])
     h4 = _cv_round(H / 4)
     (m0, m1), (q0, q1), (f0, f1) = plan["dem"], plan["d4"], plan["fill"]
@@ -199,8 +213,13 @@ def _lowres_rows(lib, handle, device, dem_window: np.ndarray, row0: int, shape: 
     d = torch.from_numpy(np.ascontiguousarray(dem_window[m0 - row0:m1 - row0], dtype=np.float32)).to(device)
     d4 = _area_rows(lib, handle, d, m0, H, (q0, q1), no_value, RESIZE_NODATA_TO_NAN | RESIZE_NAN_TO_NODATA)
     del d
-    filled = _fill_rows(d4.cpu().numpy(), q0, h4, plan["tiles"], no_value)
-    d4 = torch.from_numpy(np.ascontiguousarray(filled[f0 - q0:f1 - q0])).to(device)
+    if infill == "device":
+        from .infill import infill_device
+        infill_device(lib, handle, d4, q0, h4, no_value, FILL_AREA, FILL_BORDER)
+        d4 = d4[f0 - q0:f1 - q0]
+    else:
+        filled = _fill_rows(d4.cpu().numpy(), q0, h4, plan["tiles"], no_value)
+        d4 = torch.from_numpy(np.ascontiguousarray(filled[f0 - q0:f1 - q0])).to(device)
     return _area_rows(lib, handle, d4, f0, h4, plan["d16"], no_value, RESIZE_NODATA_TO_NAN)
 
 
@@ -216,35 +235,70 @@ def _cubic_rows(lib, handle, d16: torch.Tensor, a16: int, h16: int, dst_rows: Tu
     return dst.cpu().numpy()
 
 
+def fill_ortho_device(lib, handle, device, img: np.ndarray, no_value: float, band_bytes: int = 1 << 28) -> np.ndarray:
+    """The device form of fillNan(img, no_value, 1024, 128, 8): msr_infill_small_holes with (max_area, margin) = (8, 128) on
+    bands of whole rows of at most ``band_bytes``, so that device memory stays bounded.  Consecutive bands share
+    margin + max_area = 136 rows; each gives the rows up to the middle of what it shares, which lie 68 >= max_area rows from
+    its cut edge and so hold the whole raster's bits.  Host float32."""
+    from .infill import infill_device
+    H, W = img.shape
+    share = ORTHO_BORDER + ORTHO_AREA
+    per_band = min(H, int(band_bytes) // (4 * W))
+    if per_band < H and per_band <= share:
+        raise ValueError(f"band_bytes {band_bytes} holds {per_band} rows of {W} columns: bands need more than {share}")
+    out = np.empty_like(img)
+    top = 0
+    while True:
+        end = min(top + per_band, H)
+        band = torch.from_numpy(np.ascontiguousarray(img[top:end])).to(device)
+        infill_device(lib, handle, band, top, H, no_value, ORTHO_AREA, ORTHO_BORDER)
+        a = top + share // 2 if top else 0
+        b = end - share // 2 if end < H else H
+        out[a:b] = band[a - top:b - top].cpu().numpy()
+        if end == H:
+            return out
+        top = end - share
+
+
 def preprocess_rows(lib, handle, device, dem_window: np.ndarray, row0: int, shape: Tuple[int, int],
-                    out_rows: Tuple[int, int], no_value: float) -> np.ndarray:
-    """Rows ``out_rows`` of what ``preprocess(..., swap_dsize=False)[1]`` returns for the whole raster of ``shape``, bit for
-    bit, from ``dem_window`` = its rows [row0, row0 + len(dem_window)), which must hold window_plan(shape, out_rows)["dem"]
-    (ValueError otherwise).  Only the plan's d4, fill and d16 rows are computed.  Host float32."""
+                    out_rows: Tuple[int, int], no_value: float, infill: str = "host") -> np.ndarray:
+    """Rows ``out_rows`` of what ``preprocess(..., swap_dsize=False, infill=infill)[1]`` returns for the whole raster of
+    ``shape``, bit for bit, from ``dem_window`` = its rows [row0, row0 + len(dem_window)), which must hold
+    window_plan(shape, out_rows)["dem"] (ValueError otherwise).  Only the plan's d4, fill and d16 rows are computed.  Host
+    float32."""
+    _check_infill(infill)
     H, W = int(shape[0]), int(shape[1])
     dem_window = np.asarray(dem_window, np.float32)
     if dem_window.ndim != 2 or dem_window.shape[1] != W:
         raise ValueError(f"the row window must be 2-D with the raster's {W} columns")
     plan = window_plan(shape, out_rows)
     with torch.cuda.device(device):
-        d16 = _lowres_rows(lib, handle, device, dem_window, int(row0), shape, plan, no_value)
+        d16 = _lowres_rows(lib, handle, device, dem_window, int(row0), shape, plan, no_value, infill)
         return _cubic_rows(lib, handle, d16, plan["d16"][0], _cv_round(_cv_round(H / 4) / 4), out_rows, (H, W), no_value)
 
 
 def preprocess(lib, handle, device, img: np.ndarray, dem: np.ndarray, no_value: float,
-               swap_dsize: bool = True) -> Tuple[np.ndarray, np.ndarray]:
+               swap_dsize: bool = True, infill: str = "host", band_bytes: int = 1 << 28) -> Tuple[np.ndarray, np.ndarray]:
     """process_full_tiles.py:226-244.  Returns (filled ortho, low-resolution DEM at full size), both host float32.
+
+    ``infill="host"`` (default) in-fills with SciPy's griddata like the reference; ``"device"`` fills the same pixels on the
+    GPU with the values of infill.infill_reference (a stated deviation) and makes no SciPy call: the ortho in bands of at most
+    ``band_bytes`` (fill_ortho_device), the x1/4 grid in place between the two area steps.
 
     ``swap_dsize=True`` reproduces :241, where ``self.dem_shape`` = (rows, cols) is handed to ``cv2.resize`` as
     (width, height): the result then has shape (cols, rows), so — like the reference — only square rasters survive
     the later ``padInputs``.  ``swap_dsize=False`` resizes to (rows, cols) proper: preprocess_rows with the window [0, H)."""
     img = np.asarray(img, np.float32)
     dem = np.asarray(dem, np.float32)
-    image = fillNan(img, no_value, tile_size=1024, border=128, max_fill_area=8)
+    if _check_infill(infill) == "device":
+        with torch.cuda.device(device):
+            image = fill_ortho_device(lib, handle, device, img, no_value, band_bytes)
+    else:
+        image = fillNan(img, no_value, tile_size=1024, border=ORTHO_BORDER, max_fill_area=ORTHO_AREA)
     H, W = dem.shape
     if not swap_dsize:
-        return image, preprocess_rows(lib, handle, device, dem, 0, (H, W), (0, H), no_value)
+        return image, preprocess_rows(lib, handle, device, dem, 0, (H, W), (0, H), no_value, infill)
     h16 = _cv_round(_cv_round(H / 4) / 4)
     with torch.cuda.device(device):      # every row of the x1/16 grid, then the cubic to W rows of H columns
-        d16 = _lowres_rows(lib, handle, device, dem, 0, (H, W), _plan_from_d16((H, W), 0, h16), no_value)
+        d16 = _lowres_rows(lib, handle, device, dem, 0, (H, W), _plan_from_d16((H, W), 0, h16), no_value, infill)
         return image, _cubic_rows(lib, handle, d16, 0, h16, (0, W), (W, H), no_value)

@@ -84,17 +84,24 @@ class DEMSuperResolution:
             writes (geotiff.write_geotiff); the files are the same byte for byte.
         decoder: "host" (default) or "device" — where loadImages LZW-decodes the strips / tiles of the two input files and
             undoes their predictor (geotiff.read_geotiff); the rasters are the same bit for bit.
+        infill: "host" (default) or "device" — where preprocess in-fills the small no-data holes of the ortho and of the x1/4
+            grid.  "host" is the reference's griddata surface, tile by tile (SciPy).  "device" fills THE SAME PIXELS with
+            other values (infill.py: a local thin-plate fill, defined by infill.infill_reference, which the kernel equals bit
+            for bit); the x1/4 grid then stays on the GPU between the two area steps and no SciPy call is made.
     """
 
     def __init__(self, config: DSRConfig, model: Callable = lambda x, training=False: x, device: int = 0,
                  as_implemented: bool = True, pipeline: int = 2, range_check: str = "off", encoder: str = "host",
-                 decoder: str = "host") -> None:
+                 decoder: str = "host", infill: str = "host") -> None:
         if encoder not in ("host", "device"):
             raise ValueError(f"encoder must be 'host' or 'device', got {encoder!r}")
         self.encoder = encoder                       # saveGTiff: who differences and LZW-encodes the strips (geotiff.py)
         if decoder not in ("host", "device"):
             raise ValueError(f"decoder must be 'host' or 'device', got {decoder!r}")
         self.decoder = decoder                       # loadImages: who LZW-decodes the blocks and undoes the predictor
+        if infill not in ("host", "device"):
+            raise ValueError(f"infill must be 'host' or 'device', got {infill!r}")
+        self.infill = infill                         # preprocess: who fills the small no-data holes (preprocess.py, infill.py)
         if range_check not in ("off", "warn", "raise"):
             raise ValueError(f"range_check must be 'off', 'warn' or 'raise', got {range_check!r}")
         self.range_check = range_check
@@ -239,7 +246,8 @@ class DEMSuperResolution:
     def preprocess(self, swap_dsize: bool = True, rows: Optional[Tuple[int, int]] = None) -> None:
         """process_full_tiles.py:226-244: in-fill the ortho (stored in ``self.image`` and, as in the reference, never
         used afterwards), then replace ``self.dem`` by the synthesised low-resolution DEM (x1/4 area, in-fill, x1/4
-        area, cubic back to full size).  Resamplers on the GPU, in-filling with SciPy on the host (preprocess.py).
+        area, cubic back to full size).  Resamplers on the GPU; in-filling with SciPy on the host, or with ``infill="device"``
+        (constructor) on the GPU: the same pixels, other values (preprocess.py, infill.py).
 
         ``swap_dsize=True`` keeps the reference's (rows, cols)-as-(width, height) argument of :241, so a non-square
         raster ends with a transposed-shape DEM and fails in padInputs exactly as the reference does; pass False to
@@ -264,7 +272,7 @@ class DEMSuperResolution:
             raise ValueError(f"preprocess works on whole rasters: rows [{self.row0}, {self.row0 + self.dem.shape[0]}) of "
                              f"{self.dem_shape[0]} are set as a row window")
         self.image, self.dem = pp.preprocess(self._lib, self._h, self.device, self.img, self.dem, self.no_value,
-                                             swap_dsize=swap_dsize)
+                                             swap_dsize=swap_dsize, infill=self.infill)
 
     def _preprocess_rows(self, pp, swap_dsize: bool, rows: Tuple[int, int]) -> None:
         H, W = self.dem_shape
@@ -280,7 +288,8 @@ class DEMSuperResolution:
             missing = [f"[{a}, {b})" for a, b in ((need[0], min(need[1], have[0])), (max(need[0], have[1]), need[1])) if b > a]
             raise ValueError(f"preprocess(rows=({r0}, {r1})) reads raster rows [{need[0]}, {need[1]}); the row window "
                              f"[{have[0]}, {have[1]}) held lacks rows {' and '.join(missing)}")
-        dem = pp.preprocess_rows(self._lib, self._h, self.device, self.dem, self.row0, self.dem_shape, rows, self.no_value)
+        dem = pp.preprocess_rows(self._lib, self._h, self.device, self.dem, self.row0, self.dem_shape, rows, self.no_value,
+                                 infill=self.infill)
         img = np.ascontiguousarray(self.img[r0 - self.row0:r1 - self.row0])
         self.setImages(img, dem, row0=r0, full_shape=self.dem_shape)
         self.image = None
