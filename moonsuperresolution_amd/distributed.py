@@ -82,11 +82,16 @@ def all_gather_rows(local, n_rows: int, T: int, world: int):
 
 def process_map_sharded(shape: Tuple[int, int], tile_size: int, tiles: Sequence[Tuple[int, int]],
                         process_tile: Callable[[int, int], Tuple[np.ndarray, np.ndarray, np.ndarray]],
-                        rank: int = 0, world: int = 1, gather: bool = True, device=None):
+                        rank: int = 0, world: int = 1, gather: bool = True, device=None, as_tensor: bool = False,
+                        transfers=None, local: bool = False):
     """Run this rank's tile rows and (optionally) all-gather the finished rows into the full map on every rank.
 
     process_tile(xx, yy) -> (mean f32 [T,T], std f32 [T,T], good u8 [T,T]) (host arrays or torch tensors).
-    Returns (mean, std, good) cropped to ``shape``; without ``gather`` rows of other ranks stay zero.
+    Returns (mean, std, good) cropped to ``shape``; without ``gather`` rows of other ranks stay zero.  They are host
+    arrays, or with ``as_tensor`` the tensors on ``device`` themselves (the crop is a view): nothing is downloaded.
+    ``local`` (with ``as_tensor``): no collective and no full map — only the rows this rank computed, clipped to ``shape``:
+    rows strip_plan(...)["rows"][rank] of the products.  ``transfers``: a list that takes ("d2h", bytes, what) for every
+    product downloaded (DEMSuperResolution.transfers).
     """
     import torch
     h, w = shape
@@ -106,6 +111,11 @@ def process_map_sharded(shape: Tuple[int, int], tile_size: int, tiles: Sequence[
         mean[r0:r0 + T, xx:xx + T] = torch.as_tensor(m).to(dev)
         std[r0:r0 + T, xx:xx + T] = torch.as_tensor(s).to(dev)
         good[r0:r0 + T, xx:xx + T] = torch.as_tensor(g).to(dev)
+    if local:
+        if not as_tensor:
+            raise ValueError("local=True returns this rank's rows as tensors: pass as_tensor=True")
+        first = my_rows[0] if my_rows else 0
+        return tuple(t[:max(0, min(t.shape[0], h - first)), :w] for t in (mean, std, good))
     if world > 1 and gather:
         mean, std, good = (all_gather_rows(t, len(rows), T, world) for t in (mean, std, good))
     elif world > 1:
@@ -115,6 +125,11 @@ def process_map_sharded(shape: Tuple[int, int], tile_size: int, tiles: Sequence[
             for f, t in zip(full, (mean, std, good)):
                 f[r0:r0 + t.shape[0]] = t
         mean, std, good = full
+    if as_tensor:
+        return tuple(t[:h, :w] for t in (mean, std, good))
+    if transfers is not None and mean.is_cuda:
+        for name, t in zip(("mean", "std", "good"), (mean, std, good)):
+            transfers.append(("d2h", h * w * t.element_size(), f"{name} product"))
     return tuple(t[:h, :w].cpu().numpy() for t in (mean, std, good))
 
 
@@ -276,6 +291,40 @@ def crop_for_rank(dsr, rank: int, world: int, mode: str = "tiles") -> Tuple[int,
     if a < 0 or b > dsr.dem.shape[0]:
         raise ValueError(f"the rasters held (rows [{dsr.row0}, {dsr.row0 + dsr.dem.shape[0]})) do not contain rank "
                          f"{rank}'s rows [{r0}, {r1})")
-    dsr.setImages(np.ascontiguousarray(dsr.img[a:b]), np.ascontiguousarray(dsr.dem[a:b]), row0=r0,
-                  full_shape=dsr.dem_shape)
+    if isinstance(dsr.img, np.ndarray):
+        img, dem = np.ascontiguousarray(dsr.img[a:b]), np.ascontiguousarray(dsr.dem[a:b])
+    else:                                            # resident rasters: a copy on the device, so that the rest is released
+        img, dem = dsr.img[a:b].clone(), dsr.dem[a:b].clone()
+    dsr.setImages(img, dem, row0=r0, full_shape=dsr.dem_shape)
     return r0, r1
+
+
+# ----------------------------------------------------------------------------------------------------------------
+# Rank-local product encoding: which strips of a product file a rank can encode from the rows it computed
+# ----------------------------------------------------------------------------------------------------------------
+def strip_plan(shape: Tuple[int, int], itemsize: int, tile_size: int, world: int) -> dict:
+    """The strips of one product file of a raster of ``shape`` = (H, W) with ``itemsize`` bytes a sample, over the ranks of
+    a tile-row-sharded run (processFiles(mode="tiles", products="rank0")).  Pure arithmetic; no torch, no library.
+
+      rps        geotiff._rows_per_strip(H, W * itemsize): strip k holds rows [k rps, min((k + 1) rps, H))
+      n_strips   ceil(H / rps)
+      rows       per rank, the product rows [r0, r1) it computes: its tile rows (rows_of_rank) x tile_size, clipped to H;
+                 (H, H) or the like, r0 == r1, for a rank without rows
+      straddles  True when a strip holds rows of two ranks: a rank boundary inside the raster that is no multiple of rps.
+                 Rank-local encoding needs False (for every product dtype of the run)
+      strips     per rank, the strips [s0, s1) it encodes — consecutive ranges that cover every strip once, (s, s) for a
+                 rank without rows; None when ``straddles``"""
+    from .geotiff import _rows_per_strip
+    H, W = int(shape[0]), int(shape[1])
+    if H < 1 or W < 1 or itemsize < 1 or tile_size < 1 or world < 1:
+        raise ValueError("strip_plan needs a non-empty raster, itemsize, tile_size and world >= 1")
+    rps = _rows_per_strip(H, W * int(itemsize))
+    n_strips = -(-H // rps)
+    n_tile_rows = -(-H // tile_size)
+    rows = []
+    for r in range(world):
+        first, count = rows_of_rank(n_tile_rows, r, world)
+        rows.append((min(first * tile_size, H), min((first + count) * tile_size, H)))
+    straddles = any(0 < r0 < H and r0 % rps for r0, _ in rows)
+    strips = None if straddles else [(-(-r0 // rps), -(-r1 // rps)) for r0, r1 in rows]
+    return {"rps": rps, "n_strips": n_strips, "rows": rows, "straddles": straddles, "strips": strips}

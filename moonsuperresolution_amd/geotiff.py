@@ -158,7 +158,7 @@ def read_info(path: str) -> dict:
 
 
 def read_geotiff(path: str, band: int = 1, rows: Optional[Tuple[int, int]] = None, decoder: str = "host", device=None,
-                 band_bytes: int = 256 << 20, as_tensor: bool = False):
+                 band_bytes: int = 256 << 20, as_tensor: bool = False, transfers: Optional[list] = None):
     """Band ``band`` (1-based, like GDAL's GetRasterBand) of a (Geo)TIFF as float32, plus its metadata:
     ``{"geo": {tag: (type, count, raw bytes)}, "nodata": float | None, "dtype": numpy dtype of the file,
     "shape": (rows, cols), "byteorder": "<" | ">", "window": (r0, r1)}``.  Counterpart of loadImages
@@ -176,7 +176,9 @@ def read_geotiff(path: str, band: int = 1, rows: Optional[Tuple[int, int]] = Non
     single-band file, or a planar one with ``band`` choosing the plane); anything else is a ValueError that names the
     property, raised before the GPU is touched, and a machine without a GPU is a RuntimeError: there is no fallback.  The
     blocks go through ``device`` (default: the current one) in bands of whole block rows of at most ``band_bytes``
-    decoded bytes (plan_read_bands).  ``as_tensor=True`` returns the CUDA float32 tensor instead of a NumPy array."""
+    decoded bytes (plan_read_bands).  ``as_tensor=True`` returns the CUDA float32 tensor instead of a NumPy array.
+    ``transfers``: a list that takes ``(direction, bytes, what)`` for every copy between host and device this read issues
+    (DEMSuperResolution.transfers): the compressed blocks and their bookkeeping going up, the raster coming down."""
     if decoder not in ("host", "device"):
         raise ValueError(f"decoder must be 'host' or 'device', got {decoder!r}")
     buf, t, bo, meta = _open(path)
@@ -221,8 +223,10 @@ def read_geotiff(path: str, band: int = 1, rows: Optional[Tuple[int, int]] = Non
         if what is not None:
             raise ValueError(f"{path}: decoder='device' does not read {what}; decoder='host' does")
         out = _read_blocks_device(buf, offs, cnts, plane0, across, bw, bh, tiled, dt.kind, bps // 8, pred, rows, cols, r0, r1,
-                                  device, band_bytes)
+                                  device, band_bytes, transfers)
         meta["window"] = (r0, r1)
+        if not as_tensor and transfers is not None:
+            transfers.append(("d2h", out.numel() * 4, "decoded raster"))
         return (out if as_tensor else out.cpu().numpy()), meta
     out = np.empty((r1 - r0, cols), np.float32)
     for by in range(r0 // bh, -(-r1 // bh)):          # the block rows that intersect [r0, r1)
@@ -441,7 +445,8 @@ def lzw_decode_device_bytes(buf, offsets, lengths, out_sizes, stream=None) -> li
 
 
 def _read_blocks_device(buf, offs, cnts, plane0: int, across: int, bw: int, bh: int, tiled: bool, kind: str, sb: int,
-                        pred: int, nrows: int, cols: int, r0: int, r1: int, device, band_bytes: int):
+                        pred: int, nrows: int, cols: int, r0: int, r1: int, device, band_bytes: int,
+                        transfers: Optional[list] = None):
     """Raster rows [r0, r1) as a float32 CUDA tensor, decoded on the device band by band (plan_read_bands): gather the band's
     compressed blocks from the memory map into one host array, upload once, one decode launch, one placement launch into the
     [r1 - r0, cols] tensor.  Device memory is the output plus about 2.5 x band_bytes (compressed + decoded blocks)."""
@@ -473,6 +478,12 @@ def _read_blocks_device(buf, offs, cnts, plane0: int, across: int, bw: int, bh: 
                 for so, fo, n in zip(src_off.tolist(), o.tolist(), c.tolist()):
                     host[so:so + n] = buf[fo:fo + n]
             src = staged.to(dev, non_blocking=True)
+            if transfers is not None:
+                # per block: offset and slot (2 x int64), length and capacity (2 x int32), decoded offset (int64), origin
+                # (2 x int32) going up; the band's smallest decoded length coming down (_check_decoded)
+                transfers.append(("h2d", staged.numel(), "compressed input blocks"))
+                transfers.append(("h2d", 40 * int(idx.size), "block tables of the decoder"))
+                transfers.append(("d2h", 4, "decode status"))
             dst, dst_off, dst_len = lzw_decode_device(src, src_off, c, h * bw * sb, check=False)
             n = int(idx.size)
             blk_off = torch.from_numpy(dst_off).to(dev)
@@ -493,17 +504,26 @@ def _band_bytes_on_device(data, r0: int, r1: int, dt: np.dtype, dev):
     import torch
     if not isinstance(data, torch.Tensor):
         return torch.from_numpy(np.ascontiguousarray(data[r0:r1], dtype=dt).view(np.uint8).reshape(-1)).to(dev)
-    t = data[r0:r1].to(dev)
+    t = data[r0:r1]                                  # a view: possibly cropped (not contiguous), possibly on another device
+    integer = not t.dtype.is_floating_point and t.dtype != torch.bool
     if dt.kind == "f":
-        t = t.to(torch.float32 if dt.itemsize == 4 else torch.float64)
+        target = torch.float32 if dt.itemsize == 4 else torch.float64
+    elif integer and t.element_size() == dt.itemsize:
+        target = t.dtype                             # the same bits already
     else:
-        # the integer of dt's width with the same bits: through int64, narrowing wraps modulo 2^bits like NumPy's astype
-        same = not t.dtype.is_floating_point and t.dtype != torch.bool and t.element_size() == dt.itemsize
-        t = t if same else t.to(torch.int64).to(getattr(torch, _TORCH_BITS[dt.itemsize]))
-    return t.contiguous().view(torch.uint8).reshape(-1)
+        target = getattr(torch, _TORCH_BITS[dt.itemsize])
+        if not (integer and t.element_size() < dt.itemsize):
+            # through int64: narrowing wraps modulo 2^bits like NumPy's astype.  An integer that only widens (uint8 ->
+            # 16 bits: the ``good`` product) keeps its value in the direct conversion below and needs no such temporary
+            t = t.to(torch.int64)
+    # ONE strided copy: conversion, compaction of the cropped view and the change of device at once
+    out = torch.empty(t.shape, dtype=target, device=dev)
+    out.copy_(t)
+    return out.view(torch.uint8).reshape(-1)
 
 
-def _device_strips(data, dt: np.dtype, rps: int, predictor: int, device, band_bytes: int) -> list:
+def _device_strips(data, dt: np.dtype, rps: int, predictor: int, device, band_bytes: int,
+                   transfers: Optional[list] = None) -> list:
     """The strips of ``data`` LZW-encoded on the device, band by band (plan_bands): upload (or convert) a band, one launch,
     compact, download.  Device memory is bounded by the band: about 2.5 x band_bytes plus 1 KiB per strip."""
     rows, cols = data.shape
@@ -515,41 +535,80 @@ def _device_strips(data, dt: np.dtype, rps: int, predictor: int, device, band_by
         buf = _band_bytes_on_device(data, r0, r1, dt, dev)
         starts = np.arange(r0, r1, rps, dtype=np.int64)
         lengths = (np.minimum(starts + rps, r1) - starts) * row_bytes
-        strips += lzw_encode_device(buf, (starts - r0) * row_bytes, lengths, dt.itemsize if predictor == 2 else 0, row_bytes)
+        band = lzw_encode_device(buf, (starts - r0) * row_bytes, lengths, dt.itemsize if predictor == 2 else 0, row_bytes)
+        if transfers is not None:
+            if isinstance(data, np.ndarray):
+                transfers.append(("h2d", buf.numel(), "raw product band"))
+            # per strip: offset and slot (2 x int64), length and capacity (2 x int32) going up, the stream's length coming down
+            transfers.append(("h2d", 24 * len(band), "strip tables of the encoder"))
+            transfers.append(("d2h", 4 * len(band), "encoded strip lengths"))
+            transfers.append(("d2h", sum(len(s) for s in band), "compressed output strips"))
+        strips += band
     return strips
 
 
-def write_geotiff(path: str, data: np.ndarray, meta: Optional[dict] = None, nodata: Optional[float] = None,
-                  dtype=np.float32, compress: str = "lzw", predictor: int = 2, bigtiff: Optional[bool] = None,
-                  encoder: str = "host", device=None, band_bytes: int = 256 << 20) -> None:
-    """Write a single-band GeoTIFF the way saveGTiff does (process_full_tiles.py:481-531): LZW, PREDICTOR=2,
-    nodata tag, geotransform / projection taken from ``meta`` (as returned by ``read_geotiff``).
-
-    ``encoder="host"`` (default) differences and encodes the strips on the host.  ``encoder="device"`` does both on the
-    GPU (msr_lzw_encode_strips) and writes the same file byte for byte: ``data`` is a NumPy array or a CUDA tensor (converted
-    to ``dtype`` on the device), ``device`` the HIP device (default: the tensor's, else the current one), and the raster
-    goes through the device in bands of whole strips of at most ``band_bytes`` raw bytes.  LZW only; no CPU fallback."""
+def _checked_format(dtype, compress: str, predictor: int, encoder: str):
+    """(little-endian dtype, compression tag, predictor in force) of a file to write, or the ValueError of write_geotiff."""
     if encoder not in ("host", "device"):
         raise ValueError(f"encoder must be 'host' or 'device', got {encoder!r}")
     if encoder == "device" and compress != "lzw":
         raise ValueError(f"encoder='device' encodes LZW only, got compress={compress!r}")
-    if data.ndim != 2:
-        raise ValueError("Data must be a 2-D array (the reference raises for rank != 2 too, process_full_tiles.py:505-519).")
     dt = np.dtype(dtype).newbyteorder("<")
     if dt.kind not in "uif" or dt.itemsize not in (1, 2, 4, 8):
         raise ValueError(f"unsupported dtype {dtype}")
     comp = {"none": 1, "lzw": 5, "deflate": 8}[compress]
     if comp == 1 or dt.itemsize == 8 and predictor == 2:
         predictor = 1
-    rows, cols = data.shape
-    row_bytes = cols * dt.itemsize
-    rps = _rows_per_strip(rows, row_bytes)
+    return dt, comp, predictor
+
+
+def encode_strips(data, dtype, rps: int, compress: str = "lzw", predictor: int = 2, encoder: str = "host", device=None,
+                  band_bytes: int = 256 << 20, transfers: Optional[list] = None) -> list:
+    """The encoded strips of ``rps`` rows each (the last one shorter) of the 2-D ``data`` converted to ``dtype``: what
+    write_geotiff puts into the file for these rows.  Strips are encoded independently, so the strips of rows [a, b) of a
+    raster, a a multiple of the raster's ``rps``, are those strips of the whole raster's file: a rank of a sharded run
+    encodes the rows it computed (distributed.strip_plan) and write_strips puts the file together.  ``encoder``,
+    ``device``, ``band_bytes``: write_geotiff's; ``transfers``: a list that takes ``(direction, bytes, what)`` for every
+    copy between host and device the device encoder issues (DEMSuperResolution.transfers)."""
+    dt, comp, predictor = _checked_format(dtype, compress, predictor, encoder)
+    if data.ndim != 2:
+        raise ValueError("Data must be a 2-D array (the reference raises for rank != 2 too, process_full_tiles.py:505-519).")
     if encoder == "device":
         if device is None and not isinstance(data, np.ndarray) and getattr(data, "is_cuda", False):
             device = data.device
-        strips = _device_strips(data, dt, rps, predictor, device, band_bytes)
-    else:
-        strips = _host_strips(np.ascontiguousarray(data, dtype=dt), dt, rps, comp, predictor)
+        return _device_strips(data, dt, rps, predictor, device, band_bytes, transfers)
+    return _host_strips(np.ascontiguousarray(data, dtype=dt), dt, rps, comp, predictor)
+
+
+def write_strips(path: str, strips: list, shape: Tuple[int, int], dtype, rps: int, meta: Optional[dict] = None,
+                 nodata: Optional[float] = None, compress: str = "lzw", predictor: int = 2,
+                 bigtiff: Optional[bool] = None) -> None:
+    """The file write_geotiff writes for a raster of ``shape``, from its encoded strips in order (encode_strips, with the
+    same ``dtype``, ``rps``, ``compress`` and ``predictor``)."""
+    dt, comp, predictor = _checked_format(dtype, compress, predictor, "host")
+    rows, cols = int(shape[0]), int(shape[1])
+    if len(strips) != -(-rows // rps):
+        raise ValueError(f"{len(strips)} strips for {rows} rows of {rps} a strip")
+    _write_container(path, strips, rows, cols, dt, rps, comp, predictor, meta, nodata, bigtiff)
+
+
+def write_geotiff(path: str, data: np.ndarray, meta: Optional[dict] = None, nodata: Optional[float] = None,
+                  dtype=np.float32, compress: str = "lzw", predictor: int = 2, bigtiff: Optional[bool] = None,
+                  encoder: str = "host", device=None, band_bytes: int = 256 << 20, transfers: Optional[list] = None) -> None:
+    """Write a single-band GeoTIFF the way saveGTiff does (process_full_tiles.py:481-531): LZW, PREDICTOR=2,
+    nodata tag, geotransform / projection taken from ``meta`` (as returned by ``read_geotiff``).
+
+    ``encoder="host"`` (default) differences and encodes the strips on the host.  ``encoder="device"`` does both on the
+    GPU (msr_lzw_encode_strips) and writes the same file byte for byte: ``data`` is a NumPy array or a CUDA tensor (converted
+    to ``dtype`` on the device), ``device`` the HIP device (default: the tensor's, else the current one), and the raster
+    goes through the device in bands of whole strips of at most ``band_bytes`` raw bytes.  LZW only; no CPU fallback.
+    ``transfers``: encode_strips'."""
+    dt, comp, predictor = _checked_format(dtype, compress, predictor, encoder)
+    if data.ndim != 2:
+        raise ValueError("Data must be a 2-D array (the reference raises for rank != 2 too, process_full_tiles.py:505-519).")
+    rows, cols = data.shape
+    rps = _rows_per_strip(rows, cols * dt.itemsize)
+    strips = encode_strips(data, dt, rps, compress, predictor, encoder, device, band_bytes, transfers)
     _write_container(path, strips, rows, cols, dt, rps, comp, predictor, meta, nodata, bigtiff)
 
 

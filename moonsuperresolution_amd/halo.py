@@ -80,7 +80,16 @@ _CARRIED = ("sx", "sy", "mm_sel", "keys", "dmm")
 
 
 class HaloShardedSuperResolution(DEMSuperResolution):
-    """DEMSuperResolution with the halo mode added: ``processMapHalo(rank, world)``."""
+    """DEMSuperResolution with the halo mode added: ``processMapHalo(rank, world)``.
+
+    ``resident`` is accepted and must be False: the halo mode's bands, zones and slabs still end on the host."""
+
+    def __init__(self, *args, resident: bool = False, **kwargs) -> None:
+        if not isinstance(resident, bool):
+            raise ValueError(f"resident must be a bool, got {resident!r}")
+        if resident:
+            raise ValueError("resident=True is not built for the halo mode")
+        super().__init__(*args, **kwargs)
 
     def patchGrid(self) -> Tuple[list, list]:
         """Unique patch origins the reference's tiles touch (padded-canvas coordinates): (ys, xs), sorted."""

@@ -199,18 +199,30 @@ def _check_infill(infill: str) -> str:
     return infill
 
 
-def _lowres_rows(lib, handle, device, dem_window: np.ndarray, row0: int, shape: Tuple[int, int], plan, no_value: float,
-                 infill: str = "host") -> torch.Tensor:
+def _log(transfers, direction: str, nbytes: int, what: str) -> None:
+    """One host <-> device copy issued here, for the caller's list (DEMSuperResolution.transfers)."""
+    if transfers is not None:
+        transfers.append((direction, int(nbytes), what))
+
+
+def _lowres_rows(lib, handle, device, dem_window, row0: int, shape: Tuple[int, int], plan, no_value: float,
+                 infill: str = "host", transfers=None) -> torch.Tensor:
     """Rows plan["d16"] of the x1/16 grid (device tensor, no-data as NaN) from a row window of the input DEM that holds
     plan["dem"]: area on the d4 band, in-filling (host: of the plan's tiles; device: in place on the band, whose rows
-    plan["fill"] lie 32 rows from its cut edges and so take the whole grid's bits), area on the in-filled rows."""
+    plan["fill"] lie 32 rows from its cut edges and so take the whole grid's bits), area on the in-filled rows.
+    ``dem_window`` is a NumPy array (its rows plan["dem"] are uploaded) or a float32 CUDA tensor (they are read where they
+    lie); with ``infill="host"`` the x1/4 band goes to SciPy and comes back, either way."""
     H = int(shape[0])
     h4 = _cv_round(H / 4)
     (m0, m1), (q0, q1), (f0, f1) = plan["dem"], plan["d4"], plan["fill"]
     if m0 < row0 or m1 > row0 + dem_window.shape[0]:
         raise ValueError(f"the row window [{row0}, {row0 + dem_window.shape[0]}) lacks rows of [{m0}, {m1}), which the "
                          f"pre-processing of x1/16-grid rows {plan['d16']} reads")
-    d = torch.from_numpy(np.ascontiguousarray(dem_window[m0 - row0:m1 - row0], dtype=np.float32)).to(device)
+    if isinstance(dem_window, torch.Tensor):
+        d = dem_window[m0 - row0:m1 - row0].contiguous()      # whole rows of a contiguous raster: a view, no copy
+    else:
+        _log(transfers, "h2d", (m1 - m0) * dem_window.shape[1] * 4, "DEM rows for the x1/4 area step")
+        d = torch.from_numpy(np.ascontiguousarray(dem_window[m0 - row0:m1 - row0], dtype=np.float32)).to(device)
     d4 = _area_rows(lib, handle, d, m0, H, (q0, q1), no_value, RESIZE_NODATA_TO_NAN | RESIZE_NAN_TO_NODATA)
     del d
     if infill == "device":
@@ -218,68 +230,100 @@ def _lowres_rows(lib, handle, device, dem_window: np.ndarray, row0: int, shape: 
         infill_device(lib, handle, d4, q0, h4, no_value, FILL_AREA, FILL_BORDER)
         d4 = d4[f0 - q0:f1 - q0]
     else:
+        _log(transfers, "d2h", d4.numel() * 4, "x1/4 grid for the host in-fill")
         filled = _fill_rows(d4.cpu().numpy(), q0, h4, plan["tiles"], no_value)
+        _log(transfers, "h2d", (f1 - f0) * filled.shape[1] * 4, "in-filled x1/4 grid")
         d4 = torch.from_numpy(np.ascontiguousarray(filled[f0 - q0:f1 - q0])).to(device)
     return _area_rows(lib, handle, d4, f0, h4, plan["d16"], no_value, RESIZE_NODATA_TO_NAN)
 
 
 def _cubic_rows(lib, handle, d16: torch.Tensor, a16: int, h16: int, dst_rows: Tuple[int, int], dst_shape: Tuple[int, int],
-                no_value: float) -> np.ndarray:
+                no_value: float, as_tensor: bool = False, transfers=None):
     """Rows ``dst_rows`` of the INTER_CUBIC resize to ``dst_shape`` = (rows, cols) of an x1/16 grid of ``h16`` rows of which
-    ``d16`` holds the rows from ``a16``; NaN leaves as no_value.  Host float32."""
+    ``d16`` holds the rows from ``a16``; NaN leaves as no_value.  Host float32, or with ``as_tensor`` the device tensor."""
     dst = torch.empty((dst_rows[1] - dst_rows[0], dst_shape[1]), dtype=torch.float32, device=d16.device)
     rc = lib.msr_resize_cubic_rows(handle, d16.data_ptr(), a16, d16.shape[0], h16, d16.shape[1], dst.data_ptr(), dst_rows[0],
                                    dst.shape[0], dst_shape[0], dst_shape[1], no_value, RESIZE_NAN_TO_NODATA,
                                    torch.cuda.current_stream(d16.device).cuda_stream)
     _lib.raise_for(lib, handle, rc, "msr_resize_cubic_rows")
+    if as_tensor:
+        return dst
+    _log(transfers, "d2h", dst.numel() * 4, "synthesised DEM")
     return dst.cpu().numpy()
 
 
-def fill_ortho_device(lib, handle, device, img: np.ndarray, no_value: float, band_bytes: int = 1 << 28) -> np.ndarray:
+def fill_ortho_device(lib, handle, device, img, no_value: float, band_bytes: int = 1 << 28, transfers=None):
     """The device form of fillNan(img, no_value, 1024, 128, 8): msr_infill_small_holes with (max_area, margin) = (8, 128) on
     bands of whole rows of at most ``band_bytes``, so that device memory stays bounded.  Consecutive bands share
     margin + max_area = 136 rows; each gives the rows up to the middle of what it shares, which lie 68 >= max_area rows from
-    its cut edge and so hold the whole raster's bits.  Host float32."""
+    its cut edge and so hold the whole raster's bits.  Host float32 — or, for a float32 CUDA tensor, a tensor: every band is
+    a clone of its rows of ``img`` (which keeps its bits; a band filled in place would show the next one, in the rows they
+    share, holes the first had filled in part), and nothing leaves the device."""
     from .infill import infill_device
     H, W = img.shape
     share = ORTHO_BORDER + ORTHO_AREA
     per_band = min(H, int(band_bytes) // (4 * W))
     if per_band < H and per_band <= share:
         raise ValueError(f"band_bytes {band_bytes} holds {per_band} rows of {W} columns: bands need more than {share}")
-    out = np.empty_like(img)
+    on_device = isinstance(img, torch.Tensor)
+    out = torch.empty_like(img) if on_device and per_band < H else None if on_device else np.empty_like(img)
     top = 0
     while True:
         end = min(top + per_band, H)
-        band = torch.from_numpy(np.ascontiguousarray(img[top:end])).to(device)
+        if on_device:
+            band = img[top:end].clone()
+        else:
+            _log(transfers, "h2d", (end - top) * W * 4, "ortho band for the in-fill")
+            band = torch.from_numpy(np.ascontiguousarray(img[top:end])).to(device)
         infill_device(lib, handle, band, top, H, no_value, ORTHO_AREA, ORTHO_BORDER)
+        if out is None:                               # the whole raster in one band: the filled clone is the result
+            return band
         a = top + share // 2 if top else 0
         b = end - share // 2 if end < H else H
-        out[a:b] = band[a - top:b - top].cpu().numpy()
+        if on_device:
+            out[a:b] = band[a - top:b - top]
+        else:
+            _log(transfers, "d2h", (b - a) * W * 4, "in-filled ortho band")
+            out[a:b] = band[a - top:b - top].cpu().numpy()
         if end == H:
             return out
         top = end - share
 
 
-def preprocess_rows(lib, handle, device, dem_window: np.ndarray, row0: int, shape: Tuple[int, int],
-                    out_rows: Tuple[int, int], no_value: float, infill: str = "host") -> np.ndarray:
+def _raster(a):
+    """A raster argument as it is worked on: a float32 CUDA tensor stays one (contiguous), anything else is a float32 array."""
+    if isinstance(a, torch.Tensor):
+        if not a.is_cuda or a.dtype != torch.float32:
+            raise ValueError("a raster given as a tensor must be a CUDA float32 tensor")
+        return a.contiguous()
+    return np.asarray(a, np.float32)
+
+
+def preprocess_rows(lib, handle, device, dem_window, row0: int, shape: Tuple[int, int],
+                    out_rows: Tuple[int, int], no_value: float, infill: str = "host", transfers=None):
     """Rows ``out_rows`` of what ``preprocess(..., swap_dsize=False, infill=infill)[1]`` returns for the whole raster of
     ``shape``, bit for bit, from ``dem_window`` = its rows [row0, row0 + len(dem_window)), which must hold
     window_plan(shape, out_rows)["dem"] (ValueError otherwise).  Only the plan's d4, fill and d16 rows are computed.  Host
-    float32."""
+    float32 for an array; for a float32 CUDA tensor a tensor, with the same bits."""
     _check_infill(infill)
     H, W = int(shape[0]), int(shape[1])
-    dem_window = np.asarray(dem_window, np.float32)
+    dem_window = _raster(dem_window)
     if dem_window.ndim != 2 or dem_window.shape[1] != W:
         raise ValueError(f"the row window must be 2-D with the raster's {W} columns")
     plan = window_plan(shape, out_rows)
     with torch.cuda.device(device):
-        d16 = _lowres_rows(lib, handle, device, dem_window, int(row0), shape, plan, no_value, infill)
-        return _cubic_rows(lib, handle, d16, plan["d16"][0], _cv_round(_cv_round(H / 4) / 4), out_rows, (H, W), no_value)
+        d16 = _lowres_rows(lib, handle, device, dem_window, int(row0), shape, plan, no_value, infill, transfers)
+        return _cubic_rows(lib, handle, d16, plan["d16"][0], _cv_round(_cv_round(H / 4) / 4), out_rows, (H, W), no_value,
+                           isinstance(dem_window, torch.Tensor), transfers)
 
 
-def preprocess(lib, handle, device, img: np.ndarray, dem: np.ndarray, no_value: float,
-               swap_dsize: bool = True, infill: str = "host", band_bytes: int = 1 << 28) -> Tuple[np.ndarray, np.ndarray]:
-    """process_full_tiles.py:226-244.  Returns (filled ortho, low-resolution DEM at full size), both host float32.
+def preprocess(lib, handle, device, img, dem, no_value: float, swap_dsize: bool = True, infill: str = "host",
+               band_bytes: int = 1 << 28, transfers=None):
+    """process_full_tiles.py:226-244.  Returns (filled ortho, low-resolution DEM at full size), both host float32 — or,
+    each where the argument is a float32 CUDA tensor, a tensor with the same bits: with ``infill="device"`` nothing then
+    leaves the device; with ``infill="host"`` the ortho and the x1/4 grid, which SciPy reads, go down and their in-filled
+    forms come up.  ``transfers``: a list that takes ``(direction, bytes, what)`` for every copy between host and device
+    issued here (DEMSuperResolution.transfers).
 
     ``infill="host"`` (default) in-fills with SciPy's griddata like the reference; ``"device"`` fills the same pixels on the
     GPU with the values of infill.infill_reference (a stated deviation) and makes no SciPy call: the ortho in bands of at most
@@ -288,17 +332,22 @@ def preprocess(lib, handle, device, img: np.ndarray, dem: np.ndarray, no_value: 
     ``swap_dsize=True`` reproduces :241, where ``self.dem_shape`` = (rows, cols) is handed to ``cv2.resize`` as
     (width, height): the result then has shape (cols, rows), so — like the reference — only square rasters survive
     the later ``padInputs``.  ``swap_dsize=False`` resizes to (rows, cols) proper: preprocess_rows with the window [0, H)."""
-    img = np.asarray(img, np.float32)
-    dem = np.asarray(dem, np.float32)
+    img, dem = _raster(img), _raster(dem)
     if _check_infill(infill) == "device":
         with torch.cuda.device(device):
-            image = fill_ortho_device(lib, handle, device, img, no_value, band_bytes)
+            image = fill_ortho_device(lib, handle, device, img, no_value, band_bytes, transfers)
+    elif isinstance(img, torch.Tensor):
+        _log(transfers, "d2h", img.numel() * 4, "ortho for the host in-fill")
+        image = fillNan(img.cpu().numpy(), no_value, tile_size=1024, border=ORTHO_BORDER, max_fill_area=ORTHO_AREA)
+        _log(transfers, "h2d", image.size * 4, "in-filled ortho")
+        image = torch.from_numpy(image).to(img.device)
     else:
         image = fillNan(img, no_value, tile_size=1024, border=ORTHO_BORDER, max_fill_area=ORTHO_AREA)
     H, W = dem.shape
     if not swap_dsize:
-        return image, preprocess_rows(lib, handle, device, dem, 0, (H, W), (0, H), no_value, infill)
+        return image, preprocess_rows(lib, handle, device, dem, 0, (H, W), (0, H), no_value, infill, transfers)
     h16 = _cv_round(_cv_round(H / 4) / 4)
     with torch.cuda.device(device):      # every row of the x1/16 grid, then the cubic to W rows of H columns
-        d16 = _lowres_rows(lib, handle, device, dem, 0, (H, W), _plan_from_d16((H, W), 0, h16), no_value, infill)
-        return image, _cubic_rows(lib, handle, d16, 0, h16, (0, W), (W, H), no_value)
+        d16 = _lowres_rows(lib, handle, device, dem, 0, (H, W), _plan_from_d16((H, W), 0, h16), no_value, infill, transfers)
+        return image, _cubic_rows(lib, handle, d16, 0, h16, (0, W), (W, H), no_value, isinstance(dem, torch.Tensor),
+                                  transfers)

@@ -88,11 +88,27 @@ class DEMSuperResolution:
             grid.  "host" is the reference's griddata surface, tile by tile (SciPy).  "device" fills THE SAME PIXELS with
             other values (infill.py: a local thin-plate fill, defined by infill.infill_reference, which the kernel equals bit
             for bit); the x1/4 grid then stays on the GPU between the two area steps and no SciPy call is made.
+        resident: False (default) or True — where the rasters are HELD between the stages, never which arithmetic runs.  With
+            True, ``img`` / ``dem`` / ``image`` and the products of processMap / rebuildMap / processTiles are CUDA tensors
+            (float32; ``good`` uint8) where they are NumPy arrays otherwise, the canvases are built with device-to-device
+            copies, tiles are pasted into device maps and saveGTiff takes the tensors; a stage chosen to run on the host
+            (decoder / infill / encoder = "host", a model that is no Generator) keeps its own round trip.  The files written
+            are the same byte for byte.
+
+    ``transfers`` is a diagnostic: a list of ``(direction, bytes, what)``, direction "h2d" or "d2h", to which the driver,
+    preprocess.py and geotiff.py append every raster-scale copy they issue themselves (and the per-block bookkeeping of the
+    device codecs); processFiles empties it when it starts.  ``products_path`` is "rank0" or "gathered" after a sharded
+    processFiles: which of the two product writers ran.
     """
 
     def __init__(self, config: DSRConfig, model: Callable = lambda x, training=False: x, device: int = 0,
                  as_implemented: bool = True, pipeline: int = 2, range_check: str = "off", encoder: str = "host",
-                 decoder: str = "host", infill: str = "host") -> None:
+                 decoder: str = "host", infill: str = "host", resident: bool = False) -> None:
+        if not isinstance(resident, bool):
+            raise ValueError(f"resident must be a bool, got {resident!r}")
+        self.resident = resident                     # where the rasters are held between the stages: HBM, or host memory
+        self.transfers: List[Tuple[str, int, str]] = []
+        self.products_path = None
         if encoder not in ("host", "device"):
             raise ValueError(f"encoder must be 'host' or 'device', got {encoder!r}")
         self.encoder = encoder                       # saveGTiff: who differences and LZW-encodes the strips (geotiff.py)
@@ -168,6 +184,25 @@ class DEMSuperResolution:
         self.canvas_row0 = 0                         # first canvas row of dem_padded / img_padded (padInputs)
 
     # ------------------------------------------------------------------------------------------------
+    def _log(self, direction: str, nbytes: int, what: str) -> None:
+        """One copy this class issues itself, for ``transfers``."""
+        self.transfers.append((direction, int(nbytes), what))
+
+    def _held(self, a, what: str):
+        """A raster as this instance holds it: a float32 CUDA tensor on ``device`` (resident) or a float32 array."""
+        if isinstance(a, torch.Tensor):
+            if not a.is_cuda or a.dtype != torch.float32:
+                raise ValueError("A raster given as a tensor must be a CUDA float32 tensor.")
+            if self.resident:
+                return a.to(self.device)
+            self._log("d2h", a.numel() * 4, f"{what} raster")
+            return a.cpu().numpy()
+        a = np.asarray(a, np.float32)
+        if not self.resident:
+            return a
+        self._log("h2d", a.size * 4, f"{what} raster")
+        return torch.from_numpy(np.ascontiguousarray(a)).to(self.device)
+
     def setImages(self, img: np.ndarray, dem: np.ndarray, row0: int = 0,
                   full_shape: Optional[Tuple[int, int]] = None) -> None:
         """Stand-in for loadImages + preprocess (process_full_tiles.py:158-244): takes the arrays directly.
@@ -175,17 +210,19 @@ class DEMSuperResolution:
         With ``row0`` / ``full_shape`` the arrays are a ROW WINDOW: raster rows [row0, row0 + img.shape[0]) of a raster
         of ``full_shape`` (what a rank of a sharded run needs: distributed.input_rows).  ``dem_shape`` / ``img_shape``
         stay the full shape, so the tile list, the canvas geometry and the stitched map do not change; only padInputs
-        allocates less, and a tile whose patches leave the window is an error (processTile)."""
-        img = np.asarray(img, np.float32)
-        dem = np.asarray(dem, np.float32)
-        if img.shape != dem.shape or img.ndim != 2:
+        allocates less, and a tile whose patches leave the window is an error (processTile).
+
+        Arrays or CUDA float32 tensors.  They are held where ``resident`` says: with True an array is uploaded (once) and a
+        tensor kept as it is; with False a tensor is downloaded and an array kept."""
+        img, dem = (a if isinstance(a, torch.Tensor) else np.asarray(a, np.float32) for a in (img, dem))
+        if tuple(img.shape) != tuple(dem.shape) or img.ndim != 2:
             raise ValueError("The ortho-image and the DEM must be 2-D arrays of the same shape.")
         full = tuple(int(v) for v in (dem.shape if full_shape is None else full_shape))
         row0 = int(row0)
         if len(full) != 2 or full[1] != dem.shape[1] or row0 < 0 or row0 + dem.shape[0] > full[0]:
             raise ValueError(f"rows [{row0}, {row0 + dem.shape[0]}) x {dem.shape[1]} columns are not a row window of a "
                              f"raster of shape {full}")
-        self.img, self.dem = img, dem
+        self.img, self.dem = self._held(img, "ortho"), self._held(dem, "DEM")
         self.row0 = row0
         self.dem_shape = full
         self.img_shape = full
@@ -199,7 +236,8 @@ class DEMSuperResolution:
         """process_full_tiles.py:158-182 without GDAL: band 1 of ``<source_folder_path>/<ortho_image_name>`` and
         ``<dem_name>`` as float32 (geotiff.read_geotiff), georeferencing of the DEM kept for saveGTiff.
         ``rows=(r0, r1)`` reads only those raster rows of both files (only the strips / tiles that hold them are decoded)
-        and sets them as a row window (setImages).
+        and sets them as a row window (setImages).  ``resident``: the device decoder's tensors are kept as they are; arrays
+        decoded on the host are uploaded once.
 
         Raises ValueError if a path does not exist (same messages as the reference)."""
         from . import geotiff
@@ -209,8 +247,11 @@ class DEMSuperResolution:
             raise ValueError("The path given for the ortho-image does not exist. Provided path is: " + img_path)
         if not os.path.exists(dem_path):
             raise ValueError("The path given for the dem does not exist. Provided path is: " + dem_path)
-        img, img_meta = geotiff.read_geotiff(img_path, band=1, rows=rows, decoder=self.decoder, device=self.device)
-        dem, self.geo_meta = geotiff.read_geotiff(dem_path, band=1, rows=rows, decoder=self.decoder, device=self.device)
+        # resident: the device decoder's tensor is kept (a host-decoded array is uploaded by setImages, once)
+        how = dict(band=1, rows=rows, decoder=self.decoder, device=self.device, as_tensor=self.resident,
+                   transfers=self.transfers)
+        img, img_meta = geotiff.read_geotiff(img_path, **how)
+        dem, self.geo_meta = geotiff.read_geotiff(dem_path, **how)
         self.geo_transform = geotiff.geotransform(self.geo_meta)
         if rows is None:
             self.setImages(img, dem)
@@ -223,13 +264,24 @@ class DEMSuperResolution:
         """process_full_tiles.py:481-531 without GDAL: ``<save_path>/<map_name>_<name>.tiff``, LZW + PREDICTOR=2,
         the input DEM's georeferencing, nodata = no_value; uint8 data is stored as UInt16 like the reference does.
 
+        ``data`` may be a CUDA tensor (``data_type`` its torch or the NumPy dtype): with ``encoder="device"`` it is converted
+        and encoded where it lies, band by band (uint8 becomes uint16 on the device); with ``encoder="host"`` it is
+        downloaded once.
+
         Raises ValueError for unsupported data types and for data that is not 2-dimensional."""
         from . import geotiff
+        on_device = isinstance(data, torch.Tensor)
+        if on_device:
+            data_type = {torch.float32: np.float32, torch.uint8: np.uint8, torch.int16: np.uint16}.get(data_type, data_type)
+            if self.encoder == "host":
+                self._log("d2h", data.numel() * data.element_size(), f"{name} product")
+                data, on_device = data.cpu().numpy(), False
         if data_type == np.float32:
             out_type = np.float32
         elif data_type == np.uint8 or data_type == np.uint16:
             out_type = np.uint16
-            data = data.astype(np.uint16)
+            if not on_device:                          # a tensor is widened band by band (geotiff._band_bytes_on_device)
+                data = data.astype(np.uint16)
         else:
             raise ValueError("Unsupported data-type.")
         if len(data.shape) < 2:
@@ -241,7 +293,7 @@ class DEMSuperResolution:
         os.makedirs(self.save_path, exist_ok=True)
         geotiff.write_geotiff(os.path.join(self.save_path, self.map_name + "_" + name + ".tiff"), data,
                               getattr(self, "geo_meta", None), nodata=self.no_value, dtype=out_type, compress="lzw",
-                              predictor=2, encoder=self.encoder, device=self.device)
+                              predictor=2, encoder=self.encoder, device=self.device, transfers=self.transfers)
 
     def preprocess(self, swap_dsize: bool = True, rows: Optional[Tuple[int, int]] = None) -> None:
         """process_full_tiles.py:226-244: in-fill the ortho (stored in ``self.image`` and, as in the reference, never
@@ -272,7 +324,7 @@ class DEMSuperResolution:
             raise ValueError(f"preprocess works on whole rasters: rows [{self.row0}, {self.row0 + self.dem.shape[0]}) of "
                              f"{self.dem_shape[0]} are set as a row window")
         self.image, self.dem = pp.preprocess(self._lib, self._h, self.device, self.img, self.dem, self.no_value,
-                                             swap_dsize=swap_dsize, infill=self.infill)
+                                             swap_dsize=swap_dsize, infill=self.infill, transfers=self.transfers)
 
     def _preprocess_rows(self, pp, swap_dsize: bool, rows: Tuple[int, int]) -> None:
         H, W = self.dem_shape
@@ -289,13 +341,14 @@ class DEMSuperResolution:
             raise ValueError(f"preprocess(rows=({r0}, {r1})) reads raster rows [{need[0]}, {need[1]}); the row window "
                              f"[{have[0]}, {have[1]}) held lacks rows {' and '.join(missing)}")
         dem = pp.preprocess_rows(self._lib, self._h, self.device, self.dem, self.row0, self.dem_shape, rows, self.no_value,
-                                 infill=self.infill)
-        img = np.ascontiguousarray(self.img[r0 - self.row0:r1 - self.row0])
+                                 infill=self.infill, transfers=self.transfers)
+        img = self.img[r0 - self.row0:r1 - self.row0]
+        img = img.clone() if isinstance(img, torch.Tensor) else np.ascontiguousarray(img)   # the wider band is released
         self.setImages(img, dem, row0=r0, full_shape=self.dem_shape)
         self.image = None
 
     def processFiles(self, preprocess: bool = True, rank: int = 0, world: int = 1, mode: Optional[str] = None,
-                     gather: bool = True, swap_dsize: bool = True, **sharded) -> None:
+                     gather: bool = True, swap_dsize: bool = True, products: str = "gathered", **sharded) -> None:
         """processMap of the reference on files (process_full_tiles.py:568-587): loadImages -> preprocess ->
         padInputs -> tiles -> rebuildMap -> ``<map>_mean.tiff``, ``<map>_std.tiff``, ``<map>_good.tiff``.
         ``preprocess=False`` skips the low-resolution-DEM synthesis (feed an already pre-processed DEM); ``swap_dsize`` is
@@ -308,10 +361,27 @@ class DEMSuperResolution:
         runs its tile rows (distributed.process_map_sharded) and, with ``gather`` (needs an initialised process group),
         all-gathers the finished rows; without it the rows of other ranks stay zero in the files written.
         ``mode="halo"`` is accepted by HaloShardedSuperResolution.processFiles only; further keywords (``batching``,
-        ``accumulate``: halo.py) go to the sharded mode that takes them."""
+        ``accumulate``: halo.py) go to the sharded mode that takes them.
+
+        ``products="rank0"`` (``mode="tiles"``; needs an initialised process group when world > 1; ``gather`` is not looked
+        at): no all-gather of the products.  Every rank encodes the strips of the product rows it computed, with the
+        ``encoder`` set; the encoded strips are gathered to rank 0, which alone writes the three files — byte for byte those
+        of a one-process run.  That needs every rank boundary to be a strip boundary of the float32 and of the uint16
+        products (distributed.strip_plan): always so once a row exceeds 32 KiB.  Otherwise the run takes the gathered path,
+        and only rank 0 writes.  ``products_path`` says which of the two ran.  The default, "gathered", is the all-gather
+        after which every rank writes the files."""
+        if products not in ("gathered", "rank0"):
+            raise ValueError(f"products must be 'gathered' or 'rank0', got {products!r}")
+        del self.transfers[:]
+        self.products_path = None
         if mode is not None:
+            if products == "rank0":
+                return self._process_files_rank0(preprocess, rank, world, mode, swap_dsize, **sharded)
+            self.products_path = "gathered"
             mean, std, good = self._process_files_sharded(preprocess, rank, world, mode, gather, swap_dsize, **sharded)
         else:
+            if products != "gathered":
+                sharded = dict(sharded, products=products)
             if sharded:
                 raise TypeError(f"processFiles: {sorted(sharded)} need a sharded mode")
             self.loadImages()
@@ -358,7 +428,58 @@ class DEMSuperResolution:
         self._load_rank_rows(preprocess, rank, world, mode, swap_dsize)
         self.padInputs()
         return process_map_sharded(self.dem_shape, self.tile_size, self.generateTileList(), self.processTile, rank, world,
-                                   gather=gather, device=self.device)
+                                   gather=gather, device=self.device, as_tensor=self.resident, transfers=self.transfers)
+
+    def _process_files_rank0(self, preprocess: bool, rank: int, world: int, mode: str, swap_dsize: bool = True,
+                             **sharded) -> None:
+        """processFiles(products="rank0"): see there.  The rank's rows never leave its device before they are encoded
+        (``encoder="host"``: they are downloaded once, by saveGTiff's rule)."""
+        from . import geotiff
+        from .distributed import process_map_sharded, strip_plan
+        if mode != "tiles":
+            raise ValueError(f"products='rank0' is built for mode='tiles', got mode={mode!r}")
+        if sharded:
+            raise TypeError(f"processFiles: mode='tiles' takes no {sorted(sharded)}")
+        if world > 1:
+            import torch.distributed as dist
+            if not (dist.is_available() and dist.is_initialized()):
+                raise RuntimeError("products='rank0' needs an initialised process group")
+        self._load_rank_rows(preprocess, rank, world, mode, swap_dsize)
+        shape, T = self.dem_shape, self.tile_size
+        plans = {name: strip_plan(shape, np.dtype(dt).itemsize, T, world)
+                 for name, dt in (("mean", np.float32), ("std", np.float32), ("good", np.uint16))}
+        local = world > 1 and not any(p["straddles"] for p in plans.values())
+        self.products_path = "rank0" if local or world == 1 else "gathered"
+        self.padInputs()
+        tiles = self.generateTileList()
+        if not local:
+            # a strip straddles a rank boundary (a small raster): the gathered rows, written by rank 0 alone
+            mean, std, good = process_map_sharded(shape, T, tiles, self.processTile, rank, world, gather=True,
+                                                  device=self.device, as_tensor=self.resident, transfers=self.transfers)
+            if rank == 0:
+                for name, data in (("mean", mean), ("std", std), ("good", good)):
+                    self.saveGTiff(data, data.dtype, name)
+            return
+        mine = process_map_sharded(shape, T, tiles, self.processTile, rank, world, device=self.device, as_tensor=True,
+                                   local=True)
+        for name, data in zip(("mean", "std", "good"), mine):
+            plan = plans[name]
+            dt = np.dtype(np.uint16 if name == "good" else np.float32)
+            r0, r1 = plan["rows"][rank]
+            assert tuple(data.shape) == (r1 - r0, shape[1]), (tuple(data.shape), (r0, r1), shape)
+            if self.encoder == "host" and data.numel():
+                self._log("d2h", data.numel() * data.element_size(), f"{name} product rows")
+                data = data.cpu().numpy()
+            strips = geotiff.encode_strips(data, dt, plan["rps"], encoder=self.encoder, device=self.device,
+                                           transfers=self.transfers) if r1 > r0 else []
+            gathered = [None] * world if rank == 0 else None
+            dist.gather_object(strips, gathered, dst=0)
+            if rank == 0:
+                strips = [s for part in gathered for s in part]
+                assert len(strips) == plan["n_strips"], (len(strips), plan["n_strips"])
+                os.makedirs(self.save_path, exist_ok=True)
+                geotiff.write_strips(os.path.join(self.save_path, self.map_name + "_" + name + ".tiff"), strips, shape, dt,
+                                     plan["rps"], getattr(self, "geo_meta", None), nodata=self.no_value)
 
     def padInputs(self) -> None:
         """process_full_tiles.py:246-267: no_value canvas ((dim//1024)+1)*1024 + 2(S-s), data at offset (S-s).
@@ -379,8 +500,14 @@ class DEMSuperResolution:
             self.dem_padded = torch.full((c1 - c0, new_x), self.no_value, dtype=torch.float32, device=self.device)
             self.img_padded = torch.full((c1 - c0, new_x), self.no_value, dtype=torch.float32, device=self.device)
             y = self.row0 + (S - s) - c0                           # the first raster row given, in window rows
-            self.dem_padded[y:y + n, S - s:S - s + w] = torch.from_numpy(self.dem).to(self.device)
-            self.img_padded[y:y + n, S - s:S - s + w] = torch.from_numpy(self.img).to(self.device)
+            if isinstance(self.dem, torch.Tensor):                 # resident: device to device, on the current stream
+                self.dem_padded[y:y + n, S - s:S - s + w] = self.dem
+                self.img_padded[y:y + n, S - s:S - s + w] = self.img
+            else:
+                self._log("h2d", self.dem.size * 4, "DEM into its canvas")
+                self.dem_padded[y:y + n, S - s:S - s + w] = torch.from_numpy(self.dem).to(self.device)
+                self._log("h2d", self.img.size * 4, "ortho into its canvas")
+                self.img_padded[y:y + n, S - s:S - s + w] = torch.from_numpy(self.img).to(self.device)
             torch.cuda.current_stream(self.device).synchronize()   # the tile loop reads the canvases on other streams
         self.canvas_row0 = c0
         self.dem_window_shape = self.img_window_shape = tuple(self.dem_padded.shape)
@@ -585,7 +712,10 @@ class DEMSuperResolution:
                                              sx[c * B:].data_ptr(), sy[c * B:].data_ptr(), mm_sel[c * B:].data_ptr(),
                                              B, batch.data_ptr(), self._stream())
                 _lib.raise_for(lib, h, rc, "msr_extract_patches")
+                # a host callable is a stage on the host: its round trip is its own, resident or not
+                self._log("d2h", batch.numel() * 4, "batch for the host model")
                 out = np.array(self.model(batch.cpu().numpy(), training=False))[:, :, :, -1]
+                self._log("h2d", out.size * 4, "predictions of the host model")
                 preds[c * B:(c + 1) * B] = torch.from_numpy(np.ascontiguousarray(out, dtype=np.float32)).to(dev)
             return self.rebuildTile(preds, st["keys"], st["dmm"], nv)
 
@@ -682,7 +812,12 @@ class DEMSuperResolution:
     def processTiles(self, tiles: Sequence[Tuple[int, int]]):
         """Process a list of tiles (this rank's shard); returns {(xx,yy): (mean, std, good)} of host arrays.
         Results come back through pinned buffers with asynchronous copies retired two tiles late, so the device-to-host
-        transfer of tile t never stalls the launches of tile t+1."""
+        transfer of tile t never stalls the launches of tile t+1.
+
+        ``resident``: the values are the device tensors themselves (no download); they are written on the current stream,
+        after the generator streams (_generate_tile), so work queued on it later sees them whole."""
+        if self.resident:
+            return dict(self.iterTiles(tiles))
         out = {}
         pending = []
 
@@ -696,6 +831,7 @@ class DEMSuperResolution:
                 bufs = [torch.empty(t.shape, dtype=t.dtype, pin_memory=True) for t in (m, s, g)]
                 for b, t in zip(bufs, (m, s, g)):
                     b.copy_(t, non_blocking=True)
+                    self._log("d2h", t.numel() * t.element_size(), f"tile {key} product")
                 ev = torch.cuda.Event()
                 ev.record(torch.cuda.current_stream(self.device))
             pending.append((key, ev, bufs, (m, s, g)))
@@ -706,7 +842,13 @@ class DEMSuperResolution:
         return out
 
     def rebuildMap(self, tiles: dict):
-        """process_full_tiles.py:533-566 without file I/O: paste tiles, crop to the input extent."""
+        """process_full_tiles.py:533-566 without file I/O: paste tiles, crop to the input extent.  Device tensors in,
+        device tensors out (``resident``: processTiles gives them)."""
+        if self.resident or any(isinstance(m, torch.Tensor) for m, _, _ in tiles.values()):
+            maps = self._device_maps()
+            for key, parts in tiles.items():
+                self._paste(maps, key, parts)
+            return maps
         hp, wp = self.dem_padded_shape
         T = self.tile_size
         mean = np.zeros((hp, wp), np.float32)
@@ -724,7 +866,38 @@ class DEMSuperResolution:
         if img is not None:
             self.setImages(img, dem)
         self.padInputs()
-        return self.rebuildMap(self.processTiles(self.generateTileList()))
+        return self.mapTiles(self.generateTileList())
+
+    def mapTiles(self, tiles: Sequence[Tuple[int, int]]):
+        """processTiles + rebuildMap for the canvases padInputs built.  ``resident``: every tile is pasted into the device
+        maps as iterTiles yields it, so one tile's products are alive at a time, not the whole list's."""
+        if not self.resident:
+            return self.rebuildMap(self.processTiles(tiles))
+        maps = self._device_maps()
+        for key, parts in self.iterTiles(tiles):
+            self._paste(maps, key, parts)
+        return maps
+
+    def _device_maps(self):
+        """Zeroed (mean, std, good) of ``dem_shape`` on the device: what rebuildMap's crop of the padded canvas keeps."""
+        h, w = self.dem_shape
+        with torch.cuda.device(self.device):
+            return (torch.zeros((h, w), dtype=torch.float32, device=self.device),
+                    torch.zeros((h, w), dtype=torch.float32, device=self.device),
+                    torch.zeros((h, w), dtype=torch.uint8, device=self.device))
+
+    def _paste(self, maps, key: Tuple[int, int], parts) -> None:
+        """One tile into the device maps, clipped to them, on the current stream: the stream rebuildTile wrote the tile on
+        (and on which its tensors were allocated), so no event and no record_stream is needed and the tile loop's pipeline
+        is as deep as ever."""
+        xx, yy = key
+        h, w = maps[0].shape
+        th, tw = min(self.tile_size, h - yy), min(self.tile_size, w - xx)
+        if th <= 0 or tw <= 0:
+            return
+        with torch.cuda.device(self.device):
+            for full, t in zip(maps, parts):
+                full[yy:yy + th, xx:xx + tw] = t[:th, :tw]
 
     def close(self) -> None:
         for g in (getattr(self, "_gens", None) or [])[1:]:

@@ -91,7 +91,12 @@ def main():
     ap.add_argument("--head", default="separate", choices=("separate", "fused"),
                     help="fused: the last residual conv emits the head's partial sums (Generator(head=...), opt-in)")
     ap.add_argument("--pipeline", type=int, default=2)
+    ap.add_argument("--resident", action="store_true",
+                    help="DEMSuperResolution(resident=True): the rasters are uploaded once and cropped / padded on the device "
+                         "(tile mode only)")
     args = ap.parse_args()
+    if args.resident and args.halo:
+        ap.error("--resident is not built for the halo mode")
     if args.crop_inputs and not (args.halo or args.gpus > 1 or int(os.environ.get("WORLD_SIZE", "1")) > 1):
         ap.error("--crop-inputs needs a sharded run: --halo or --gpus N")
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
@@ -129,7 +134,7 @@ def main():
     img, dem = synthetic_raster(args.rows, args.cols, seed=0)
     gen = Generator(S, B, variant="gaugan", weights=1234, eps=7, device=local, precision=args.precision, head=args.head)
     dsr = DEMSuperResolution(DSRConfig(image_size=S, stride=s, batch_size=B, tile_size=T), model=gen, device=local,
-                             pipeline=args.pipeline)
+                             pipeline=args.pipeline, resident=args.resident)
     dsr.setImages(img, dem)
     del img, dem
     shard_rank, shard_world = rank, world
