@@ -437,6 +437,25 @@ int msr_tiff_blocks_to_f32(msr_handle* h, const uint8_t* src_dev, const int64_t*
  * tail [result, cap); -1 for a null pointer, a negative argument or one above INT32_MAX. */
 int64_t msr_lzw_decode_strip_host(const uint8_t* in, int64_t n_in, uint8_t* out, int64_t cap);
 
+/* One reduced-resolution level (a TIFF overview) of a raster in DEVICE memory, one launch (csrc/tiff_overview.hip, the rule in
+ * csrc/tiff_overview.h; geotiff.py write_geotiff(tile=, overviews=, encoder="device"), twin: geotiff.overview_reference).
+ * src_dev is [rows, cols] samples of sample_kind 'f' (sample_bytes 4: float32) or 'u' (sample_bytes 1 or 2), dst_dev
+ * [ceil(rows / 2), ceil(cols / 2)] of the same type.  dst[i][j] comes from src[2i : 2i + 2][2j : 2j + 2] clipped to the raster.
+ *   float32  a pixel counts iff v != no_value (a NaN counts and propagates; has_nodata = 0: every pixel counts).  No counting
+ *            pixel: no_value.  Otherwise s / (float)n, s the float32 sum of the n counting values in row-major order started
+ *            from the first of them, not from 0 (-0.0 alone stays -0.0): one rounding per addition and one for the division.
+ *   uint     the maximum of the block.
+ * One thread per destination pixel, 64-bit offsets, no LDS.  src is not modified; src and dst must not overlap.  h may be NULL.
+ * MSR_ERR_INVALID before any launch, with a message that names the argument: a null pointer, rows or cols <= 0, more than
+ * 2^31 - 1 source pixels, an unknown kind or width, has_nodata other than 0 / 1 or set with an integer kind.  Asynchronous on
+ * `stream`; no allocation. */
+int msr_overview_half(msr_handle* h, const void* src_dev, int32_t rows, int32_t cols, int32_t sample_kind, int32_t sample_bytes,
+                      int32_t has_nodata, float no_value, void* dst_dev, void* stream);
+/* HOST code: the same rule (the same function of csrc/tiff_overview.h) looped over host buffers, so that it can be checked
+ * against the twin without a GPU.  0, or -1 for an argument msr_overview_half rejects. */
+int msr_overview_half_host(const void* src, int32_t rows, int32_t cols, int32_t sample_kind, int32_t sample_bytes,
+                           int32_t has_nodata, float no_value, void* dst);
+
 /* ---- measurement ----------------------------------------------------------------------------- */
 typedef struct {
     char name[48];        /* kernel family, e.g. "conv_igemm_f32" */

@@ -90,6 +90,8 @@ SYMBOLS = [
     ("msr_tiff_blocks_to_f32", C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                          _P, C.c_int32, C.c_int32, C.c_int32, _P]),
     ("msr_lzw_decode_strip_host", C.c_int64, [_P, C.c_int64, _P, C.c_int64]),
+    ("msr_overview_half", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P, _P]),
+    ("msr_overview_half_host", C.c_int, [_P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, _P]),
     ("msr_infill_workspace_bytes", C.c_int64, [C.c_int32, C.c_int32]),
     ("msr_infill_small_holes", C.c_int, [_P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_float, C.c_int32, C.c_int32, _P,
                                          C.c_int64, _P]),

@@ -19,6 +19,9 @@ and ``_good.tiff`` (UInt16) as LZW GeoTIFFs with ``PREDICTOR=2`` and a nodata ta
   (ModelPixelScale 33550, ModelTiepoint 33922, ModelTransformation 34264, GeoKeyDirectory 34735, GeoDoubleParams
   34736, GeoAsciiParams 34737, GDAL_METADATA 42112) — the output keeps the input's geotransform and projection
   byte for byte, which is what ``saveGTiff`` does with ``SetGeoTransform`` / ``SetProjection``.
+  Opt-in: ``tile=(tile_h, tile_w)`` writes tiles instead of strips and ``overviews=n`` adds n reduced-resolution levels as
+  chained IFDs (GDAL's internal-overview layout), each the 2 x 2 reduction ``overview_reference`` of the one before; with
+  ``encoder="device"`` the levels are reduced (csrc/tiff_overview.hip) and the tiles encoded on the GPU, same bytes out.
 
 The LZW codec lives in libmoonsr_hip.so's host code (csrc/host_codecs.cpp).  GDAL is absent here, so the codec and
 container are validated against an independent implementation instead: PIL/libtiff reads what this module writes
@@ -111,8 +114,31 @@ def _values(entry, bo: str):
     return vals
 
 
-def _open(path: str):
-    """Header and first IFD of a (Geo)TIFF: (memory map, tag dict, byte order, meta).  No pixel block is touched."""
+def _next_ifd(buf, big: bool, bo: str, off: int) -> int:
+    """The next-IFD pointer of the IFD at ``off`` (0: the chain ends)."""
+    if big:
+        n = struct.unpack_from(bo + "Q", buf, off)[0]
+        return struct.unpack_from(bo + "Q", buf, off + 8 + 20 * n)[0]
+    n = struct.unpack_from(bo + "H", buf, off)[0]
+    return struct.unpack_from(bo + "I", buf, off + 2 + 12 * n)[0]
+
+
+def _overview_ifds(buf, big: bool, bo: str, first: int) -> list:
+    """The tag dicts of the reduced-resolution levels: the IFDs chained behind the first one whose NewSubfileType (254)
+    has bit 0 set, in file order.  A chain that loops or leaves the file ends where it does."""
+    out, seen, off = [], {first}, _next_ifd(buf, big, bo, first)
+    while off and off not in seen and off + 8 <= buf.size:
+        seen.add(off)
+        t = _read_ifd(buf, big, bo, off)
+        if 254 in t and _values(t[254], bo)[0] & 1:
+            out.append(t)
+        off = _next_ifd(buf, big, bo, off)
+    return out
+
+
+def _open(path: str, overview: int = 0):
+    """Header and first IFD of a (Geo)TIFF: (memory map, tag dict, byte order, meta).  No pixel block is touched.
+    ``overview=k > 0``: the IFD of the k-th reduced-resolution level instead (read_geotiff)."""
     buf = np.memmap(path, dtype=np.uint8, mode="r")
     head = bytes(buf[:16])
     if head[:2] == b"II":
@@ -129,6 +155,11 @@ def _open(path: str):
     else:
         raise ValueError(f"{path}: not a TIFF file (magic {magic})")
     t = _read_ifd(buf, big, bo, ifd)
+    if overview:
+        levels = _overview_ifds(buf, big, bo, ifd)
+        if overview > len(levels):
+            raise ValueError(f"{path}: overview {overview} does not exist: the file has {len(levels)} reduced level(s)")
+        t = levels[overview - 1]
 
     def val(tag, default=None):
         return _values(t[tag], bo) if tag in t else default
@@ -148,6 +179,8 @@ def _open(path: str):
             nodata = None
     meta = {"geo": {k: t[k] for k in GEO_TAGS if k in t}, "nodata": nodata, "dtype": dt.newbyteorder("="),
             "shape": (rows, cols), "byteorder": bo, "window": (0, rows)}
+    if overview:
+        meta["overview"] = overview
     return buf, t, bo, meta
 
 
@@ -157,8 +190,24 @@ def read_info(path: str) -> dict:
     return _open(path)[3]
 
 
+def overview_shapes(path: str) -> list:
+    """``[(rows, cols), ...]`` of the reduced-resolution levels of a file (write_geotiff(overviews=)), level 1 first, from
+    the IFDs alone; ``[]`` for a file without any.  ``read_geotiff(overview=k)`` reads level k."""
+    buf = np.memmap(path, dtype=np.uint8, mode="r")
+    head = bytes(buf[:16])
+    if head[:2] not in (b"II", b"MM"):
+        raise ValueError(f"{path}: not a TIFF file")
+    bo = "<" if head[:2] == b"II" else ">"
+    magic = struct.unpack_from(bo + "H", head, 2)[0]
+    if magic not in (42, 43):
+        raise ValueError(f"{path}: not a TIFF file (magic {magic})")
+    big = magic == 43
+    first = struct.unpack_from(bo + ("Q" if big else "I"), head, 8 if big else 4)[0]
+    return [(_values(t[257], bo)[0], _values(t[256], bo)[0]) for t in _overview_ifds(buf, big, bo, first)]
+
+
 def read_geotiff(path: str, band: int = 1, rows: Optional[Tuple[int, int]] = None, decoder: str = "host", device=None,
-                 band_bytes: int = 256 << 20, as_tensor: bool = False, transfers: Optional[list] = None):
+                 band_bytes: int = 256 << 20, as_tensor: bool = False, transfers: Optional[list] = None, overview: int = 0):
     """Band ``band`` (1-based, like GDAL's GetRasterBand) of a (Geo)TIFF as float32, plus its metadata:
     ``{"geo": {tag: (type, count, raw bytes)}, "nodata": float | None, "dtype": numpy dtype of the file,
     "shape": (rows, cols), "byteorder": "<" | ">", "window": (r0, r1)}``.  Counterpart of loadImages
@@ -178,10 +227,17 @@ def read_geotiff(path: str, band: int = 1, rows: Optional[Tuple[int, int]] = Non
     blocks go through ``device`` (default: the current one) in bands of whole block rows of at most ``band_bytes``
     decoded bytes (plan_read_bands).  ``as_tensor=True`` returns the CUDA float32 tensor instead of a NumPy array.
     ``transfers``: a list that takes ``(direction, bytes, what)`` for every copy between host and device this read issues
-    (DEMSuperResolution.transfers): the compressed blocks and their bookkeeping going up, the raster coming down."""
+    (DEMSuperResolution.transfers): the compressed blocks and their bookkeeping going up, the raster coming down.
+
+    ``overview=k > 0`` reads the k-th reduced-resolution level instead (the k-th IFD of the chain whose NewSubfileType has
+    bit 0 set: write_geotiff(overviews=), GDAL's internal overviews), with either decoder and the same keywords: ``rows``
+    and ``meta["shape"]`` are that level's, ``meta["geo"]`` is that IFD's (empty in files written here) and
+    ``meta["overview"] = k`` is added.  ValueError for a level the file does not have (overview_shapes lists them)."""
     if decoder not in ("host", "device"):
         raise ValueError(f"decoder must be 'host' or 'device', got {decoder!r}")
-    buf, t, bo, meta = _open(path)
+    if isinstance(overview, bool) or not isinstance(overview, (int, np.integer)) or overview < 0:
+        raise ValueError(f"overview must be an integer >= 0, got {overview!r}")
+    buf, t, bo, meta = _open(path, int(overview))
 
     def val(tag, default=None):
         return _values(t[tag], bo) if tag in t else default
@@ -589,12 +645,173 @@ def write_strips(path: str, strips: list, shape: Tuple[int, int], dtype, rps: in
     rows, cols = int(shape[0]), int(shape[1])
     if len(strips) != -(-rows // rps):
         raise ValueError(f"{len(strips)} strips for {rows} rows of {rps} a strip")
-    _write_container(path, strips, rows, cols, dt, rps, comp, predictor, meta, nodata, bigtiff)
+    _write_container(path, [(rows, cols, strips)], dt, rps, None, comp, predictor, meta, nodata, bigtiff)
+
+
+# ---- tiles and overviews --------------------------------------------------------------------------------------------
+OVERVIEW_DTYPES = ("<f4", "|u1", "<u2")
+
+
+def overview_reference(a: np.ndarray, nodata: Optional[float] = None) -> np.ndarray:
+    """The next reduced-resolution level of the 2-D raster ``a`` (float32, uint8 or uint16): the NumPy twin that DEFINES
+    what write_geotiff(overviews=) stores and whose bits csrc/tiff_overview.h (the kernel of msr_overview_half and
+    msr_overview_half_host) reproduces.  The result is ceil(rows / 2) x ceil(cols / 2) of ``a``'s dtype; ``dst[i, j]`` comes
+    from ``a[2i : 2i + 2, 2j : 2j + 2]`` clipped to the raster.
+
+    float32: a pixel counts iff ``v != float32(nodata)`` (a NaN counts and propagates; ``nodata=None``: every pixel
+    counts).  No counting pixel gives ``nodata``; otherwise ``s / float32(n)`` with ``s`` the float32 sum of the n counting
+    values in row-major order, started from the first of them and not from 0, so that -0.0 alone stays -0.0: one rounding
+    per addition, one for the division.  uint8 / uint16: the maximum of the block (``nodata`` is not looked at), so the
+    overview of a ``good`` mask is 1 exactly where the overview of its ``mean`` is not nodata."""
+    a = np.asarray(a)
+    if a.ndim != 2 or a.dtype.newbyteorder("<").str not in OVERVIEW_DTYPES or 0 in a.shape:
+        raise ValueError(f"overview_reference takes a non-empty 2-D float32, uint8 or uint16 array, got {a.dtype} {a.shape}")
+    rows, cols = a.shape
+    dr, dc = -(-rows // 2), -(-cols // 2)
+    pad = np.zeros((2 * dr, 2 * dc), a.dtype)
+    pad[:rows, :cols] = a
+    inside = np.zeros((2 * dr, 2 * dc), bool)
+    inside[:rows, :cols] = True
+    quads = [(pad[y::2, x::2], inside[y::2, x::2]) for y, x in ((0, 0), (0, 1), (1, 0), (1, 1))]     # row-major
+    if a.dtype.kind == "u":
+        out = quads[0][0].copy()
+        for v, _ in quads[1:]:
+            out = np.maximum(out, v)              # outside the raster: 0, the smallest unsigned value
+        return out
+    nv = None if nodata is None else np.float32(nodata)
+    s = np.zeros((dr, dc), np.float32)
+    n = np.zeros((dr, dc), np.int32)
+    with np.errstate(all="ignore"):
+        for v, ins in quads:
+            counts = ins if nv is None else ins & (v != nv)
+            s = np.where(counts, np.where(n > 0, s + v, v), s).astype(np.float32)
+            n += counts
+        mean = s / np.maximum(n, 1).astype(np.float32)
+    return mean if nv is None else np.where(n > 0, mean, nv).astype(np.float32)
+
+
+def check_layout(tile, overviews, shape: Optional[Tuple[int, int]] = None, dt: Optional[np.dtype] = None):
+    """write_geotiff's ``tile`` and ``overviews`` checked: ``(tile as a pair of ints or None, overviews)``, or the ValueError
+    that names the keyword.  What depends on the raster (the largest ``overviews``, the dtype) is checked where ``shape`` /
+    ``dt`` are given."""
+    if tile is not None:
+        ok = isinstance(tile, (tuple, list)) and len(tile) == 2 and all(
+            isinstance(v, (int, np.integer)) and not isinstance(v, bool) and v > 0 and v % 16 == 0 for v in tile)
+        if not ok:
+            raise ValueError(f"tile must be None or (tile_h, tile_w), both positive multiples of 16 (TIFF 6.0), got {tile!r}")
+        tile = (int(tile[0]), int(tile[1]))
+    if isinstance(overviews, bool) or not isinstance(overviews, (int, np.integer)) or overviews < 0:
+        raise ValueError(f"overviews must be an integer >= 0, got {overviews!r}")
+    overviews = int(overviews)
+    if overviews and tile is None:
+        raise ValueError(f"overviews={overviews} needs tile=(tile_h, tile_w): reduced levels are written in tiles")
+    if overviews and shape is not None:
+        most = (max(int(shape[0]), int(shape[1])) - 1).bit_length()          # ceil(log2(max(rows, cols)))
+        if overviews > most:
+            raise ValueError(f"overviews={overviews} is more than the {most} level(s) a {shape[0]} x {shape[1]} raster has")
+    if overviews and dt is not None and np.dtype(dt).newbyteorder("<").str not in OVERVIEW_DTYPES:
+        raise ValueError(f"overviews are built for float32, uint8 and uint16 files, got dtype {np.dtype(dt)}")
+    return tile, overviews
+
+
+def _encode_block(raw: np.ndarray, comp: int) -> bytes:
+    return raw.tobytes() if comp == 1 else lzw_encode(raw) if comp == 5 else zlib.compress(raw.tobytes(), 6)
+
+
+def _host_tiles(arr: np.ndarray, dt: np.dtype, th: int, tw: int, comp: int, predictor: int) -> list:
+    """The tiles of ``arr`` in row-major order encoded on the host: an edge tile is padded with zero bytes, then the
+    predictor differences every tile row, then msr_lzw_encode / zlib / nothing."""
+    rows, cols = arr.shape
+    tiles = []
+    for ty in range(-(-rows // th)):
+        for tx in range(-(-cols // tw)):
+            t = np.zeros((th, tw), dt)
+            blk = arr[ty * th:(ty + 1) * th, tx * tw:(tx + 1) * tw]
+            t[:blk.shape[0], :blk.shape[1]] = blk
+            if predictor == 2:
+                u = t.view(np.dtype(f"<u{dt.itemsize}"))
+                d = u.copy()
+                d[:, 1:] = u[:, 1:] - u[:, :-1]
+                t = d
+            tiles.append(_encode_block(np.ascontiguousarray(t), comp))
+    return tiles
+
+
+def _host_levels(arr: np.ndarray, dt: np.dtype, tile: Tuple[int, int], overviews: int, nodata: Optional[float], comp: int,
+                 predictor: int) -> list:
+    """``[(rows, cols, tiles), ...]`` of the raster and its ``overviews`` reduced levels (overview_reference)."""
+    levels = []
+    for k in range(overviews + 1):
+        if k:
+            arr = overview_reference(arr, nodata if dt.kind == "f" else None)
+        levels.append((arr.shape[0], arr.shape[1], _host_tiles(arr, dt, tile[0], tile[1], comp, predictor)))
+    return levels
+
+
+def _device_levels(data, dt: np.dtype, tile: Tuple[int, int], overviews: int, nodata: Optional[float], predictor: int, device,
+                   band_bytes: int, transfers: Optional[list] = None) -> list:
+    """_host_levels on the device, with the same bytes.  Every level goes through in bands of whole tile rows of at most
+    ``band_bytes`` raw bytes (one tile row where that is larger): the band's bytes (_band_bytes_on_device for level 0; a
+    view for the others), msr_overview_half of the band into its rows of the next level (a band starts on a multiple of
+    tile_h, an even row, so those rows depend on this band alone), the tile-major arrangement with torch copies (pad, then
+    one permuted copy), one msr_lzw_encode_strips launch with row_bytes = tile_w * sample_bytes, compaction and download.
+    Device memory is about 2.5 x band_bytes plus the next level (a quarter of the one being encoded, so at most a third of
+    the raster with the level after it)."""
+    import torch
+    lib = _lib.load()
+    dev = _torch_device(device)
+    th, tw = tile
+    sb = dt.itemsize
+    bits = getattr(torch, _TORCH_BITS[sb])           # the container of a sample's bits: they are only copied here
+    has_nodata = int(dt.kind == "f" and nodata is not None)
+    levels = []
+    cur = data
+    with torch.cuda.device(dev):
+        s = torch.cuda.current_stream(dev)
+        for k in range(overviews + 1):
+            rows, cols = int(cur.shape[0]), int(cur.shape[1])
+            across, down = -(-cols // tw), -(-rows // th)
+            nxt = torch.empty((-(-rows // 2), -(-cols // 2)), dtype=bits, device=dev) if k < overviews else None
+            per_band = max(1, int(band_bytes) // (th * across * tw * sb))
+            blocks = []
+            for t0 in range(0, down, per_band):
+                t1 = min(t0 + per_band, down)
+                r0, r1 = t0 * th, min(t1 * th, rows)
+                if k == 0:
+                    band = _band_bytes_on_device(cur, r0, r1, dt, dev).view(bits).reshape(r1 - r0, cols)
+                else:
+                    band = cur[r0:r1]
+                if nxt is not None:
+                    rc = lib.msr_overview_half(None, band.data_ptr(), r1 - r0, cols, ord(dt.kind), sb, has_nodata,
+                                               float(nodata) if has_nodata else 0.0, nxt[r0 // 2:].data_ptr(),
+                                               C.c_void_p(s.cuda_stream))
+                    _lib.raise_for(lib, None, rc, "msr_overview_half")
+                nt = t1 - t0
+                if (r1 - r0, cols) != (nt * th, across * tw):
+                    padded = torch.zeros((nt * th, across * tw), dtype=bits, device=dev)
+                    padded[:r1 - r0, :cols] = band
+                    band = padded
+                tiles = band.view(nt, th, across, tw).permute(0, 2, 1, 3).contiguous().view(torch.uint8).reshape(-1)
+                n = nt * across
+                enc = lzw_encode_device(tiles, np.arange(n, dtype=np.int64) * (th * tw * sb), np.full(n, th * tw * sb, np.int64),
+                                        sb if predictor == 2 else 0, tw * sb)
+                if transfers is not None:
+                    if k == 0 and isinstance(data, np.ndarray):
+                        transfers.append(("h2d", (r1 - r0) * cols * sb, "raw product band"))
+                    # per tile: offset and slot (2 x int64), length and capacity (2 x int32) going up, the stream's length down
+                    transfers.append(("h2d", 24 * n, "tile tables of the encoder"))
+                    transfers.append(("d2h", 4 * n, "encoded tile lengths"))
+                    transfers.append(("d2h", sum(len(b) for b in enc), "compressed output tiles"))
+                blocks += enc
+            levels.append((rows, cols, blocks))
+            cur = nxt
+    return levels
 
 
 def write_geotiff(path: str, data: np.ndarray, meta: Optional[dict] = None, nodata: Optional[float] = None,
                   dtype=np.float32, compress: str = "lzw", predictor: int = 2, bigtiff: Optional[bool] = None,
-                  encoder: str = "host", device=None, band_bytes: int = 256 << 20, transfers: Optional[list] = None) -> None:
+                  encoder: str = "host", device=None, band_bytes: int = 256 << 20, transfers: Optional[list] = None, *,
+                  tile: Optional[Tuple[int, int]] = None, overviews: int = 0) -> None:
     """Write a single-band GeoTIFF the way saveGTiff does (process_full_tiles.py:481-531): LZW, PREDICTOR=2,
     nodata tag, geotransform / projection taken from ``meta`` (as returned by ``read_geotiff``).
 
@@ -602,82 +819,127 @@ def write_geotiff(path: str, data: np.ndarray, meta: Optional[dict] = None, noda
     GPU (msr_lzw_encode_strips) and writes the same file byte for byte: ``data`` is a NumPy array or a CUDA tensor (converted
     to ``dtype`` on the device), ``device`` the HIP device (default: the tensor's, else the current one), and the raster
     goes through the device in bands of whole strips of at most ``band_bytes`` raw bytes.  LZW only; no CPU fallback.
-    ``transfers``: encode_strips'."""
+    ``transfers``: encode_strips'.
+
+    ``tile=(tile_h, tile_w)`` (positive multiples of 16) writes tiles in row-major order instead of strips: TileWidth /
+    TileLength / TileOffsets / TileByteCounts and no strip tag; an edge tile is padded with zero bytes before the predictor,
+    which restarts on every tile row; everything else as without it.  ``overviews=n > 0`` (needs ``tile``; at most
+    ceil(log2(max(rows, cols))); float32, uint8 or uint16 files) adds n reduced-resolution levels, level k the
+    ``overview_reference`` of level k - 1 with this ``nodata``: each an IFD of its own chained behind the main one, with
+    NewSubfileType = 1, the nodata tag, the main IFD's tile size, compression, predictor and sample format, and no geo tags.
+    File order: header, the tiles of level 0, 1 ... n, then the IFDs in order, each followed by its out-of-line values — GDAL's
+    convention for internal overviews.  Both encoders write the same bytes; on the device the levels are reduced there too
+    (msr_overview_half; _device_levels).  ``read_geotiff(overview=k)`` reads level k.  With the defaults, None and 0, the file
+    is the one written before these keywords existed."""
     dt, comp, predictor = _checked_format(dtype, compress, predictor, encoder)
     if data.ndim != 2:
         raise ValueError("Data must be a 2-D array (the reference raises for rank != 2 too, process_full_tiles.py:505-519).")
     rows, cols = data.shape
-    rps = _rows_per_strip(rows, cols * dt.itemsize)
-    strips = encode_strips(data, dt, rps, compress, predictor, encoder, device, band_bytes, transfers)
-    _write_container(path, strips, rows, cols, dt, rps, comp, predictor, meta, nodata, bigtiff)
+    tile, overviews = check_layout(tile, overviews, (rows, cols), dt)
+    if tile is None:
+        rps = _rows_per_strip(rows, cols * dt.itemsize)
+        strips = encode_strips(data, dt, rps, compress, predictor, encoder, device, band_bytes, transfers)
+        levels = [(rows, cols, strips)]
+    elif encoder == "device":
+        rps = None
+        if device is None and not isinstance(data, np.ndarray) and getattr(data, "is_cuda", False):
+            device = data.device
+        levels = _device_levels(data, dt, tile, overviews, nodata, predictor, device, band_bytes, transfers)
+    else:
+        rps = None
+        levels = _host_levels(np.ascontiguousarray(data, dtype=dt), dt, tile, overviews, nodata, comp, predictor)
+    _write_container(path, levels, dt, rps, tile, comp, predictor, meta, nodata, bigtiff)
 
 
-def _write_container(path: str, strips: list, rows: int, cols: int, dt: np.dtype, rps: int, comp: int, predictor: int,
-                     meta: Optional[dict], nodata: Optional[float], bigtiff: Optional[bool]) -> None:
-    """The TIFF around the encoded strips: header, strips, IFD (strip offsets and byte counts, geo tags, nodata), classic
-    or BigTIFF by size."""
-    n_strips = len(strips)
-    total = sum(len(s) for s in strips)
+def _write_container(path: str, levels: list, dt: np.dtype, rps: Optional[int], tile: Optional[Tuple[int, int]], comp: int,
+                     predictor: int, meta: Optional[dict], nodata: Optional[float], bigtiff: Optional[bool]) -> None:
+    """The TIFF around the encoded blocks of ``levels`` = [(rows, cols, blocks), ...], the raster first and then its reduced
+    levels: header, the blocks level after level, then one IFD per level, each followed by its out-of-line values and chained
+    to the next; classic or BigTIFF by size.  The blocks are strips of ``rps`` rows (``tile`` None; one level) or tiles of
+    ``tile`` = (tile_h, tile_w) in row-major order.  The first IFD carries the geo tags; the others NewSubfileType = 1; all
+    of them the nodata tag."""
+    n_blocks = sum(len(blocks) for _, _, blocks in levels)
+    total = sum(len(b) for _, _, blocks in levels for b in blocks)
     geo = dict((meta or {}).get("geo", {}))
-    big = total + 8 * n_strips * 2 + sum(len(v[2]) for v in geo.values()) + 4096 > 0xFFFF0000
+    big = total + 8 * n_blocks * 2 + sum(len(v[2]) for v in geo.values()) + 4096 * len(levels) > 0xFFFF0000
     if bigtiff is not None:
         big = bool(bigtiff)
     off_t = "Q" if big else "I"
-    entries = {
-        256: (4, 1, struct.pack("<I", cols)), 257: (4, 1, struct.pack("<I", rows)),
-        258: (3, 1, struct.pack("<H", dt.itemsize * 8)), 259: (3, 1, struct.pack("<H", comp)),
-        262: (3, 1, struct.pack("<H", 1)), 277: (3, 1, struct.pack("<H", 1)),
-        278: (4, 1, struct.pack("<I", rps)), 284: (3, 1, struct.pack("<H", 1)),
-        339: (3, 1, struct.pack("<H", {"u": 1, "i": 2, "f": 3}[dt.kind])),
-    }
-    if predictor != 1:
-        entries[317] = (3, 1, struct.pack("<H", predictor))
-    for k, v in geo.items():
-        typ, cnt, raw = v
-        if (meta or {}).get("byteorder", "<") == ">" and _TYPE_SIZE.get(typ, 1) > 1:
-            w = _TYPE_SIZE[typ] if typ not in (5, 10) else 4
-            raw = np.frombuffer(raw, np.dtype(f">u{w}")).astype(np.dtype(f"<u{w}")).tobytes()
-        entries[k] = (typ, cnt, raw)
-    if nodata is not None:
-        txt = (repr(float(nodata)) if float(nodata) != int(nodata) else str(int(nodata))).encode() + b"\0"
-        entries[GDAL_NODATA] = (2, len(txt), txt)
-    header = 16 if big else 8
-    pos = header
-    offsets = []
-    for s in strips:
-        offsets.append(pos)
-        pos += len(s) + (len(s) & 1)
-    entries[273] = (16 if big else 4, n_strips, struct.pack("<" + off_t * n_strips, *offsets))
-    entries[279] = (16 if big else 4, n_strips, struct.pack("<" + off_t * n_strips, *(len(s) for s in strips)))
-    tags = sorted(entries)
-    ifd_off = pos
     esz, vsz = (20, 8) if big else (12, 4)
-    ifd_size = (8 if big else 2) + len(tags) * esz + (8 if big else 4)
-    extra_off = ifd_off + ifd_size
-    ifd = bytearray(struct.pack("<Q" if big else "<H", len(tags)))
-    extra = bytearray()
-    for k in tags:
-        typ, cnt, raw = entries[k]
-        ifd += struct.pack("<HH", k, typ) + struct.pack("<" + off_t, cnt)
-        if len(raw) <= vsz:
-            ifd += raw.ljust(vsz, b"\0")
+    pos = 16 if big else 8
+    ifds = []
+    for k, (rows, cols, blocks) in enumerate(levels):
+        entries = {
+            256: (4, 1, struct.pack("<I", cols)), 257: (4, 1, struct.pack("<I", rows)),
+            258: (3, 1, struct.pack("<H", dt.itemsize * 8)), 259: (3, 1, struct.pack("<H", comp)),
+            262: (3, 1, struct.pack("<H", 1)), 277: (3, 1, struct.pack("<H", 1)),
+            284: (3, 1, struct.pack("<H", 1)),
+            339: (3, 1, struct.pack("<H", {"u": 1, "i": 2, "f": 3}[dt.kind])),
+        }
+        if k:
+            entries[254] = (4, 1, struct.pack("<I", 1))          # NewSubfileType: a reduced-resolution version
+        if predictor != 1:
+            entries[317] = (3, 1, struct.pack("<H", predictor))
+        for tag, v in (geo.items() if k == 0 else ()):
+            typ, cnt, raw = v
+            if (meta or {}).get("byteorder", "<") == ">" and _TYPE_SIZE.get(typ, 1) > 1:
+                w = _TYPE_SIZE[typ] if typ not in (5, 10) else 4
+                raw = np.frombuffer(raw, np.dtype(f">u{w}")).astype(np.dtype(f"<u{w}")).tobytes()
+            entries[tag] = (typ, cnt, raw)
+        if nodata is not None:
+            txt = (repr(float(nodata)) if float(nodata) != int(nodata) else str(int(nodata))).encode() + b"\0"
+            entries[GDAL_NODATA] = (2, len(txt), txt)
+        offsets = []
+        for b in blocks:
+            offsets.append(pos)
+            pos += len(b) + (len(b) & 1)
+        n = len(blocks)
+        if tile is None:
+            entries[278] = (4, 1, struct.pack("<I", rps))
+            tag_off, tag_cnt = 273, 279
         else:
-            if len(extra) & 1:
-                extra += b"\0"
-            ifd += struct.pack("<" + off_t, extra_off + len(extra))
-            extra += raw
-    ifd += struct.pack("<" + off_t, 0)
+            entries[322] = (4, 1, struct.pack("<I", tile[1]))
+            entries[323] = (4, 1, struct.pack("<I", tile[0]))
+            tag_off, tag_cnt = 324, 325
+        entries[tag_off] = (16 if big else 4, n, struct.pack("<" + off_t * n, *offsets))
+        entries[tag_cnt] = (16 if big else 4, n, struct.pack("<" + off_t * n, *(len(b) for b in blocks)))
+        ifds.append(entries)
+    first_ifd = pos
+    tail = bytearray()
+    for k, entries in enumerate(ifds):
+        tags = sorted(entries)
+        ifd_off = pos
+        ifd_size = (8 if big else 2) + len(tags) * esz + (8 if big else 4)
+        extra_off = ifd_off + ifd_size
+        ifd = bytearray(struct.pack("<Q" if big else "<H", len(tags)))
+        extra = bytearray()
+        for tag in tags:
+            typ, cnt, raw = entries[tag]
+            ifd += struct.pack("<HH", tag, typ) + struct.pack("<" + off_t, cnt)
+            if len(raw) <= vsz:
+                ifd += raw.ljust(vsz, b"\0")
+            else:
+                if len(extra) & 1:
+                    extra += b"\0"
+                ifd += struct.pack("<" + off_t, extra_off + len(extra))
+                extra += raw
+        last = k == len(ifds) - 1
+        if not last and len(extra) & 1:
+            extra += b"\0"                                       # the next IFD starts on a word boundary
+        pos = extra_off + len(extra)
+        ifd += struct.pack("<" + off_t, 0 if last else pos)
+        tail += ifd + extra
     with open(path, "wb") as f:
         if big:
-            f.write(b"II" + struct.pack("<HHHQ", 43, 8, 0, ifd_off))
+            f.write(b"II" + struct.pack("<HHHQ", 43, 8, 0, first_ifd))
         else:
-            f.write(b"II" + struct.pack("<HI", 42, ifd_off))
-        for s in strips:
-            f.write(s)
-            if len(s) & 1:
-                f.write(b"\0")
-        f.write(bytes(ifd))
-        f.write(bytes(extra))
+            f.write(b"II" + struct.pack("<HI", 42, first_ifd))
+        for _, _, blocks in levels:
+            for b in blocks:
+                f.write(b)
+                if len(b) & 1:
+                    f.write(b"\0")
+        f.write(bytes(tail))
 
 
 def geotransform(meta: dict) -> Optional[Tuple[float, float, float, float, float, float]]:

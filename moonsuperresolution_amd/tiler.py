@@ -94,6 +94,11 @@ class DEMSuperResolution:
             copies, tiles are pasted into device maps and saveGTiff takes the tensors; a stage chosen to run on the host
             (decoder / infill / encoder = "host", a model that is no Generator) keeps its own round trip.  The files written
             are the same byte for byte.
+        product_tile, overviews: None and 0 (default: strips, as ever), or what saveGTiff hands to geotiff.write_geotiff as
+            ``tile`` and ``overviews``: products in tiles of (tile_h, tile_w), positive multiples of 16, with that many
+            reduced-resolution levels (``overviews`` > 0 needs ``product_tile``); with ``encoder="device"`` the levels are
+            reduced and the tiles encoded on the GPU.  The rank-local writer (processFiles(products="rank0")) knows strips
+            only and refuses ``product_tile``.
 
     ``transfers`` is a diagnostic: a list of ``(direction, bytes, what)``, direction "h2d" or "d2h", to which the driver,
     preprocess.py and geotiff.py append every raster-scale copy they issue themselves (and the per-block bookkeeping of the
@@ -103,7 +108,10 @@ class DEMSuperResolution:
 
     def __init__(self, config: DSRConfig, model: Callable = lambda x, training=False: x, device: int = 0,
                  as_implemented: bool = True, pipeline: int = 2, range_check: str = "off", encoder: str = "host",
-                 decoder: str = "host", infill: str = "host", resident: bool = False) -> None:
+                 decoder: str = "host", infill: str = "host", resident: bool = False,
+                 product_tile: Optional[Tuple[int, int]] = None, overviews: int = 0) -> None:
+        from . import geotiff
+        self.product_tile, self.overviews = geotiff.check_layout(product_tile, overviews)   # saveGTiff: the products' layout
         if not isinstance(resident, bool):
             raise ValueError(f"resident must be a bool, got {resident!r}")
         self.resident = resident                     # where the rasters are held between the stages: HBM, or host memory
@@ -293,7 +301,8 @@ class DEMSuperResolution:
         os.makedirs(self.save_path, exist_ok=True)
         geotiff.write_geotiff(os.path.join(self.save_path, self.map_name + "_" + name + ".tiff"), data,
                               getattr(self, "geo_meta", None), nodata=self.no_value, dtype=out_type, compress="lzw",
-                              predictor=2, encoder=self.encoder, device=self.device, transfers=self.transfers)
+                              predictor=2, encoder=self.encoder, device=self.device, transfers=self.transfers,
+                              tile=self.product_tile, overviews=self.overviews)
 
     def preprocess(self, swap_dsize: bool = True, rows: Optional[Tuple[int, int]] = None) -> None:
         """process_full_tiles.py:226-244: in-fill the ortho (stored in ``self.image`` and, as in the reference, never
@@ -372,6 +381,9 @@ class DEMSuperResolution:
         after which every rank writes the files."""
         if products not in ("gathered", "rank0"):
             raise ValueError(f"products must be 'gathered' or 'rank0', got {products!r}")
+        if products == "rank0" and self.product_tile is not None:
+            raise ValueError(f"products='rank0' writes strips only: product_tile={self.product_tile!r} needs "
+                             "products='gathered'")
         del self.transfers[:]
         self.products_path = None
         if mode is not None:
