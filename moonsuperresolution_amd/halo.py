@@ -23,6 +23,8 @@ with the default ``batching="band"`` every band is compacted and batched on its 
 the batch mates of a patch — and through SPADE's batch moments its output — follow the band cut.  What stays resident is the rank's
 accumulator slab (3 float32 images of the canvas rows its patches reach: 2.1 GB for a 1/8 share of the 15000 x 70000 raster)
 plus one band; round 2 kept all predictions of the rank (34 GB at that size).
+A band's compaction and its calls (extract, generate) are the tile mode's helpers (tiler._compact_patches, _generator_calls,
+_host_model_calls); this module owns the bands, the carry between them, the accumulation and the zones.
 Exchange: the two boundary-zone slabs go to the neighbours as non-blocking send / recv while the interior rows (reached by this
 rank's patches only) are finalised; the zones are finalised when the neighbours' slabs have arrived.
 
@@ -47,7 +49,7 @@ import torch
 
 from . import _lib
 from .distributed import halo_zone_rows, patch_grid_1d
-from .tiler import DEMSuperResolution
+from .tiler import _CARRIED, DEMSuperResolution
 
 
 def batch_schedule(valid_per_band: Sequence[int], batch_size: int) -> List[Tuple[int, int]]:
@@ -74,9 +76,6 @@ def flush_padding(valid_per_band: Sequence[int], batch_size: int) -> List[Tuple[
     issued = batch_size * sum(c for c, _ in sched)
     carry = sched[-1][1] if sched else 0
     return [(issued + slot, 0xFFFFFFFE, 0xFFFFFFFF) for slot in range(carry, batch_size)] if carry else []
-
-
-_CARRIED = ("sx", "sy", "mm_sel", "keys", "dmm")
 
 
 class HaloShardedSuperResolution(DEMSuperResolution):
@@ -107,53 +106,26 @@ class HaloShardedSuperResolution(DEMSuperResolution):
     # ------------------------------------------------------------------------------------------------------------
     def _generate_rows(self, ys: Sequence[int], xs: Sequence[int], carry: Optional[dict] = None, last: bool = True):
         """Validity, normalisation statistics, device-side batch assembly and the generator calls for every patch at
-        rows `ys`: returns (preds [ncall * B, S, S], keys [cap, 2] canvas origins, dmm [cap, 2], patches to stitch).
+        rows `ys` (the tile mode's helpers, on the caller's stream, the pipeline streams forked from and joined to it): returns
+        (preds [ncall * B, S, S], keys [cap, 2] canvas origins, dmm [cap, 2], patches to stitch).
         The kernels that read the canvas get window rows (origin - canvas_row0, tiler.padInputs); the keys stay canvas
-        origins (msr_compact_patches subtracts tile_y = -canvas_row0).
+        origins (the compaction subtracts tile_y = -canvas_row0).
         ``carry`` (batching="rank"): the rank's state {"n": patches carried, "issued": patches of the calls made so far, and
         the carried rows of the five compaction outputs}.  They stand in front of this band's patches; only whole calls are
         issued, unless ``last``, and the rest is left in ``carry``.  The patches to stitch are the live rows of the calls
         issued (with carry=None: the band's valid patches, as ever)."""
         S, B = self.image_size, self.batch_size
-        lib, h, dev = self._lib, self._h, self.device
-        c0, rows, cols = self._window()
+        dev = self.device
+        c0 = self._window()[0]
         self._check_rows(f"patch rows {ys[0]} .. {ys[-1]}", ys)
         with torch.cuda.device(dev):
             cur = torch.cuda.current_stream(dev)
-            stream = cur.cuda_stream
             xt = torch.tensor(xs, dtype=torch.int32, device=dev)
             yt = torch.tensor([y - c0 for y in ys], dtype=torch.int32, device=dev)
-            ox = xt.repeat(len(ys))
-            oy = yt.repeat_interleave(len(xs))
-            n = int(ox.numel())
-            carry_n = 0 if carry is None else carry["n"]
-            cap = max(B, (carry_n + n + B - 1) // B * B)
-            valid = torch.empty(n, dtype=torch.uint8, device=dev)
-            minmax = torch.empty((n, 4), dtype=torch.float32, device=dev)
-            sx = torch.empty(cap, dtype=torch.int32, device=dev)
-            sy = torch.empty(cap, dtype=torch.int32, device=dev)
-            mm_sel = torch.empty((cap, 4), dtype=torch.float32, device=dev)
-            keys = torch.empty((cap, 2), dtype=torch.int32, device=dev)
-            dmm = torch.empty((cap, 2), dtype=torch.float32, device=dev)
-            meta = torch.empty(2, dtype=torch.int32, device=dev)
-            rc = lib.msr_patch_stats(h, self.img_padded.data_ptr(), self.dem_padded.data_ptr(), rows, cols, ox.data_ptr(),
-                                     oy.data_ptr(), n, self.no_value, valid.data_ptr(), minmax.data_ptr(), stream)
-            _lib.raise_for(lib, h, rc, "msr_patch_stats")
-            if carry is None:
-                rc = lib.msr_compact_patches(h, valid.data_ptr(), ox.data_ptr(), oy.data_ptr(), minmax.data_ptr(), n, 0, -c0,
-                                             B, cap, sx.data_ptr(), sy.data_ptr(), mm_sel.data_ptr(), keys.data_ptr(),
-                                             dmm.data_ptr(), meta.data_ptr(), stream)
-                _lib.raise_for(lib, h, rc, "msr_compact_patches")
-            else:
-                out = dict(zip(_CARRIED, (sx, sy, mm_sel, keys, dmm)))
-                for name in _CARRIED if carry_n else ():
-                    out[name][:carry_n].copy_(carry[name])          # the earlier band's tail, device to device
-                rc = lib.msr_compact_patches_carry(h, valid.data_ptr(), ox.data_ptr(), oy.data_ptr(), minmax.data_ptr(), n, 0,
-                                                   -c0, B, cap, carry_n, sx.data_ptr(), sy.data_ptr(), mm_sel.data_ptr(),
-                                                   keys.data_ptr(), dmm.data_ptr(), meta.data_ptr(), stream)
-                _lib.raise_for(lib, h, rc, "msr_compact_patches_carry")
-            tot, ncall = (int(v) for v in meta.cpu().tolist())
-            nv = tot - carry_n                            # this band's own valid patches
+            st = self._compact_patches(xt.repeat(len(ys)), yt.repeat_interleave(len(xs)), 0, -c0, carry)
+            cap, keys, dmm = st["cap"], st["keys"], st["dmm"]
+            tot, ncall = (int(v) for v in st["meta"].cpu().tolist())
+            nv = tot - (0 if carry is None else carry["n"])   # this band's own valid patches
             seq0 = 0                                      # index, in the sequence the calls are cut from, of slot 0
             if carry is not None:
                 seq0 = carry["issued"]
@@ -164,8 +136,7 @@ class HaloShardedSuperResolution(DEMSuperResolution):
             preds = torch.empty((max(ncall * B, 1), S, S), dtype=torch.float32, device=dev)
             self.last_noise_ids = None                # [cap, 3] of the band just issued, with the counter sampler
             if self._gen is not None:
-                if self._gens is None:
-                    self._make_pipeline()
+                self._ready_pipeline()
                 batches = [torch.empty((B, S, S, 2), dtype=torch.float32, device=dev) for _ in self._gens]
                 ids = None
                 if self.counter_noise:
@@ -180,33 +151,16 @@ class HaloShardedSuperResolution(DEMSuperResolution):
                 self.last_noise_ids = ids
                 for ps in self._pstreams:
                     ps.wait_stream(cur)
-                for c in range(ncall):
-                    k = c % len(self._gens)
-                    with torch.cuda.stream(self._pstreams[k]):
-                        rc = lib.msr_extract_patches(h, self.img_padded.data_ptr(), self.dem_padded.data_ptr(), rows, cols,
-                                                     sx[c * B:].data_ptr(), sy[c * B:].data_ptr(),
-                                                     mm_sel[c * B:].data_ptr(), B, batches[k].data_ptr(), self._stream())
-                        _lib.raise_for(lib, h, rc, "msr_extract_patches")
-                        self._gens[k].forward_device(batches[k], out=preds[c * B:(c + 1) * B].unsqueeze(-1),
-                                                     noise_ids=None if ids is None else ids[c * B:(c + 1) * B])
-                        if c == 0:
-                            self._range_enqueue(self._gens[k])
+                self._generator_calls(st, ncall, preds, batches, ids)
                 for ps in self._pstreams:
                     cur.wait_stream(ps)
-                    for t in batches + [preds, sx, sy, mm_sel] + ([] if ids is None else [ids]):
+                    for t in batches + [preds, st["sx"], st["sy"], st["mm_sel"]] + ([] if ids is None else [ids]):
                         t.record_stream(ps)
             else:
-                batch = torch.empty((B, S, S, 2), dtype=torch.float32, device=dev)
-                for c in range(ncall):
-                    rc = lib.msr_extract_patches(h, self.img_padded.data_ptr(), self.dem_padded.data_ptr(), rows, cols,
-                                                 sx[c * B:].data_ptr(), sy[c * B:].data_ptr(), mm_sel[c * B:].data_ptr(), B,
-                                                 batch.data_ptr(), stream)
-                    _lib.raise_for(lib, h, rc, "msr_extract_patches")
-                    out = np.array(self.model(batch.cpu().numpy(), training=False))[:, :, :, -1]
-                    preds[c * B:(c + 1) * B] = torch.from_numpy(np.ascontiguousarray(out, dtype=np.float32)).to(dev)
+                self._host_model_calls(st, ncall, preds)
             if carry is not None:
-                for name, t in zip(_CARRIED, (sx, sy, mm_sel, keys, dmm)):
-                    carry[name] = t[n_out:tot].clone()    # < B rows; the band's arrays go with its predictions
+                for name in _CARRIED:
+                    carry[name] = st[name][n_out:tot].clone()    # < B rows; the band's arrays go with its predictions
                 carry["n"] = tot - n_out
                 carry["issued"] = seq0 + ncall * B
             self.last_counts_halo = (nv, ncall)
@@ -430,10 +384,20 @@ class HaloShardedSuperResolution(DEMSuperResolution):
     def cropHalo(self, slabs: Sequence[Tuple[Tuple[torch.Tensor, torch.Tensor, torch.Tensor], Tuple[int, int]]]):
         """Assemble per-rank slabs (in rank order) into the final rasters cropped to the input extent: final pixel
         (y, x) is canvas pixel (y + S - s, x + S - s)."""
+        return self._crop_to_raster([torch.cat([sl[0][k] for sl in slabs], dim=0) for k in range(3)])
+
+    def _crop_to_raster(self, parts: Sequence[torch.Tensor]):
+        """Whole-canvas-height products -> host arrays of the raster's extent."""
         halo = self.image_size - self.stride
         h, w = self.dem_shape
-        parts = [torch.cat([sl[0][k] for sl in slabs], dim=0) for k in range(3)]
         return tuple(p[halo:halo + h, halo:halo + w].cpu().numpy() for p in parts)
+
+    def ownedRowCounts(self, world: int) -> List[int]:
+        """Canvas rows each rank of ``world`` owns, in rank order: its slab's height, what all_gather_var_rows takes."""
+        ys, _ = self.patchGrid()
+        hp = self.dem_padded_shape[0]
+        zones = halo_zone_rows(ys, self.image_size, world)
+        return [(hp if z["own_hi"] is None else z["own_hi"]) - z["own_lo"] for z in zones]
 
     def _process_files_sharded(self, preprocess: bool, rank: int, world: int, mode: str, gather: bool,
                                swap_dsize: bool = True, batching: str = "band", accumulate: str = "blocks"):
@@ -445,16 +409,12 @@ class HaloShardedSuperResolution(DEMSuperResolution):
         from .distributed import all_gather_var_rows
         self._load_rank_rows(preprocess, rank, world, mode, swap_dsize)
         (m, sd, g), (own_lo, own_hi) = self.processMapHalo(rank=rank, world=world, batching=batching, accumulate=accumulate)
-        hp = self.dem_padded_shape[0]
         if world > 1 and gather:
-            ys, _ = self.patchGrid()
-            zones = halo_zone_rows(ys, self.image_size, world)
-            counts = [(hp if z["own_hi"] is None else z["own_hi"]) - z["own_lo"] for z in zones]
+            counts = self.ownedRowCounts(world)
             parts = [all_gather_var_rows(t, counts) for t in (m, sd, g)]
         else:
+            hp = self.dem_padded_shape[0]
             parts = [torch.zeros((hp,) + tuple(t.shape[1:]), dtype=t.dtype, device=t.device) for t in (m, sd, g)]
             for full, t in zip(parts, (m, sd, g)):
                 full[own_lo:own_hi] = t
-        halo = self.image_size - self.stride
-        h, w = self.dem_shape
-        return tuple(p[halo:halo + h, halo:halo + w].cpu().numpy() for p in parts)
+        return self._crop_to_raster(parts)

@@ -14,6 +14,7 @@ What moves to the GPU (libmoonsr_hip.so, csrc/tiler.hip):
   batch assembly           -> msr_compact_patches (stable device-side compaction of the valid patches)
 Batch composition is exactly the reference's Python loop (invalid patches are skipped, the last batch is
 zero-padded: process_full_tiles.py:455-474) — SPADE's batch statistics make that composition part of the result.
+It is stated once, for the tiles and for halo.py's bands: _compact_patches, then _generator_calls / _host_model_calls.
 The host needs only the two counts (valid patches, calls) of a tile, 8 bytes fetched through pinned memory while
 the previous tile is still generating (iterTiles), so the generator stream never drains between tiles.
 """
@@ -63,6 +64,9 @@ def blend_window(image_size: int) -> np.ndarray:
     kern = (kern - kern.min()) / (kern.max() - kern.min())
     p = S // 16
     return np.ascontiguousarray((kern + 1e-7)[p:-p, p:-p])
+
+
+_CARRIED = ("sx", "sy", "mm_sel", "keys", "dmm")     # the compaction's five outputs, in the order of the kernel's arguments
 
 
 class DEMSuperResolution:
@@ -117,14 +121,11 @@ class DEMSuperResolution:
         self.resident = resident                     # where the rasters are held between the stages: HBM, or host memory
         self.transfers: List[Tuple[str, int, str]] = []
         self.products_path = None
-        if encoder not in ("host", "device"):
-            raise ValueError(f"encoder must be 'host' or 'device', got {encoder!r}")
+        for name, where in (("encoder", encoder), ("decoder", decoder), ("infill", infill)):
+            if where not in ("host", "device"):
+                raise ValueError(f"{name} must be 'host' or 'device', got {where!r}")
         self.encoder = encoder                       # saveGTiff: who differences and LZW-encodes the strips (geotiff.py)
-        if decoder not in ("host", "device"):
-            raise ValueError(f"decoder must be 'host' or 'device', got {decoder!r}")
         self.decoder = decoder                       # loadImages: who LZW-decodes the blocks and undoes the predictor
-        if infill not in ("host", "device"):
-            raise ValueError(f"infill must be 'host' or 'device', got {infill!r}")
         self.infill = infill                         # preprocess: who fills the small no-data holes (preprocess.py, infill.py)
         if range_check not in ("off", "warn", "raise"):
             raise ValueError(f"range_check must be 'off', 'warn' or 'raise', got {range_check!r}")
@@ -589,15 +590,108 @@ class DEMSuperResolution:
         xs = np.array(patch_origins_1d(px, S, s, T), dtype=np.int32)
         return np.stack([np.tile(xs, len(ys)), np.repeat(ys, len(xs))], axis=1)
 
+    # -- the batching sequence of both modes (halo.py: _generate_rows): compaction, then per call extract + generate.  The
+    # streams, waits, events and record_stream calls around it are the caller's: there the modes differ, and speed is decided
+    def _cap(self, n: int) -> int:
+        """Rows of the compaction outputs for n candidates: whole calls of B, at least one."""
+        return max(1, -(-n // self.batch_size)) * self.batch_size
+
+    def _compact_patches(self, ox: torch.Tensor, oy: torch.Tensor, tile_x: int, tile_y: int,
+                         carry: Optional[dict] = None) -> dict:
+        """On torch's current stream: getPatch's validity test and normalize's reductions for the candidates at (ox, oy),
+        generation order (msr_patch_stats), then the batch assembly of process_full_tiles.py:455-474 on the device
+        (msr_compact_patches).  Origins and ``tile_y`` are WINDOW rows (padInputs); the keys, origin - (tile_x, tile_y), come
+        out as in the full canvas.  ``carry`` (halo.py, batching="rank"): {"n": rows carried over, and those rows of the five
+        outputs}; they are copied to the front and the compaction starts behind them (msr_compact_patches_carry).
+        ``meta`` = {valid patches, carried ones included; calls} stays on the device: how the host gets it is the caller's."""
+        lib, h, dev = self._lib, self._h, self.device
+        _, rows, cols = self._window()
+        n = int(ox.numel())
+        carry_n = 0 if carry is None else carry["n"]
+        cap = self._cap(carry_n + n)
+        i32, f32 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float32, device=dev)
+        valid = torch.empty(n, dtype=torch.uint8, device=dev)
+        minmax = torch.empty((n, 4), **f32)
+        st = dict(n=n, cap=cap, keep=(ox, oy, valid, minmax), sx=torch.empty(cap, **i32), sy=torch.empty(cap, **i32),
+                  mm_sel=torch.empty((cap, 4), **f32), keys=torch.empty((cap, 2), **i32), dmm=torch.empty((cap, 2), **f32),
+                  meta=torch.empty(2, **i32))
+        stream = self._stream()
+        rc = lib.msr_patch_stats(h, self.img_padded.data_ptr(), self.dem_padded.data_ptr(), rows, cols, ox.data_ptr(),
+                                 oy.data_ptr(), n, self.no_value, valid.data_ptr(), minmax.data_ptr(), stream)
+        _lib.raise_for(lib, h, rc, "msr_patch_stats")
+        args = (h, valid.data_ptr(), ox.data_ptr(), oy.data_ptr(), minmax.data_ptr(), n, tile_x, tile_y, self.batch_size, cap)
+        outs = tuple(st[name].data_ptr() for name in _CARRIED) + (st["meta"].data_ptr(), stream)
+        if carry is None:
+            rc = lib.msr_compact_patches(*args, *outs)
+            _lib.raise_for(lib, h, rc, "msr_compact_patches")
+        else:
+            for name in _CARRIED if carry_n else ():
+                st[name][:carry_n].copy_(carry[name])               # the earlier band's tail, device to device
+            rc = lib.msr_compact_patches_carry(*args, carry_n, *outs)
+            _lib.raise_for(lib, h, rc, "msr_compact_patches_carry")
+        return st
+
+    def _extract_batch(self, st: dict, c: int, batch: torch.Tensor) -> None:
+        """On torch's current stream: the B patches of call ``c`` of the compacted list ``st``, normalised, into ``batch``
+        [B, S, S, 2] (msr_extract_patches; rows behind the last valid patch are zero patches)."""
+        B = self.batch_size
+        _, rows, cols = self._window()                # sx / sy are window origins already (_compact_patches)
+        rc = self._lib.msr_extract_patches(self._h, self.img_padded.data_ptr(), self.dem_padded.data_ptr(), rows, cols,
+                                           st["sx"][c * B:].data_ptr(), st["sy"][c * B:].data_ptr(),
+                                           st["mm_sel"][c * B:].data_ptr(), B, batch.data_ptr(), self._stream())
+        _lib.raise_for(self._lib, self._h, rc, "msr_extract_patches")
+
+    def _ready_pipeline(self) -> None:
+        """Before a tile's or band's calls: the handles exist (close() drops them); clones follow a load() on the base one."""
+        if self._gens is None:
+            self._make_pipeline()
+        for g in self._gens[1:]:
+            if g.weights_version != self._gen.weights_version:
+                g.load(self._gen._weights)
+                g.weights_version = self._gen.weights_version
+
+    def _generator_calls(self, st: dict, ncall: int, preds: torch.Tensor, batches: Sequence[torch.Tensor],
+                         ids: Optional[torch.Tensor] = None, gated: bool = False) -> None:
+        """The first ``ncall`` calls of the compacted list ``st``.  They are independent batches: they alternate over the
+        pipeline's handles, each on its own stream, so that the low-occupancy head of one call overlaps the tail of the other.
+        Call c extracts into ``batches[c % handles]`` and writes ``preds[c * B:(c + 1) * B]``: patches never leave HBM.
+        ``ids`` [cap, 3]: every row's noise id (sampler="counter").  ``gated``: the matrix-bound part of a call waits for the
+        event the previous call recorded (forward_device).  The first call's handle takes the range scan (range_check)."""
+        B = self.batch_size
+        for c in range(ncall):
+            k = c % len(self._gens)
+            with torch.cuda.stream(self._pstreams[k]):
+                self._extract_batch(st, c, batches[k])
+                self._gens[k].forward_device(batches[k], out=preds[c * B:(c + 1) * B].unsqueeze(-1),
+                                             gate=self._gate if gated else None,
+                                             noise_ids=None if ids is None else ids[c * B:(c + 1) * B])
+                if c == 0:
+                    self._range_enqueue(self._gens[k])
+                if gated:
+                    self._gate_ring = (self._gate_ring + 1) % len(self._gate_events)
+                    self._gate = self._gate_events[self._gate_ring]
+                    self._gate.record(self._pstreams[k])
+
+    def _host_model_calls(self, st: dict, ncall: int, preds: torch.Tensor) -> None:
+        """_generator_calls for a host callable, on the current stream: a stage on the host, resident or not, whose round trip
+        per call ``transfers`` lists."""
+        S, B = self.image_size, self.batch_size
+        batch = torch.empty((B, S, S, 2), dtype=torch.float32, device=self.device)
+        for c in range(ncall):
+            self._extract_batch(st, c, batch)
+            self._log("d2h", batch.numel() * 4, "batch for the host model")
+            out = np.array(self.model(batch.cpu().numpy(), training=False))[:, :, :, -1]
+            self._log("h2d", out.size * 4, "predictions of the host model")
+            preds[c * B:(c + 1) * B] = torch.from_numpy(np.ascontiguousarray(out, dtype=np.float32)).to(self.device)
+
     # -- one tile = prepare (validity, min/max, device-side batch assembly) -> generate -> stitch -------------------
     def _prepare_tile(self, px: int, py: int):
-        """Asynchronous first half of processTile on the handle's preparation stream: getPatch's validity test and
-        normalize's reductions for every patch of the tile (msr_patch_stats), then the batch assembly of
-        process_full_tiles.py:455-474 on the device (msr_compact_patches).  The host gets back two integers
-        {valid patches, calls} through pinned memory, behind an event — it fetches them while the GPU is still busy
-        with the previous tile (processTiles), so no flag array crosses PCIe and no host-side compaction exists."""
-        S, s, B, T = self.image_size, self.stride, self.batch_size, self.tile_size
-        lib, h, dev = self._lib, self._h, self.device
+        """Asynchronous first half of processTile on the handle's preparation stream: the tile's candidate patches and
+        their compaction into calls (_compact_patches).  The host gets back two integers {valid patches, calls} through
+        pinned memory, behind an event — it fetches them while the GPU is still busy with the previous tile
+        (processTiles), so no flag array crosses PCIe and no host-side compaction exists."""
+        S, s, T = self.image_size, self.stride, self.tile_size
+        dev = self.device
         if self._prep_stream is None:
             self._prep_stream = torch.cuda.Stream(dev)
         # The padded rasters are produced on the caller's stream (padInputs, or tensors the caller built): the preparation
@@ -608,7 +702,7 @@ class DEMSuperResolution:
         if getattr(self, "_raster_token", None) != token:
             self._prep_stream.wait_stream(torch.cuda.current_stream(dev))
             self._raster_token = token
-        c0, rows, cols = self._window()
+        c0 = self._window()[0]
         rx, ry = patch_origins_1d(px, S, s, T), patch_origins_1d(py, S, s, T)
         self._check_rows(f"tile ({px}, {py})", ry)
         st = {"px": px, "py": py}
@@ -617,52 +711,31 @@ class DEMSuperResolution:
             ys = torch.arange(ry.start - c0, ry.stop - c0, ry.step, dtype=torch.int32, device=dev)   # window rows
             ox = xs.repeat(ys.numel())                      # generation order: y outer, x inner (:453-454)
             oy = ys.repeat_interleave(xs.numel())
-            n = int(xs.numel() * ys.numel())
-            cap = max(B, (n + B - 1) // B * B)
-            valid = torch.empty(n, dtype=torch.uint8, device=dev)
-            minmax = torch.empty((n, 4), dtype=torch.float32, device=dev)
-            sx = torch.empty(cap, dtype=torch.int32, device=dev)
-            sy = torch.empty(cap, dtype=torch.int32, device=dev)
-            mm_sel = torch.empty((cap, 4), dtype=torch.float32, device=dev)
-            keys = torch.empty((cap, 2), dtype=torch.int32, device=dev)
-            dmm = torch.empty((cap, 2), dtype=torch.float32, device=dev)
-            meta = torch.empty(2, dtype=torch.int32, device=dev)
             if self.counter_noise:
                 # Row d of the tile's compacted list draws the noise (d, px, py), padding rows of the last call included: the
                 # id names the tile (canvas coordinates) and the position in its compaction, nothing of this rank or run.
+                cap = self._cap(int(ox.numel()))
                 ids = torch.empty((cap, 3), dtype=torch.int32, device=dev)
                 ids[:, 0] = torch.arange(cap, dtype=torch.int32, device=dev)
                 ids[:, 1] = px
                 ids[:, 2] = py
                 st["noise_ids"] = ids
-            stream = self._prep_stream.cuda_stream
-            rc = lib.msr_patch_stats(h, self.img_padded.data_ptr(), self.dem_padded.data_ptr(), rows, cols,
-                                     ox.data_ptr(), oy.data_ptr(), n, self.no_value, valid.data_ptr(),
-                                     minmax.data_ptr(), stream)
-            _lib.raise_for(lib, h, rc, "msr_patch_stats")
-            # tile_y in window rows too: the keys (origin - tile origin) come out as in the full canvas
-            rc = lib.msr_compact_patches(h, valid.data_ptr(), ox.data_ptr(), oy.data_ptr(), minmax.data_ptr(), n, px,
-                                         py - c0, B, cap, sx.data_ptr(), sy.data_ptr(), mm_sel.data_ptr(), keys.data_ptr(),
-                                         dmm.data_ptr(), meta.data_ptr(), stream)
-            _lib.raise_for(lib, h, rc, "msr_compact_patches")
+            st.update(self._compact_patches(ox, oy, px, py - c0))   # tile_y in window rows too
             meta_host = torch.empty(2, dtype=torch.int32, pin_memory=True)
-            meta_host.copy_(meta, non_blocking=True)
+            meta_host.copy_(st["meta"], non_blocking=True)
             ev = torch.cuda.Event()
             ev.record(self._prep_stream)
-        st.update(n=n, cap=cap, sx=sx, sy=sy, mm_sel=mm_sel, keys=keys, dmm=dmm, meta=meta, meta_host=meta_host, event=ev,
-                  keep=(ox, oy, valid, minmax))
+        st.update(meta_host=meta_host, event=ev)
         return st
 
     def _generate_tile(self, st):
         """Second half of processTile: the tile's generator calls (batches cut from the compacted origins, the last
         one zero-padded) and the stitcher, all on the current stream / the pipeline streams."""
         S, B = self.image_size, self.batch_size
-        lib, h, dev = self._lib, self._h, self.device
-        _, rows, cols = self._window()                # sx / sy are window origins already (_prepare_tile)
+        dev = self.device
         st["event"].synchronize()                     # 8 bytes; the GPU keeps working on what is already queued
         self._range_retire()                          # the previous tile's scan (range_check), read at the same point
         nv, ncall = (int(v) for v in st["meta_host"].tolist())
-        total = ncall * B
         sx, sy, mm_sel = st["sx"], st["sy"], st["mm_sel"]
         ids = st.get("noise_ids")                     # sampler="counter" only; None leaves every call as it always was
         self._last = (st["keys"], nv, ncall)
@@ -672,63 +745,28 @@ class DEMSuperResolution:
             for t in (sx, sy, mm_sel, st["keys"], st["dmm"]):
                 t.record_stream(cur)
             if self._gen is not None:
-                # The calls of a tile are independent batches: alternate them over `pipeline` generator handles, each
-                # on its own stream, so that the low-occupancy head of one call overlaps the tail of the other.
-                # Patches go from the rasters to `preds` without leaving HBM.  `preds` is one of two persistent
-                # buffers (no allocation per tile — a fresh 0.5 GB hipMalloc drains the device), and the generator
-                # streams wait only for the events they need (this tile's preparation; the stitcher pass that last read
-                # this buffer, two tiles ago), so tile t+1 starts generating while tile t is being stitched.
-                if self._gens is None:
-                    self._make_pipeline()
-                for g in self._gens[1:]:       # a load() on the base generator after construction: the clones follow
-                    if g.weights_version != self._gen.weights_version:
-                        g.load(self._gen._weights)
-                        g.weights_version = self._gen.weights_version
+                # The calls go to one of two persistent buffers (no allocation per tile — a fresh 0.5 GB hipMalloc drains the
+                # device), and the generator streams wait only for the events they need (this tile's preparation; the stitcher
+                # pass that last read this buffer, two tiles ago), so tile t+1 starts generating while tile t is stitched.
+                self._ready_pipeline()
                 buf = self._tile_buffers(st["cap"])
-                preds, batches = buf["preds"], self._batches
                 for ps in self._pstreams:
                     ps.wait_event(st["event"])
                     if buf["free"] is not None:
                         ps.wait_event(buf["free"])
                     for t in (sx, sy, mm_sel) + (() if ids is None else (ids,)):
                         t.record_stream(ps)
-                gated = self.gated and len(self._gens) > 1
-                for c in range(ncall):
-                    k = c % len(self._gens)
-                    with torch.cuda.stream(self._pstreams[k]):
-                        rc = lib.msr_extract_patches(h, self.img_padded.data_ptr(), self.dem_padded.data_ptr(), rows,
-                                                     cols, sx[c * B:].data_ptr(), sy[c * B:].data_ptr(),
-                                                     mm_sel[c * B:].data_ptr(), B, batches[k].data_ptr(), self._stream())
-                        _lib.raise_for(lib, h, rc, "msr_extract_patches")
-                        self._gens[k].forward_device(batches[k], out=preds[c * B:(c + 1) * B].unsqueeze(-1),
-                                                     gate=self._gate if gated else None,
-                                                     noise_ids=None if ids is None else ids[c * B:(c + 1) * B])
-                        if c == 0:
-                            self._range_enqueue(self._gens[k])
-                        if gated:
-                            self._gate_ring = (self._gate_ring + 1) % len(self._gate_events)
-                            self._gate = self._gate_events[self._gate_ring]
-                            self._gate.record(self._pstreams[k])
+                self._generator_calls(st, ncall, buf["preds"], self._batches, ids, self.gated and len(self._gens) > 1)
                 for ps in self._pstreams:
                     cur.wait_stream(ps)
                 cur.wait_event(st["event"])
-                out = self.rebuildTile(preds, st["keys"], st["dmm"], nv)
+                out = self.rebuildTile(buf["preds"], st["keys"], st["dmm"], nv)
                 buf["free"] = torch.cuda.Event()
                 buf["free"].record(cur)
                 return out
             cur.wait_event(st["event"])
-            preds = torch.empty((max(total, 1), S, S), dtype=torch.float32, device=dev)
-            batch = torch.empty((B, S, S, 2), dtype=torch.float32, device=dev)
-            for c in range(ncall):
-                rc = lib.msr_extract_patches(h, self.img_padded.data_ptr(), self.dem_padded.data_ptr(), rows, cols,
-                                             sx[c * B:].data_ptr(), sy[c * B:].data_ptr(), mm_sel[c * B:].data_ptr(),
-                                             B, batch.data_ptr(), self._stream())
-                _lib.raise_for(lib, h, rc, "msr_extract_patches")
-                # a host callable is a stage on the host: its round trip is its own, resident or not
-                self._log("d2h", batch.numel() * 4, "batch for the host model")
-                out = np.array(self.model(batch.cpu().numpy(), training=False))[:, :, :, -1]
-                self._log("h2d", out.size * 4, "predictions of the host model")
-                preds[c * B:(c + 1) * B] = torch.from_numpy(np.ascontiguousarray(out, dtype=np.float32)).to(dev)
+            preds = torch.empty((max(ncall * B, 1), S, S), dtype=torch.float32, device=dev)
+            self._host_model_calls(st, ncall, preds)
             return self.rebuildTile(preds, st["keys"], st["dmm"], nv)
 
     # -- range_check: one scan per tile, read one tile late -------------------------------------------------------------

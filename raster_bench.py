@@ -150,7 +150,7 @@ def main():
     mine = shard_tile_rows(tiles, shard_rank, shard_world)
     if args.halo:
         from moonsuperresolution_amd import HaloShardedSuperResolution
-        from moonsuperresolution_amd.distributed import all_gather_var_rows, halo_zone_rows
+        from moonsuperresolution_amd.distributed import all_gather_var_rows
         hs = HaloShardedSuperResolution(DSRConfig(image_size=S, stride=s, batch_size=B, tile_size=T), model=gen,
                                         device=local, pipeline=args.pipeline)
         hs.dem_shape, hs.img_shape = dsr.dem_shape, dsr.img_shape
@@ -180,9 +180,7 @@ def main():
         t_ex = time.perf_counter() - t0 - t_acc
         free_b, total_b = torch.cuda.mem_get_info()
         if world > 1 and args.gather:
-            ys, _ = hs.patchGrid()
-            zones = halo_zone_rows(ys, S, world)
-            counts = [(hs.dem_padded_shape[0] if z["own_hi"] is None else z["own_hi"]) - z["own_lo"] for z in zones]
+            counts = hs.ownedRowCounts(world)
             m, sd, g = (all_gather_var_rows(t, counts) for t in (m, sd, g))
             torch.cuda.synchronize()
         if world > 1:
@@ -284,10 +282,7 @@ def main():
         st0 = dsr._prepare_tile(*todo[0])
         st0["event"].synchronize()
         real = torch.empty((B, S, S, 2), device="cuda")
-        rows_p, cols_p = dsr.dem_window_shape       # the tensors' own shape: sx / sy are window origins
-        dsr._lib.msr_extract_patches(dsr._h, dsr.img_padded.data_ptr(), dsr.dem_padded.data_ptr(), rows_p, cols_p,
-                                     st0["sx"].data_ptr(), st0["sy"].data_ptr(), st0["mm_sel"].data_ptr(), B,
-                                     real.data_ptr(), torch.cuda.current_stream().cuda_stream)
+        dsr._extract_batch(st0, 0, real)
         gen_only = gen_pass([real for _ in dsr._gens])
         gen_only_noise = gen_pass([torch.zeros((B, S, S, 2), device="cuda").uniform_(-0.5, 0.5) for _ in dsr._gens])
     tot = torch.tensor([patches, calls, elapsed], dtype=torch.float64, device="cuda")

@@ -200,6 +200,57 @@ def test_tile_mode_products_do_not_depend_on_pipeline_run_or_ranks(hip_lib, weig
     gen2.close()
 
 
+def test_gated_tile_loop_gives_the_ungated_products(hip_lib, weights, monkeypatch):
+    """MSR_TILER_GATED=1 (read at construction): every call of a two-handle pipeline waits, in its matrix-bound part, for the
+    event the previous call recorded on the other stream.  An ordering of work only: all three products are the bits of the
+    ungated two-handle loop and of the one-handle loop."""
+    from moonsuperresolution_amd import DEMSuperResolution, Generator
+    img, dem = synthetic_raster(SHAPE[0], SHAPE[1], seed=9, hole=HOLE)
+    gen = Generator(S, B, variant="gaugan", weights=weights, sampler="counter", seed=SEED)
+
+    def run(pipeline, gated):
+        if gated:
+            monkeypatch.setenv("MSR_TILER_GATED", "1")
+        else:
+            monkeypatch.delenv("MSR_TILER_GATED", raising=False)
+        d = DEMSuperResolution(_cfg(), model=gen, pipeline=pipeline)
+        assert d.gated == gated and len(d._gens) == pipeline
+        out = d.processMap(img, dem)
+        d.close()
+        return out
+
+    got = run(2, True)
+    assert got[2].any() and not got[2].all() and np.isfinite(got[0][got[2] > 0]).all()
+    for name, want in (("ungated pipeline=2", run(2, False)), ("pipeline=1", run(1, False))):
+        for k in range(3):
+            assert np.array_equal(got[k], want[k], equal_nan=True), (name, k)
+    gen.close()
+
+
+def test_pipeline_clones_follow_a_load_on_the_base_generator(hip_lib, weights):
+    """load() on the generator a two-handle driver was built on: the next map is the map of a fresh driver on the new weights,
+    so the clone (which takes every second call of a tile) holds them too."""
+    from moonsuperresolution_amd import DEMSuperResolution, Generator, make_weights
+    img, dem = synthetic_raster(SHAPE[0], SHAPE[1], seed=9, hole=HOLE)
+    other = make_weights("gaugan", S, seed=4321)
+    gen = Generator(S, B, variant="gaugan", weights=weights, sampler="counter", seed=SEED)
+    d = DEMSuperResolution(_cfg(), model=gen, pipeline=2)
+    first = d.processMap(img, dem)
+    gen.load(other)
+    second = d.processMap(img, dem)
+    assert all(g.weights_version == gen.weights_version for g in d._gens)
+    d.close()
+    fresh_gen = Generator(S, B, variant="gaugan", weights=other, sampler="counter", seed=SEED)
+    fresh = DEMSuperResolution(_cfg(), model=fresh_gen, pipeline=1)      # one handle: nothing of a clone in what is expected
+    want = fresh.processMap(img, dem)
+    fresh.close()
+    for k in range(3):
+        assert np.array_equal(second[k], want[k], equal_nan=True), k
+    assert np.array_equal(first[2], second[2]) and not np.array_equal(first[0], second[0], equal_nan=True)
+    gen.close()
+    fresh_gen.close()
+
+
 # ---- 4. graph replay ----------------------------------------------------------------------------------------------------
 def test_graph_replay_follows_the_noise_buffer(hip_lib, weights):
     """The noise pointer never changes, so the second call captures and the third replays; the fill runs on the stream ahead

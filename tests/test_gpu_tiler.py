@@ -295,6 +295,27 @@ def test_identity_map_bit_exact_many_geometries(dsr, S, stride, B, T, shape, hol
     d.close()
 
 
+def test_halo_mode_logs_the_host_model_round_trips(dsr):
+    """``transfers`` lists every copy the driver issues itself: with a host-callable model the halo mode downloads one batch and
+    uploads one block of predictions per generator call, as the tile mode does.  The map is the one
+    test_gpu_halo.py::test_identity_model_halo_mode expects for this geometry (the oracle's, bit for bit)."""
+    from moonsuperresolution_amd import DSRConfig, HaloShardedSuperResolution
+    S, stride, B, T, shape, hole = 64, 16, 4, 128, (200, 330), (90, 110, 140, 170)
+    img, dem = synthetic_raster(shape[0], shape[1], seed=S + stride, hole=hole)
+    d = HaloShardedSuperResolution(DSRConfig(image_size=S, stride=stride, batch_size=B, tile_size=T), model=f32_identity)
+    got = d.cropHalo([d.processMapHalo(img, dem, band_rows=2)])
+    ncall = d.last_counts_halo[1]
+    assert len(d.last_band_counts) >= 3 and ncall == sum(c for _, c in d.last_band_counts) > len(d.last_band_counts)
+    down = [t for t in d.transfers if t[0] == "d2h"]
+    up = [t for t in d.transfers if t[0] == "h2d" and "host model" in t[2]]
+    assert down == [("d2h", B * S * S * 2 * 4, "batch for the host model")] * ncall
+    assert up == [("h2d", B * S * S * 4, "predictions of the host model")] * ncall
+    want = tiler_ref.process_map_halo(img, dem, f32_identity, S, stride, B, T, NOVAL, world=1)
+    for a, b in zip(got, want):
+        assert np.array_equal(a, b, equal_nan=True)
+    d.close()
+
+
 def test_all_nodata_raster_gives_no_value_everywhere(dsr):
     DEMSuperResolution, DSRConfig = dsr
     img = np.full((100, 100), 0.5, np.float32)

@@ -25,10 +25,7 @@ torch.cuda.synchronize()
 ncall = d.last_counts[1]
 st = d._prepare_tile(*tiles[0])
 st["event"].synchronize()
-sx, sy, mm = st["sx"], st["sy"], st["mm_sel"]
-rows, cols = d.dem_padded_shape
 preds = d._bufs[0]["preds"]
-lib, h = d._lib, d._h
 
 
 def run(name, per_call_out, extract, nstreams=2, reps=2, gated=False):
@@ -46,9 +43,7 @@ def run(name, per_call_out, extract, nstreams=2, reps=2, gated=False):
             k = c % nstreams
             with torch.cuda.stream(d._pstreams[k]):
                 if extract:
-                    lib.msr_extract_patches(h, d.img_padded.data_ptr(), d.dem_padded.data_ptr(), rows, cols,
-                                            sx[c * B:].data_ptr(), sy[c * B:].data_ptr(), mm[c * B:].data_ptr(), B,
-                                            d._batches[k].data_ptr(), torch.cuda.current_stream().cuda_stream)
+                    d._extract_batch(st, c, d._batches[k])
                 out = preds[c * B:(c + 1) * B].unsqueeze(-1) if per_call_out else outs[k]
                 d._gens[k].forward_device(d._batches[k], out=out, gate=last if gated else None)
                 if gated:
