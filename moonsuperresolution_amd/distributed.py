@@ -188,6 +188,39 @@ def exchange_halo_start(send_down, send_up, recv_down_shape, recv_up_shape, rank
     return wait
 
 
+def exchange_strip_rows(slabs: Sequence, plans: Sequence[dict], rank: int, world: int) -> list:
+    """The hand-over before rank-local encoding in halo mode: per product, ``slabs[i]`` holds this rank's rows
+    ``plans[i]["rows"][rank]`` (halo_strip_plan; a cropped view will do).  Rows ``give[rank]`` of it go to rank - 1, rows
+    ``take[rank]`` come from rank + 1 — non-blocking send / recv like exchange_halo_start, all products in one batch, the
+    contiguous send buffers kept until the wait — and the rows of the rank's strips, [s0 rps, min(s1 rps, H)), are returned as
+    one tensor per product: a view of the slab where nothing is taken, else one concatenation.  A rank that neither gives nor
+    takes issues nothing (and needs no process group)."""
+    import torch
+    import torch.distributed as dist
+    ops, keep, got, kept = [], [], [], []
+    for slab, plan in zip(slabs, plans):
+        if not plan["local"]:
+            raise ValueError("exchange_strip_rows: a strip of this plan holds rows of three ranks (plan['local'] is False)")
+        (r0, r1), (g0, g1), (t0, t1) = plan["rows"][rank], plan["give"][rank], plan["take"][rank]
+        if slab.shape[0] != r1 - r0:
+            raise ValueError(f"exchange_strip_rows: {slab.shape[0]} rows given for rank {rank}'s rows [{r0}, {r1})")
+        n_give, n_take = max(0, g1 - g0), max(0, t1 - t0)
+        recv = None
+        if n_give:                                       # my first rows complete rank - 1's last strip
+            keep.append(slab[:n_give].contiguous())
+            ops.append(dist.P2POp(dist.isend, keep[-1], rank - 1))
+        if n_take:
+            recv = torch.empty((n_take,) + tuple(slab.shape[1:]), dtype=slab.dtype, device=slab.device)
+            ops.append(dist.P2POp(dist.irecv, recv, rank + 1))
+        kept.append(slab[n_give:])
+        got.append(recv)
+    if ops:
+        for req in dist.batch_isend_irecv(ops):
+            req.wait()
+        keep.clear()
+    return [k if g is None else torch.cat([k, g], dim=0) for k, g in zip(kept, got)]
+
+
 def all_gather_var_rows(local, counts: Sequence[int]):
     """All-gather of row slabs whose row counts differ by rank (halo mode: ownership boundaries follow patch rows, not
     tiles): pad to the largest count, one all_gather_into_tensor, trim.  counts[r] = rows of rank r."""
@@ -328,3 +361,37 @@ def strip_plan(shape: Tuple[int, int], itemsize: int, tile_size: int, world: int
     straddles = any(0 < r0 < H and r0 % rps for r0, _ in rows)
     strips = None if straddles else [(-(-r0 // rps), -(-r1 // rps)) for r0, r1 in rows]
     return {"rps": rps, "n_strips": n_strips, "rows": rows, "straddles": straddles, "strips": strips}
+
+
+def halo_strip_plan(shape: Tuple[int, int], itemsize: int, image_size: int, stride: int, tile_size: int, world: int) -> dict:
+    """strip_plan for a patch-row-sharded run (processFiles(mode="halo", products="rank0")).  Ownership follows patch rows
+    (halo_zone_rows), not tiles, so a rank boundary is seldom a strip boundary; instead of giving up, the rank that owns a
+    strip's first row takes the strip's other rows from the rank above (exchange_strip_rows).  Pure arithmetic.
+
+      rps, n_strips  as in strip_plan
+      rows       per rank, the product rows [r0, r1) it finalises: canvas rows [own_lo, own_hi) less the S - s margin, clipped
+                 to [0, H].  Consecutive, covering [0, H); (H, H) for a rank whose zone lies below the raster
+      strips     per rank, the strips [s0, s1) it encodes: strip k goes to the rank that owns row k rps.  Consecutive,
+                 covering every strip once; (s, s) for a rank that owns no first row of a strip
+      take       per rank, the rows [t0, t1) it needs from rank + 1 to complete its last strip: [r1, min(s1 rps, H)), empty
+                 (t0 == t1) when r1 is a multiple of rps or H, or when the rank encodes no strip
+      give       per rank, take[rank - 1]: the rows it hands down; (0, 0) for rank 0
+      local      False when some take[r] reaches beyond rows[r + 1] (a strip holds rows of three ranks): rank-local encoding
+                 needs True (for every product dtype of the run)"""
+    from .geotiff import _rows_per_strip
+    H, W = int(shape[0]), int(shape[1])
+    if H < 1 or W < 1 or itemsize < 1 or tile_size < 1 or world < 1 or image_size < 1 or not 0 < stride <= image_size:
+        raise ValueError("strip_plan needs a non-empty raster, itemsize, tile_size and world >= 1")
+    S, halo = int(image_size), int(image_size) - int(stride)
+    rps = _rows_per_strip(H, W * int(itemsize))
+    n_strips = -(-H // rps)
+    ys = patch_grid_1d(tile_rows(tile_origins((H, W), tile_size)), S, stride, tile_size)
+
+    def clip(c):                                          # canvas row -> raster row
+        return H if c is None else max(0, min(H, c - halo))
+    rows = [(clip(z["own_lo"]), clip(z["own_hi"])) for z in halo_zone_rows(ys, S, world)]
+    strips = [(min(n_strips, -(-r0 // rps)), min(n_strips, -(-r1 // rps))) for r0, r1 in rows]
+    take = [(r1, min(s1 * rps, H) if s1 > s0 else r1) for (_, r1), (s0, s1) in zip(rows, strips)]
+    give = [(0, 0)] + take[:-1]
+    local = all(t1 <= rows[r + 1][1] for r, (t0, t1) in enumerate(take) if t1 > t0)
+    return {"rps": rps, "n_strips": n_strips, "rows": rows, "strips": strips, "take": take, "give": give, "local": local}

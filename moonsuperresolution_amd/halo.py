@@ -81,7 +81,17 @@ def flush_padding(valid_per_band: Sequence[int], batch_size: int) -> List[Tuple[
 class HaloShardedSuperResolution(DEMSuperResolution):
     """DEMSuperResolution with the halo mode added: ``processMapHalo(rank, world)``.
 
-    ``resident`` is accepted and must be False: the halo mode's bands, zones and slabs still end on the host."""
+    ``resident`` is accepted and must be False: the halo mode's inputs and its default products still end on the host.
+
+    ``processFiles(mode="halo", rank=, world=)`` is the driver on files (DEMSuperResolution.processFiles; ``batching`` and
+    ``accumulate`` go to processMapHalo).  With the default ``products="gathered"`` every rank all-gathers the three slabs,
+    downloads them and writes the files.  With ``products="rank0"`` the slabs stay on the rank's device: it crops them (views)
+    to its raster rows, hands the rows that belong to a strip begun by the rank below down to it and takes the rest of its own
+    last strip from the rank above (distributed.halo_strip_plan / exchange_strip_rows: fewer than rows-per-strip rows a
+    product and boundary, recorded in ``handover_rows`` = {product: (give, take)}), encodes its strips with the ``encoder``
+    set, and rank 0 alone writes — byte for byte the files of the gathered run with the same ranks.  ``products_path`` is
+    "rank0" then (always with one rank, which needs no process group); when a strip holds rows of three ranks the run takes
+    the gathered slabs instead, rank 0 alone writes, and ``products_path`` is "gathered"."""
 
     def __init__(self, *args, resident: bool = False, **kwargs) -> None:
         if not isinstance(resident, bool):
@@ -89,6 +99,7 @@ class HaloShardedSuperResolution(DEMSuperResolution):
         if resident:
             raise ValueError("resident=True is not built for the halo mode")
         super().__init__(*args, **kwargs)
+        self.handover_rows = {}                      # processFiles(products="rank0"): per product (give, take) of this rank
 
     def patchGrid(self) -> Tuple[list, list]:
         """Unique patch origins the reference's tiles touch (padded-canvas coordinates): (ys, xs), sorted."""
@@ -418,3 +429,46 @@ class HaloShardedSuperResolution(DEMSuperResolution):
             for full, t in zip(parts, (m, sd, g)):
                 full[own_lo:own_hi] = t
         return self._crop_to_raster(parts)
+
+    def _process_files_rank0(self, preprocess: bool, rank: int, world: int, mode: str, swap_dsize: bool = True,
+                             batching: str = "band", accumulate: str = "blocks", **sharded) -> None:
+        """processFiles(mode="halo", products="rank0"): see processFiles.  The slabs a rank finalised stay on its device until
+        they are encoded (``encoder="host"``: the rows of its strips are downloaded once, after the hand-over)."""
+        if mode != "halo":
+            return super()._process_files_rank0(preprocess, rank, world, mode, swap_dsize, **sharded)
+        if sharded:
+            raise TypeError(f"processFiles: mode='halo' takes no {sorted(sharded)}")
+        from .distributed import all_gather_var_rows, exchange_strip_rows, halo_strip_plan
+        if world > 1:
+            import torch.distributed as dist
+            if not (dist.is_available() and dist.is_initialized()):
+                raise RuntimeError("products='rank0' needs an initialised process group")
+        self._load_rank_rows(preprocess, rank, world, mode, swap_dsize)
+        slabs, (own_lo, own_hi) = self.processMapHalo(rank=rank, world=world, batching=batching, accumulate=accumulate)
+        (h, w), halo = self.dem_shape, self.image_size - self.stride
+        names = ("mean", "std", "good")
+        plans = [halo_strip_plan((h, w), np.dtype(dt).itemsize, self.image_size, self.stride, self.tile_size, world)
+                 for dt in (np.float32, np.float32, np.uint16)]
+        local = all(p["local"] for p in plans)
+        self.products_path = "rank0" if local or world == 1 else "gathered"
+        self.handover_rows = {}
+        if not local:
+            # a strip holds rows of three ranks (a narrow raster): the gathered slabs, written by rank 0 alone
+            counts = self.ownedRowCounts(world)
+            products = self._crop_to_raster([all_gather_var_rows(t, counts) for t in slabs])
+            if rank == 0:
+                for name, data in zip(names, products):
+                    self.saveGTiff(data, data.dtype, name)
+            return
+        r0, r1 = plans[0]["rows"][rank]                   # the rows are the same for every product: views, nothing moves
+        c0 = r0 + halo - own_lo if r1 > r0 else 0        # a zone below the raster: no product row
+        assert 0 <= c0 and c0 + r1 - r0 <= own_hi - own_lo, ((r0, r1), (own_lo, own_hi))
+        mine = [t[c0:c0 + r1 - r0, halo:halo + w] for t in slabs]
+        for name, plan in zip(names, plans):
+            self.handover_rows[name] = (plan["give"][rank], plan["take"][rank])
+        if world > 1:
+            torch.cuda.current_stream(self.device).synchronize()  # the slabs are complete before rows of them are sent
+        with torch.cuda.device(self.device):
+            mine = exchange_strip_rows(mine, plans, rank, world)
+        for name, data, plan in zip(names, mine, plans):
+            self._encode_gather_write(name, data, plan, rank, world)

@@ -373,13 +373,16 @@ class DEMSuperResolution:
         ``mode="halo"`` is accepted by HaloShardedSuperResolution.processFiles only; further keywords (``batching``,
         ``accumulate``: halo.py) go to the sharded mode that takes them.
 
-        ``products="rank0"`` (``mode="tiles"``; needs an initialised process group when world > 1; ``gather`` is not looked
+        ``products="rank0"`` (a sharded mode; needs an initialised process group when world > 1; ``gather`` is not looked
         at): no all-gather of the products.  Every rank encodes the strips of the product rows it computed, with the
         ``encoder`` set; the encoded strips are gathered to rank 0, which alone writes the three files — byte for byte those
         of a one-process run.  That needs every rank boundary to be a strip boundary of the float32 and of the uint16
         products (distributed.strip_plan): always so once a row exceeds 32 KiB.  Otherwise the run takes the gathered path,
         and only rank 0 writes.  ``products_path`` says which of the two ran.  The default, "gathered", is the all-gather
-        after which every rank writes the files."""
+        after which every rank writes the files.  With ``mode="halo"`` (HaloShardedSuperResolution) rank boundaries follow
+        patch rows, so the rank that owns a strip's first row first receives the strip's other rows from the rank above
+        (distributed.halo_strip_plan, exchange_strip_rows); the files are those of the gathered halo run with the same ranks,
+        and the fallback is taken only when a strip holds rows of three ranks."""
         if products not in ("gathered", "rank0"):
             raise ValueError(f"products must be 'gathered' or 'rank0', got {products!r}")
         if products == "rank0" and self.product_tile is not None:
@@ -447,7 +450,6 @@ class DEMSuperResolution:
                              **sharded) -> None:
         """processFiles(products="rank0"): see there.  The rank's rows never leave its device before they are encoded
         (``encoder="host"``: they are downloaded once, by saveGTiff's rule)."""
-        from . import geotiff
         from .distributed import process_map_sharded, strip_plan
         if mode != "tiles":
             raise ValueError(f"products='rank0' is built for mode='tiles', got mode={mode!r}")
@@ -476,23 +478,36 @@ class DEMSuperResolution:
         mine = process_map_sharded(shape, T, tiles, self.processTile, rank, world, device=self.device, as_tensor=True,
                                    local=True)
         for name, data in zip(("mean", "std", "good"), mine):
-            plan = plans[name]
-            dt = np.dtype(np.uint16 if name == "good" else np.float32)
-            r0, r1 = plan["rows"][rank]
+            r0, r1 = plans[name]["rows"][rank]
             assert tuple(data.shape) == (r1 - r0, shape[1]), (tuple(data.shape), (r0, r1), shape)
-            if self.encoder == "host" and data.numel():
-                self._log("d2h", data.numel() * data.element_size(), f"{name} product rows")
-                data = data.cpu().numpy()
-            strips = geotiff.encode_strips(data, dt, plan["rps"], encoder=self.encoder, device=self.device,
-                                           transfers=self.transfers) if r1 > r0 else []
+            self._encode_gather_write(name, data, plans[name], rank, world)
+
+    def _encode_gather_write(self, name: str, data, plan: dict, rank: int, world: int) -> None:
+        """The last steps of both rank-local writers: ``data`` holds the rows of this rank's strips ``plan["strips"][rank]`` of
+        product ``name`` (a device tensor; distributed.strip_plan / halo_strip_plan).  They are encoded where ``encoder`` says
+        (on the host after one download), the encoded strips are gathered to rank 0 (no process group with one rank), and
+        rank 0 writes the file."""
+        from . import geotiff
+        shape = self.dem_shape
+        dt = np.dtype(np.uint16 if name == "good" else np.float32)
+        s0, s1 = plan["strips"][rank]
+        if self.encoder == "host" and data.numel():
+            self._log("d2h", data.numel() * data.element_size(), f"{name} product rows")
+            data = data.cpu().numpy()
+        strips = geotiff.encode_strips(data, dt, plan["rps"], encoder=self.encoder, device=self.device,
+                                       transfers=self.transfers) if data.shape[0] else []
+        assert len(strips) == s1 - s0, (name, rank, len(strips), (s0, s1))
+        if world > 1:
+            import torch.distributed as dist
             gathered = [None] * world if rank == 0 else None
             dist.gather_object(strips, gathered, dst=0)
             if rank == 0:
                 strips = [s for part in gathered for s in part]
-                assert len(strips) == plan["n_strips"], (len(strips), plan["n_strips"])
-                os.makedirs(self.save_path, exist_ok=True)
-                geotiff.write_strips(os.path.join(self.save_path, self.map_name + "_" + name + ".tiff"), strips, shape, dt,
-                                     plan["rps"], getattr(self, "geo_meta", None), nodata=self.no_value)
+        if rank == 0:
+            assert len(strips) == plan["n_strips"], (len(strips), plan["n_strips"])
+            os.makedirs(self.save_path, exist_ok=True)
+            geotiff.write_strips(os.path.join(self.save_path, self.map_name + "_" + name + ".tiff"), strips, shape, dt,
+                                 plan["rps"], getattr(self, "geo_meta", None), nodata=self.no_value)
 
     def padInputs(self) -> None:
         """process_full_tiles.py:246-267: no_value canvas ((dim//1024)+1)*1024 + 2(S-s), data at offset (S-s).
