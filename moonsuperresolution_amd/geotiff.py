@@ -13,15 +13,17 @@ and ``_good.tiff`` (UInt16) as LZW GeoTIFFs with ``PREDICTOR=2`` and a nodata ta
   metadata (shape included) from the header alone — what a rank of a sharded run needs to read only its own rows.
   The blocks are decoded on the host (default) or, ``decoder="device"``, LZW files on the GPU (csrc/geotiff_codec.hip:
   LZW per block, then predictor, conversion and placement) with the same bits out.
-* write: single band, little-endian, strips, LZW + horizontal predictor (or none / deflate), classic TIFF or BigTIFF
-  chosen by size; the strips are differenced and LZW-encoded on the host (default) or, ``encoder="device"``, on the GPU
-  (csrc/geotiff_codec.hip) with the same bytes out, GDAL_NODATA tag, and the GeoTIFF georeferencing tags of the input **passed through verbatim**
-  (ModelPixelScale 33550, ModelTiepoint 33922, ModelTransformation 34264, GeoKeyDirectory 34735, GeoDoubleParams
-  34736, GeoAsciiParams 34737, GDAL_METADATA 42112) — the output keeps the input's geotransform and projection
-  byte for byte, which is what ``saveGTiff`` does with ``SetGeoTransform`` / ``SetProjection``.
-  Opt-in: ``tile=(tile_h, tile_w)`` writes tiles instead of strips and ``overviews=n`` adds n reduced-resolution levels as
-  chained IFDs (GDAL's internal-overview layout), each the 2 x 2 reduction ``overview_reference`` of the one before; with
-  ``encoder="device"`` the levels are reduced (csrc/tiff_overview.hip) and the tiles encoded on the GPU, same bytes out.
+* write: single band, little-endian, LZW + horizontal predictor (or none / deflate), classic TIFF or BigTIFF chosen by
+  size, in blocks that are strips of whole rows (default) or, ``tile=(tile_h, tile_w)``, zero-padded tiles; with tiles,
+  ``overviews=n`` adds n reduced-resolution levels as chained IFDs (GDAL's internal-overview layout), each the 2 x 2
+  reduction ``overview_reference`` of the one before.  The blocks of either layout are differenced and encoded one by one
+  on the host (default; _encode_block) or, ``encoder="device"``, band by band on the GPU (_encode_band_device:
+  csrc/geotiff_codec.hip, the levels reduced by csrc/tiff_overview.hip) with the same bytes out; one container writer
+  (_write_container) puts either layout into the file, with the GDAL_NODATA tag and the GeoTIFF georeferencing tags of the
+  input **passed through verbatim** (ModelPixelScale 33550, ModelTiepoint 33922, ModelTransformation 34264,
+  GeoKeyDirectory 34735, GeoDoubleParams 34736, GeoAsciiParams 34737, GDAL_METADATA 42112) — the output keeps the
+  input's geotransform and projection byte for byte, which is what ``saveGTiff`` does with ``SetGeoTransform`` /
+  ``SetProjection``.
 
 The LZW codec lives in libmoonsr_hip.so's host code (csrc/host_codecs.cpp).  GDAL is absent here, so the codec and
 container are validated against an independent implementation instead: PIL/libtiff reads what this module writes
@@ -32,7 +34,7 @@ from __future__ import annotations
 import ctypes as C
 import struct
 import zlib
-from typing import Dict, Optional, Tuple
+from typing import Dict, NamedTuple, Optional, Tuple
 
 import numpy as np
 
@@ -109,9 +111,7 @@ def _values(entry, bo: str):
     typ, cnt, raw = entry
     if typ == 2:
         return raw
-    fmt = _TYPE_FMT[typ]
-    vals = struct.unpack(bo + fmt * cnt if len(fmt) == 1 else bo + fmt * cnt, raw)
-    return vals
+    return struct.unpack(bo + _TYPE_FMT[typ] * cnt, raw)
 
 
 def _next_ifd(buf, big: bool, bo: str, off: int) -> int:
@@ -136,24 +136,24 @@ def _overview_ifds(buf, big: bool, bo: str, first: int) -> list:
     return out
 
 
+def _header(path: str):
+    """(memory map, BigTIFF or not, byte order, offset of the first IFD) of a TIFF file."""
+    buf = np.memmap(path, dtype=np.uint8, mode="r")
+    head = bytes(buf[:16])
+    if head[:2] not in (b"II", b"MM"):
+        raise ValueError(f"{path}: not a TIFF file")
+    bo = "<" if head[:2] == b"II" else ">"
+    magic = struct.unpack_from(bo + "H", head, 2)[0]
+    if magic not in (42, 43):
+        raise ValueError(f"{path}: not a TIFF file (magic {magic})")
+    big = magic == 43
+    return buf, big, bo, struct.unpack_from(bo + ("Q" if big else "I"), head, 8 if big else 4)[0]
+
+
 def _open(path: str, overview: int = 0):
     """Header and first IFD of a (Geo)TIFF: (memory map, tag dict, byte order, meta).  No pixel block is touched.
     ``overview=k > 0``: the IFD of the k-th reduced-resolution level instead (read_geotiff)."""
-    buf = np.memmap(path, dtype=np.uint8, mode="r")
-    head = bytes(buf[:16])
-    if head[:2] == b"II":
-        bo = "<"
-    elif head[:2] == b"MM":
-        bo = ">"
-    else:
-        raise ValueError(f"{path}: not a TIFF file")
-    magic = struct.unpack_from(bo + "H", head, 2)[0]
-    if magic == 42:
-        big, ifd = False, struct.unpack_from(bo + "I", head, 4)[0]
-    elif magic == 43:
-        big, ifd = True, struct.unpack_from(bo + "Q", head, 8)[0]
-    else:
-        raise ValueError(f"{path}: not a TIFF file (magic {magic})")
+    buf, big, bo, ifd = _header(path)
     t = _read_ifd(buf, big, bo, ifd)
     if overview:
         levels = _overview_ifds(buf, big, bo, ifd)
@@ -193,17 +193,53 @@ def read_info(path: str) -> dict:
 def overview_shapes(path: str) -> list:
     """``[(rows, cols), ...]`` of the reduced-resolution levels of a file (write_geotiff(overviews=)), level 1 first, from
     the IFDs alone; ``[]`` for a file without any.  ``read_geotiff(overview=k)`` reads level k."""
-    buf = np.memmap(path, dtype=np.uint8, mode="r")
-    head = bytes(buf[:16])
-    if head[:2] not in (b"II", b"MM"):
-        raise ValueError(f"{path}: not a TIFF file")
-    bo = "<" if head[:2] == b"II" else ">"
-    magic = struct.unpack_from(bo + "H", head, 2)[0]
-    if magic not in (42, 43):
-        raise ValueError(f"{path}: not a TIFF file (magic {magic})")
-    big = magic == 43
-    first = struct.unpack_from(bo + ("Q" if big else "I"), head, 8 if big else 4)[0]
+    buf, big, bo, first = _header(path)
     return [(_values(t[257], bo)[0], _values(t[256], bo)[0]) for t in _overview_ifds(buf, big, bo, first)]
+
+
+class _Blocks(NamedTuple):
+    """Where the blocks (strips or tiles) that hold one band of an IFD lie, and what is in them: what both readers need."""
+    bw: int                 # block width and height in pixels (a strip: the raster's width; the last strip may be shorter)
+    bh: int
+    across: int             # blocks in a row of blocks, and rows of blocks
+    down: int
+    tiled: bool
+    offs: tuple             # file offset and byte count of every block of the IFD
+    cnts: tuple
+    plane0: int             # index of the band's first block (a planar file: of its plane)
+    ch: int                 # the band's sample among the ``spp`` samples of a block pixel (a chunky file: every band's)
+    spp: int
+    dt: np.dtype            # the samples as stored, in the file's byte order; their width in bytes and kind "u" / "i" / "f"
+    sb: int
+    kind: str
+    pred: int               # Predictor and Compression tags
+    comp: int
+    rows: int               # the raster
+    cols: int
+
+
+def _block_geometry(t: dict, bo: str, meta: dict, band: int) -> _Blocks:
+    """The _Blocks of band ``band`` (1-based) from the tag dict ``t`` and the ``meta`` of an IFD (_open); ValueError for a band
+    the file does not have."""
+    def val(tag, default=None):
+        return _values(t[tag], bo) if tag in t else default
+
+    rows, cols = meta["shape"]
+    dt = np.dtype(meta["dtype"]).newbyteorder(bo)
+    spp, planar = val(277, (1,))[0], val(284, (1,))[0]
+    if not 1 <= band <= spp:
+        raise ValueError(f"band {band} out of range: the file has {spp}")
+    tiled = 322 in t
+    if tiled:
+        bw, bh = val(322)[0], val(323)[0]
+        offs, cnts = val(324), val(325)
+    else:
+        bw, bh = cols, min(val(278, (rows,))[0], rows)
+        offs, cnts = val(273), val(279)
+    across, down = -(-cols // bw), -(-rows // bh)
+    plane0, ch, chunk_spp = ((band - 1) * across * down, 0, 1) if planar == 2 else (0, band - 1, spp)
+    return _Blocks(bw, bh, across, down, tiled, offs, cnts, plane0, ch, chunk_spp, dt, dt.itemsize, dt.kind,
+                   val(317, (1,))[0], val(259, (1,))[0], rows, cols)
 
 
 def read_geotiff(path: str, band: int = 1, rows: Optional[Tuple[int, int]] = None, decoder: str = "host", device=None,
@@ -238,10 +274,6 @@ def read_geotiff(path: str, band: int = 1, rows: Optional[Tuple[int, int]] = Non
     if isinstance(overview, bool) or not isinstance(overview, (int, np.integer)) or overview < 0:
         raise ValueError(f"overview must be an integer >= 0, got {overview!r}")
     buf, t, bo, meta = _open(path, int(overview))
-
-    def val(tag, default=None):
-        return _values(t[tag], bo) if tag in t else default
-
     nrows, cols = meta["shape"]
     if rows is None:
         r0, r1 = 0, nrows
@@ -249,78 +281,55 @@ def read_geotiff(path: str, band: int = 1, rows: Optional[Tuple[int, int]] = Non
         r0, r1 = int(rows[0]), int(rows[1])
         if not 0 <= r0 < r1 <= nrows:
             raise ValueError(f"{path}: row window ({r0}, {r1}) is not inside the raster's {nrows} rows")
-    rows = nrows
-    spp = val(277, (1,))[0]
-    bps = val(258, (1,))[0]
-    comp = val(259, (1,))[0]
-    pred = val(317, (1,))[0]
-    planar = val(284, (1,))[0]
-    if not 1 <= band <= spp:
-        raise ValueError(f"band {band} out of range: the file has {spp}")
-    dt = np.dtype(meta["dtype"]).newbyteorder(bo)
-    tiled = 322 in t
-    if tiled:
-        bw, bh = val(322)[0], val(323)[0]
-        offs, cnts = val(324), val(325)
-    else:
-        bw, bh = cols, val(278, (rows,))[0]
-        bh = min(bh, rows)
-        offs, cnts = val(273), val(279)
-    across, down = -(-cols // bw), -(-rows // bh)
-    per_plane = across * down
-    chunk_spp = 1 if planar == 2 else spp
-    plane0 = (band - 1) * per_plane if planar == 2 else 0
+    g = _block_geometry(t, bo, meta, band)
+    meta["window"] = (r0, r1)
     if decoder == "device":
-        what = (f"compression {comp} (only LZW, 5, is decoded)" if comp != 5 else
-                f"predictor {pred} (only 1 and 2 are undone)" if pred not in (1, 2) else
+        what = (f"compression {g.comp} (only LZW, 5, is decoded)" if g.comp != 5 else
+                f"predictor {g.pred} (only 1 and 2 are undone)" if g.pred not in (1, 2) else
                 "big-endian samples" if bo == ">" else
-                f"{bps}-bit samples" if bps == 64 else
-                f"chunky multi-band blocks ({spp} samples per pixel)" if chunk_spp != 1 else None)
+                f"{g.sb * 8}-bit samples" if g.sb == 8 else
+                f"chunky multi-band blocks ({g.spp} samples per pixel)" if g.spp != 1 else None)
         if what is not None:
             raise ValueError(f"{path}: decoder='device' does not read {what}; decoder='host' does")
-        out = _read_blocks_device(buf, offs, cnts, plane0, across, bw, bh, tiled, dt.kind, bps // 8, pred, rows, cols, r0, r1,
-                                  device, band_bytes, transfers)
-        meta["window"] = (r0, r1)
+        out = _read_blocks_device(buf, g, r0, r1, device, band_bytes, transfers)
         if not as_tensor and transfers is not None:
             transfers.append(("d2h", out.numel() * 4, "decoded raster"))
         return (out if as_tensor else out.cpu().numpy()), meta
+    dt, native = g.dt, g.dt.newbyteorder("=")
     out = np.empty((r1 - r0, cols), np.float32)
-    for by in range(r0 // bh, -(-r1 // bh)):          # the block rows that intersect [r0, r1)
-        for bx in range(across):
-            i = plane0 + by * across + bx
-            raw = bytes(buf[offs[i]:offs[i] + cnts[i]])
-            h = bh if tiled else min(bh, rows - by * bh)
-            nbytes = h * bw * chunk_spp * (bps // 8)
-            if comp == 1:
+    for by in range(r0 // g.bh, -(-r1 // g.bh)):          # the block rows that intersect [r0, r1)
+        for bx in range(g.across):
+            i = g.plane0 + by * g.across + bx
+            raw = bytes(buf[g.offs[i]:g.offs[i] + g.cnts[i]])
+            h = g.bh if g.tiled else min(g.bh, nrows - by * g.bh)
+            nbytes = h * g.bw * g.spp * g.sb
+            if g.comp == 1:
                 data = np.frombuffer(raw[:nbytes].ljust(nbytes, b"\0"), np.uint8)
-            elif comp == 5:
+            elif g.comp == 5:
                 data = lzw_decode(raw, nbytes)
-            elif comp in (8, 32946):
+            elif g.comp in (8, 32946):
                 data = np.frombuffer(zlib.decompress(raw)[:nbytes].ljust(nbytes, b"\0"), np.uint8)
-            elif comp == 32773:
+            elif g.comp == 32773:
                 data = _packbits_decode(raw, nbytes)
             else:
-                raise ValueError(f"{path}: unsupported compression {comp}")
-            if pred == 3:
+                raise ValueError(f"{path}: unsupported compression {g.comp}")
+            if g.pred == 3:
                 # floating-point predictor: bytes of a row are stored most-significant plane first, byte-differenced
-                b = data.reshape(h, bw * chunk_spp * (bps // 8)).copy()
-                b = np.cumsum(b, axis=1, dtype=np.uint8) if chunk_spp == 1 else _cumsum_stride(b, chunk_spp)
-                nb = bps // 8
-                b = b.reshape(h, nb, bw * chunk_spp).transpose(0, 2, 1)
+                b = data.reshape(h, nbytes // h).copy()
+                b = np.cumsum(b, axis=1, dtype=np.uint8) if g.spp == 1 else _cumsum_stride(b, g.spp)
+                b = b.reshape(h, g.sb, g.bw * g.spp).transpose(0, 2, 1)
                 if bo == "<":
                     b = b[:, :, ::-1]
-                arr = np.ascontiguousarray(b).view(dt).reshape(h, bw, chunk_spp)
+                arr = np.ascontiguousarray(b).view(dt).reshape(h, g.bw, g.spp)
             else:
-                arr = data.view(dt).reshape(h, bw, chunk_spp)
-                if pred == 2:
-                    ut = np.dtype(f"u{bps // 8}")
-                    arr = np.cumsum(arr.astype(dt.newbyteorder("=")).view(ut), axis=1, dtype=ut).view(dt.newbyteorder("="))
-            ch = 0 if planar == 2 else band - 1
-            y0, x0 = by * bh, bx * bw
-            ya, yb = max(y0, r0), min(y0 + h, rows, r1)      # the block's rows inside the window
-            ww = min(bw, cols - x0)
-            out[ya - r0:yb - r0, x0:x0 + ww] = arr[ya - y0:yb - y0, :ww, ch]
-    meta["window"] = (r0, r1)
+                arr = data.view(dt).reshape(h, g.bw, g.spp)
+                if g.pred == 2:
+                    ut = np.dtype(f"u{g.sb}")
+                    arr = np.cumsum(arr.astype(native).view(ut), axis=1, dtype=ut).view(native)
+            y0, x0 = by * g.bh, bx * g.bw
+            ya, yb = max(y0, r0), min(y0 + h, nrows, r1)      # the block's rows inside the window
+            ww = min(g.bw, cols - x0)
+            out[ya - r0:yb - r0, x0:x0 + ww] = arr[ya - y0:yb - y0, :ww, g.ch]
     return out, meta
 
 
@@ -337,20 +346,15 @@ def _rows_per_strip(rows: int, row_bytes: int) -> int:
     return max(1, min(rows, (1 << 16) // max(row_bytes, 1)))
 
 
-def _host_strips(arr: np.ndarray, dt: np.dtype, rps: int, comp: int, predictor: int) -> list:
-    """The strips of ``arr`` encoded on the host: NumPy differencing, then msr_lzw_encode / zlib / nothing."""
-    rows = arr.shape[0]
-    strips = []
-    for s in range(-(-rows // rps)):
-        blk = arr[s * rps:(s + 1) * rps]
-        if predictor == 2:
-            u = blk.view(np.dtype(f"<u{dt.itemsize}"))
-            d = u.copy()
-            d[:, 1:] = u[:, 1:] - u[:, :-1]
-            blk = d
-        raw = np.ascontiguousarray(blk)
-        strips.append(raw.tobytes() if comp == 1 else lzw_encode(raw) if comp == 5 else zlib.compress(raw.tobytes(), 6))
-    return strips
+def _encode_block(blk: np.ndarray, dt: np.dtype, comp: int, predictor: int) -> bytes:
+    """One block of a file — a strip, or a tile padded to its full size — encoded on the host: the horizontal predictor
+    differences every row of it in NumPy, then msr_lzw_encode / zlib / nothing."""
+    if predictor == 2:
+        u = blk.view(np.dtype(f"<u{dt.itemsize}"))
+        blk = u.copy()
+        blk[:, 1:] = u[:, 1:] - u[:, :-1]
+    raw = np.ascontiguousarray(blk)
+    return raw.tobytes() if comp == 1 else lzw_encode(raw) if comp == 5 else zlib.compress(raw.tobytes(), 6)
 
 
 def plan_bands(rows: int, row_bytes: int, rps: int, band_bytes: int) -> list:
@@ -362,33 +366,39 @@ def plan_bands(rows: int, row_bytes: int, rps: int, band_bytes: int) -> list:
     return [(s0, min(s0 + per_band, n_strips)) for s0 in range(0, n_strips, per_band)]
 
 
-def _torch_device(device, what: str = "encoder"):
-    """The CUDA device of the device encoder / decoder, or the RuntimeError of a machine without one."""
+def _torch_device(device, what: str = "encoder", data=None):
+    """The CUDA device of the device encoder / decoder, or the RuntimeError of a machine without one.  ``device`` None: the
+    device of ``data`` where that is a CUDA tensor, else the current one."""
     import torch
     if not torch.cuda.is_available():
         raise RuntimeError(f"moonsuperresolution_amd needs a HIP device (MI355X / gfx950) for {what}='device'; there is no "
                            f"CPU fallback ({what}='host' is the host codec)")
+    if device is None and getattr(data, "is_cuda", False):
+        return data.device
     if device is None:
         return torch.device("cuda", torch.cuda.current_device())
     return torch.device("cuda", device) if isinstance(device, int) else torch.device(device)
 
 
-def _encode_strips_device(buf, offsets, lengths, sample_bytes: int, row_bytes: int, stream=None):
-    """One msr_lzw_encode_strips launch on ``buf``'s device: (dst, dst_off, dst_len) with dst / dst_len device tensors (the
-    slots of capacity n + n // 2 + 1024 at dst_off, a host int64 array; dst_len int32, -1 = the slot was too small).
-    Asynchronous on ``stream`` (default: the current stream); the tensors it returns keep the inputs of the launch alive."""
+def _launch_blocks(who: str, buf, arrays, slots, limit: int, errors, stream, entry: str, call):
+    """The launch of a block codec on ``buf``'s device, all but the library call itself.  The checks: ``arrays`` — offsets,
+    lengths and what else ``slots`` takes, an entry per block — of one length, every block inside ``buf`` and at most
+    ``limit`` bytes long (``errors``: the two ValueError texts).  The output slots: ``slots(lengths, ...)`` gives each block's
+    capacity and slot size, and the slots lie back to back in dst, at dst_off.  The tables on the device (int64
+    src_off | dst_off, int32 src_len | dst_cap), dst, and dst_len with -1 everywhere.  Then ``call(lib, head, tail)``: the entry
+    ``entry`` with the arguments in front of and behind its own, on ``stream`` (default: the current one).  Returns (dst,
+    dst_off, dst_len): dst_off a host int64 array; the tensors keep the inputs of the launch alive."""
     import torch
     lib = _lib.load()
     if not (isinstance(buf, torch.Tensor) and buf.is_cuda and buf.dtype == torch.uint8 and buf.is_contiguous()):
-        raise ValueError("lzw_encode_device needs a contiguous uint8 CUDA tensor")
-    off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
-    ln = np.ascontiguousarray(lengths, dtype=np.int64).reshape(-1)
-    if off.size != ln.size:
-        raise ValueError("offsets and lengths differ in length")
-    if ln.size and (ln.min() < 0 or off.min() < 0 or int((off + ln).max()) > buf.numel() or ln.max() > (1 << 30)):
-        raise ValueError("a strip lies outside the buffer (or is longer than 2^30 bytes)")
-    cap = ln + ln // 2 + 1024
-    dst_off = np.concatenate(([0], np.cumsum(cap)[:-1])).astype(np.int64) if ln.size else np.zeros(0, np.int64)
+        raise ValueError(f"{who} needs a contiguous uint8 CUDA tensor")
+    off, ln, *rest = (np.ascontiguousarray(a, dtype=np.int64).reshape(-1) for a in arrays)
+    if any(a.size != off.size for a in (ln, *rest)):
+        raise ValueError(errors[0])
+    if ln.size and (ln.min() < 0 or off.min() < 0 or int((off + ln).max()) > buf.numel() or ln.max() > limit):
+        raise ValueError(errors[1])
+    cap, slot = slots(ln, *rest)
+    dst_off = np.concatenate(([0], np.cumsum(slot)[:-1])).astype(np.int64) if ln.size else np.zeros(0, np.int64)
     dev = buf.device
     with torch.cuda.device(dev):
         s = torch.cuda.current_stream(dev) if stream is None else stream
@@ -396,15 +406,25 @@ def _encode_strips_device(buf, offsets, lengths, sample_bytes: int, row_bytes: i
             table = torch.from_numpy(np.concatenate([off, dst_off])).to(dev)              # int64: src_off | dst_off
             table32 = torch.from_numpy(np.concatenate([ln, cap]).astype(np.int32)).to(dev)   # int32: src_len | dst_cap
             n = int(ln.size)
-            dst = torch.empty(max(int(cap.sum()), 1), dtype=torch.uint8, device=dev)
+            dst = torch.empty(max(int(slot.sum()), 1), dtype=torch.uint8, device=dev)
             dst_len = torch.full((max(n, 1),), -1, dtype=torch.int32, device=dev)
-            rc = lib.msr_lzw_encode_strips(None, buf.data_ptr(), table.data_ptr(), table32.data_ptr(), n, int(sample_bytes),
-                                           int(row_bytes), dst.data_ptr(), table.data_ptr() + 8 * n,
-                                           table32.data_ptr() + 4 * n, dst_len.data_ptr(), C.c_void_p(s.cuda_stream))
-            _lib.raise_for(lib, None, rc, "msr_lzw_encode_strips")
+            rc = call(lib, (None, buf.data_ptr(), table.data_ptr(), table32.data_ptr(), n),
+                      (dst.data_ptr(), table.data_ptr() + 8 * n, table32.data_ptr() + 4 * n, dst_len.data_ptr(),
+                       C.c_void_p(s.cuda_stream)))
+            _lib.raise_for(lib, None, rc, entry)
             for t in (buf, table, table32):
                 t.record_stream(s)
     return dst, dst_off, dst_len[:n]
+
+
+def _encode_strips_device(buf, offsets, lengths, sample_bytes: int, row_bytes: int, stream=None):
+    """One msr_lzw_encode_strips launch on ``buf``'s device: (dst, dst_off, dst_len) with dst / dst_len device tensors (the
+    slots of capacity n + n // 2 + 1024 at dst_off, a host int64 array; dst_len int32, -1 = the slot was too small).
+    Asynchronous on ``stream`` (default: the current stream); the tensors it returns keep the inputs of the launch alive."""
+    return _launch_blocks(
+        "lzw_encode_device", buf, (offsets, lengths), lambda ln: (ln + ln // 2 + 1024,) * 2, 1 << 30,
+        ("offsets and lengths differ in length", "a strip lies outside the buffer (or is longer than 2^30 bytes)"), stream,
+        "msr_lzw_encode_strips", lambda lib, head, tail: lib.msr_lzw_encode_strips(*head, int(sample_bytes), int(row_bytes), *tail))
 
 
 def _download_strips(dst, dst_off: np.ndarray, dst_len) -> list:
@@ -451,40 +471,21 @@ def lzw_decode_device(buf, offsets, lengths, out_sizes, stream=None, check: bool
     Asynchronous on ``stream`` (default: the current stream) with ``check=False``; with ``check=True`` it waits for the
     lengths and raises ValueError("malformed LZW stream") if one is negative, as the host path does."""
     import torch
-    lib = _lib.load()
-    if not (isinstance(buf, torch.Tensor) and buf.is_cuda and buf.dtype == torch.uint8 and buf.is_contiguous()):
-        raise ValueError("lzw_decode_device needs a contiguous uint8 CUDA tensor")
-    off = np.ascontiguousarray(offsets, dtype=np.int64).reshape(-1)
-    ln = np.ascontiguousarray(lengths, dtype=np.int64).reshape(-1)
-    cap = np.ascontiguousarray(out_sizes, dtype=np.int64).reshape(-1)
-    if not off.size == ln.size == cap.size:
-        raise ValueError("offsets, lengths and out_sizes differ in length")
-    if ln.size and (ln.min() < 0 or off.min() < 0 or int((off + ln).max()) > buf.numel() or ln.max() >= (1 << 31)):
-        raise ValueError("a block lies outside the buffer (or is longer than 2^31 - 1 bytes)")
-    if cap.size and (cap.min() < 0 or cap.max() >= (1 << 31)):
-        raise ValueError("an output size is negative or above 2^31 - 1 bytes")
-    slot = (cap + 15) // 16 * 16
-    dst_off = np.concatenate(([0], np.cumsum(slot)[:-1])).astype(np.int64) if cap.size else np.zeros(0, np.int64)
-    dev = buf.device
-    with torch.cuda.device(dev):
-        s = torch.cuda.current_stream(dev) if stream is None else stream
-        with torch.cuda.stream(s):
-            table = torch.from_numpy(np.concatenate([off, dst_off])).to(dev)                  # int64: src_off | dst_off
-            table32 = torch.from_numpy(np.concatenate([ln, cap]).astype(np.int32)).to(dev)       # int32: src_len | dst_cap
-            n = int(ln.size)
-            dst = torch.empty(max(int(slot.sum()), 1), dtype=torch.uint8, device=dev)
-            dst_len = torch.full((max(n, 1),), -1, dtype=torch.int32, device=dev)
-            rc = lib.msr_lzw_decode_strips(None, buf.data_ptr(), table.data_ptr(), table32.data_ptr(), n, dst.data_ptr(),
-                                           table.data_ptr() + 8 * n, table32.data_ptr() + 4 * n, dst_len.data_ptr(),
-                                           C.c_void_p(s.cuda_stream))
-            _lib.raise_for(lib, None, rc, "msr_lzw_decode_strips")
-            for t in (buf, table, table32):
-                t.record_stream(s)
+
+    def slots(ln, cap):
+        if cap.size and (cap.min() < 0 or cap.max() >= (1 << 31)):
+            raise ValueError("an output size is negative or above 2^31 - 1 bytes")
+        return cap, (cap + 15) // 16 * 16
+
+    dst, dst_off, dst_len = _launch_blocks(
+        "lzw_decode_device", buf, (offsets, lengths, out_sizes), slots, (1 << 31) - 1,
+        ("offsets, lengths and out_sizes differ in length", "a block lies outside the buffer (or is longer than 2^31 - 1 bytes)"),
+        stream, "msr_lzw_decode_strips", lambda lib, head, tail: lib.msr_lzw_decode_strips(*head, *tail))
     if check:
         if stream is not None:
-            torch.cuda.current_stream(dev).wait_stream(stream)
-        _check_decoded(dst_len[:n])
-    return dst, dst_off, dst_len[:n]
+            torch.cuda.current_stream(buf.device).wait_stream(stream)
+        _check_decoded(dst_len)
+    return dst, dst_off, dst_len
 
 
 def _check_decoded(dst_len) -> None:
@@ -500,26 +501,26 @@ def lzw_decode_device_bytes(buf, offsets, lengths, out_sizes, stream=None) -> li
     return [host[o:o + c].tobytes() for o, c in zip(dst_off.tolist(), np.asarray(out_sizes, np.int64).reshape(-1).tolist())]
 
 
-def _read_blocks_device(buf, offs, cnts, plane0: int, across: int, bw: int, bh: int, tiled: bool, kind: str, sb: int,
-                        pred: int, nrows: int, cols: int, r0: int, r1: int, device, band_bytes: int,
-                        transfers: Optional[list] = None):
-    """Raster rows [r0, r1) as a float32 CUDA tensor, decoded on the device band by band (plan_read_bands): gather the band's
-    compressed blocks from the memory map into one host array, upload once, one decode launch, one placement launch into the
-    [r1 - r0, cols] tensor.  Device memory is the output plus about 2.5 x band_bytes (compressed + decoded blocks)."""
+def _read_blocks_device(buf, g: _Blocks, r0: int, r1: int, device, band_bytes: int, transfers: Optional[list] = None):
+    """Raster rows [r0, r1) of the blocks ``g`` of the memory map ``buf`` as a float32 CUDA tensor, decoded on the device band
+    by band (plan_read_bands): gather the band's compressed blocks from the memory map into one host array, upload once, one
+    decode launch, one placement launch into the [r1 - r0, cols] tensor.  Device memory is the output plus about
+    2.5 x band_bytes (compressed + decoded blocks)."""
     import torch
     lib = _lib.load()
     dev = _torch_device(device, "decoder")
-    offs, cnts = np.asarray(offs, np.int64), np.asarray(cnts, np.int64)
+    offs, cnts = np.asarray(g.offs, np.int64), np.asarray(g.cnts, np.int64)
+    across, bw, bh, sb = g.across, g.bw, g.bh, g.sb
     with torch.cuda.device(dev):
         s = torch.cuda.current_stream(dev)
-        out = torch.empty((r1 - r0, cols), dtype=torch.float32, device=dev)
+        out = torch.empty((r1 - r0, g.cols), dtype=torch.float32, device=dev)
         for b0, b1 in plan_read_bands(r0, r1, bh, across * bh * bw * sb, band_bytes):
             by = np.repeat(np.arange(b0, b1, dtype=np.int64), across)
             bx = np.tile(np.arange(across, dtype=np.int64), b1 - b0)
-            idx = plane0 + by * across + bx
+            idx = g.plane0 + by * across + bx
             o = offs[idx]
             c = np.clip(np.minimum(cnts[idx], buf.size - o), 0, None)      # a block that runs past the file's end is cut there
-            h = np.full(idx.size, bh, np.int64) if tiled else np.minimum(bh, nrows - by * bh)
+            h = np.full(idx.size, bh, np.int64) if g.tiled else np.minimum(bh, g.rows - by * bh)
             lo, hi = int(o.min()), int((o + c).max())
             total = int(c.sum())
             # the file's bytes go to pinned memory (the one host copy), from where the upload is one DMA transfer
@@ -545,8 +546,8 @@ def _read_blocks_device(buf, offs, cnts, plane0: int, across: int, bw: int, bh: 
             blk_off = torch.from_numpy(dst_off).to(dev)
             origin = torch.from_numpy(np.concatenate([bx * bw, by * bh]).astype(np.int32)).to(dev)      # x0 | y0
             rc = lib.msr_tiff_blocks_to_f32(None, dst.data_ptr(), blk_off.data_ptr(), origin.data_ptr(), origin.data_ptr() + 4 * n,
-                                            n, int(bw), int(bh), ord(kind), int(sb), int(pred), out.data_ptr(), int(r0),
-                                            int(r1 - r0), int(cols), C.c_void_p(s.cuda_stream))
+                                            n, int(bw), int(bh), ord(g.kind), int(sb), int(g.pred), out.data_ptr(), int(r0),
+                                            int(r1 - r0), int(g.cols), C.c_void_p(s.cuda_stream))
             _lib.raise_for(lib, None, rc, "msr_tiff_blocks_to_f32")
             _check_decoded(dst_len)          # waits for the band: its buffers are free before the next one is gathered
     return out
@@ -578,28 +579,37 @@ def _band_bytes_on_device(data, r0: int, r1: int, dt: np.dtype, dev):
     return out.view(torch.uint8).reshape(-1)
 
 
+def _encode_band_device(blocks, offsets, lengths, sample_bytes: int, row_bytes: int, transfers: Optional[list], kind: str,
+                        raw: Optional[int]) -> list:
+    """The last steps of a band of the device encoder, strips or tiles (``kind``: "strip" / "tile"): ``blocks``, the band laid
+    out block after block as a uint8 device tensor, goes through one launch, compaction and download (lzw_encode_device), and
+    ``transfers`` takes the band's entries; ``raw``: the bytes of the band where it was uploaded from the host, else None."""
+    enc = lzw_encode_device(blocks, offsets, lengths, sample_bytes, row_bytes)
+    if transfers is not None:
+        if raw is not None:
+            transfers.append(("h2d", raw, "raw product band"))
+        # per block: offset and slot (2 x int64), length and capacity (2 x int32) going up, the stream's length coming down
+        transfers.append(("h2d", 24 * len(enc), f"{kind} tables of the encoder"))
+        transfers.append(("d2h", 4 * len(enc), f"encoded {kind} lengths"))
+        transfers.append(("d2h", sum(len(b) for b in enc), f"compressed output {kind}s"))
+    return enc
+
+
 def _device_strips(data, dt: np.dtype, rps: int, predictor: int, device, band_bytes: int,
                    transfers: Optional[list] = None) -> list:
     """The strips of ``data`` LZW-encoded on the device, band by band (plan_bands): upload (or convert) a band, one launch,
     compact, download.  Device memory is bounded by the band: about 2.5 x band_bytes plus 1 KiB per strip."""
     rows, cols = data.shape
     row_bytes = cols * dt.itemsize
-    dev = _torch_device(device)
+    dev = _torch_device(device, data=data)
     strips = []
     for s0, s1 in plan_bands(rows, row_bytes, rps, band_bytes):
         r0, r1 = s0 * rps, min(s1 * rps, rows)
         buf = _band_bytes_on_device(data, r0, r1, dt, dev)
         starts = np.arange(r0, r1, rps, dtype=np.int64)
         lengths = (np.minimum(starts + rps, r1) - starts) * row_bytes
-        band = lzw_encode_device(buf, (starts - r0) * row_bytes, lengths, dt.itemsize if predictor == 2 else 0, row_bytes)
-        if transfers is not None:
-            if isinstance(data, np.ndarray):
-                transfers.append(("h2d", buf.numel(), "raw product band"))
-            # per strip: offset and slot (2 x int64), length and capacity (2 x int32) going up, the stream's length coming down
-            transfers.append(("h2d", 24 * len(band), "strip tables of the encoder"))
-            transfers.append(("d2h", 4 * len(band), "encoded strip lengths"))
-            transfers.append(("d2h", sum(len(s) for s in band), "compressed output strips"))
-        strips += band
+        strips += _encode_band_device(buf, (starts - r0) * row_bytes, lengths, dt.itemsize if predictor == 2 else 0, row_bytes,
+                                      transfers, "strip", buf.numel() if isinstance(data, np.ndarray) else None)
     return strips
 
 
@@ -630,10 +640,9 @@ def encode_strips(data, dtype, rps: int, compress: str = "lzw", predictor: int =
     if data.ndim != 2:
         raise ValueError("Data must be a 2-D array (the reference raises for rank != 2 too, process_full_tiles.py:505-519).")
     if encoder == "device":
-        if device is None and not isinstance(data, np.ndarray) and getattr(data, "is_cuda", False):
-            device = data.device
         return _device_strips(data, dt, rps, predictor, device, band_bytes, transfers)
-    return _host_strips(np.ascontiguousarray(data, dtype=dt), dt, rps, comp, predictor)
+    arr = np.ascontiguousarray(data, dtype=dt)
+    return [_encode_block(arr[r:r + rps], dt, comp, predictor) for r in range(0, arr.shape[0], rps)]
 
 
 def write_strips(path: str, strips: list, shape: Tuple[int, int], dtype, rps: int, meta: Optional[dict] = None,
@@ -714,26 +723,16 @@ def check_layout(tile, overviews, shape: Optional[Tuple[int, int]] = None, dt: O
     return tile, overviews
 
 
-def _encode_block(raw: np.ndarray, comp: int) -> bytes:
-    return raw.tobytes() if comp == 1 else lzw_encode(raw) if comp == 5 else zlib.compress(raw.tobytes(), 6)
-
-
 def _host_tiles(arr: np.ndarray, dt: np.dtype, th: int, tw: int, comp: int, predictor: int) -> list:
-    """The tiles of ``arr`` in row-major order encoded on the host: an edge tile is padded with zero bytes, then the
-    predictor differences every tile row, then msr_lzw_encode / zlib / nothing."""
+    """The tiles of ``arr`` in row-major order encoded on the host (_encode_block), an edge tile padded with zero bytes."""
     rows, cols = arr.shape
     tiles = []
-    for ty in range(-(-rows // th)):
-        for tx in range(-(-cols // tw)):
+    for y in range(0, rows, th):
+        for x in range(0, cols, tw):
             t = np.zeros((th, tw), dt)
-            blk = arr[ty * th:(ty + 1) * th, tx * tw:(tx + 1) * tw]
+            blk = arr[y:y + th, x:x + tw]
             t[:blk.shape[0], :blk.shape[1]] = blk
-            if predictor == 2:
-                u = t.view(np.dtype(f"<u{dt.itemsize}"))
-                d = u.copy()
-                d[:, 1:] = u[:, 1:] - u[:, :-1]
-                t = d
-            tiles.append(_encode_block(np.ascontiguousarray(t), comp))
+            tiles.append(_encode_block(t, dt, comp, predictor))
     return tiles
 
 
@@ -751,15 +750,16 @@ def _host_levels(arr: np.ndarray, dt: np.dtype, tile: Tuple[int, int], overviews
 def _device_levels(data, dt: np.dtype, tile: Tuple[int, int], overviews: int, nodata: Optional[float], predictor: int, device,
                    band_bytes: int, transfers: Optional[list] = None) -> list:
     """_host_levels on the device, with the same bytes.  Every level goes through in bands of whole tile rows of at most
-    ``band_bytes`` raw bytes (one tile row where that is larger): the band's bytes (_band_bytes_on_device for level 0; a
-    view for the others), msr_overview_half of the band into its rows of the next level (a band starts on a multiple of
-    tile_h, an even row, so those rows depend on this band alone), the tile-major arrangement with torch copies (pad, then
-    one permuted copy), one msr_lzw_encode_strips launch with row_bytes = tile_w * sample_bytes, compaction and download.
+    ``band_bytes`` raw bytes (one tile row where that is larger; plan_bands, a tile row counting as a strip of tile_h rows of
+    the padded width): the band's bytes (_band_bytes_on_device for level 0; a view for the others), msr_overview_half of the
+    band into its rows of the next level (a band starts on a multiple of tile_h, an even row, so those rows depend on this
+    band alone), the tile-major arrangement with torch copies (pad, then one permuted copy), then _encode_band_device as for
+    strips: one msr_lzw_encode_strips launch with row_bytes = tile_w * sample_bytes, compaction and download.
     Device memory is about 2.5 x band_bytes plus the next level (a quarter of the one being encoded, so at most a third of
     the raster with the level after it)."""
     import torch
     lib = _lib.load()
-    dev = _torch_device(device)
+    dev = _torch_device(device, data=data)
     th, tw = tile
     sb = dt.itemsize
     bits = getattr(torch, _TORCH_BITS[sb])           # the container of a sample's bits: they are only copied here
@@ -770,12 +770,10 @@ def _device_levels(data, dt: np.dtype, tile: Tuple[int, int], overviews: int, no
         s = torch.cuda.current_stream(dev)
         for k in range(overviews + 1):
             rows, cols = int(cur.shape[0]), int(cur.shape[1])
-            across, down = -(-cols // tw), -(-rows // th)
+            across = -(-cols // tw)
             nxt = torch.empty((-(-rows // 2), -(-cols // 2)), dtype=bits, device=dev) if k < overviews else None
-            per_band = max(1, int(band_bytes) // (th * across * tw * sb))
             blocks = []
-            for t0 in range(0, down, per_band):
-                t1 = min(t0 + per_band, down)
+            for t0, t1 in plan_bands(rows, across * tw * sb, th, band_bytes):
                 r0, r1 = t0 * th, min(t1 * th, rows)
                 if k == 0:
                     band = _band_bytes_on_device(cur, r0, r1, dt, dev).view(bits).reshape(r1 - r0, cols)
@@ -792,17 +790,10 @@ def _device_levels(data, dt: np.dtype, tile: Tuple[int, int], overviews: int, no
                     padded[:r1 - r0, :cols] = band
                     band = padded
                 tiles = band.view(nt, th, across, tw).permute(0, 2, 1, 3).contiguous().view(torch.uint8).reshape(-1)
-                n = nt * across
-                enc = lzw_encode_device(tiles, np.arange(n, dtype=np.int64) * (th * tw * sb), np.full(n, th * tw * sb, np.int64),
-                                        sb if predictor == 2 else 0, tw * sb)
-                if transfers is not None:
-                    if k == 0 and isinstance(data, np.ndarray):
-                        transfers.append(("h2d", (r1 - r0) * cols * sb, "raw product band"))
-                    # per tile: offset and slot (2 x int64), length and capacity (2 x int32) going up, the stream's length down
-                    transfers.append(("h2d", 24 * n, "tile tables of the encoder"))
-                    transfers.append(("d2h", 4 * n, "encoded tile lengths"))
-                    transfers.append(("d2h", sum(len(b) for b in enc), "compressed output tiles"))
-                blocks += enc
+                lengths = np.full(nt * across, th * tw * sb, np.int64)
+                raw = (r1 - r0) * cols * sb if k == 0 and isinstance(data, np.ndarray) else None
+                blocks += _encode_band_device(tiles, np.cumsum(lengths) - lengths, lengths, sb if predictor == 2 else 0, tw * sb,
+                                              transfers, "tile", raw)
             levels.append((rows, cols, blocks))
             cur = nxt
     return levels
@@ -836,17 +827,13 @@ def write_geotiff(path: str, data: np.ndarray, meta: Optional[dict] = None, noda
         raise ValueError("Data must be a 2-D array (the reference raises for rank != 2 too, process_full_tiles.py:505-519).")
     rows, cols = data.shape
     tile, overviews = check_layout(tile, overviews, (rows, cols), dt)
+    rps = None
     if tile is None:
         rps = _rows_per_strip(rows, cols * dt.itemsize)
-        strips = encode_strips(data, dt, rps, compress, predictor, encoder, device, band_bytes, transfers)
-        levels = [(rows, cols, strips)]
+        levels = [(rows, cols, encode_strips(data, dt, rps, compress, predictor, encoder, device, band_bytes, transfers))]
     elif encoder == "device":
-        rps = None
-        if device is None and not isinstance(data, np.ndarray) and getattr(data, "is_cuda", False):
-            device = data.device
         levels = _device_levels(data, dt, tile, overviews, nodata, predictor, device, band_bytes, transfers)
     else:
-        rps = None
         levels = _host_levels(np.ascontiguousarray(data, dtype=dt), dt, tile, overviews, nodata, comp, predictor)
     _write_container(path, levels, dt, rps, tile, comp, predictor, meta, nodata, bigtiff)
 

@@ -49,7 +49,7 @@ import torch
 
 from . import _lib
 from .distributed import halo_zone_rows, patch_grid_1d
-from .tiler import _CARRIED, DEMSuperResolution
+from .tiler import _CARRIED, PRODUCTS, DEMSuperResolution, _need_process_group
 
 
 def batch_schedule(valid_per_band: Sequence[int], batch_size: int) -> List[Tuple[int, int]]:
@@ -439,16 +439,13 @@ class HaloShardedSuperResolution(DEMSuperResolution):
         if sharded:
             raise TypeError(f"processFiles: mode='halo' takes no {sorted(sharded)}")
         from .distributed import all_gather_var_rows, exchange_strip_rows, halo_strip_plan
-        if world > 1:
-            import torch.distributed as dist
-            if not (dist.is_available() and dist.is_initialized()):
-                raise RuntimeError("products='rank0' needs an initialised process group")
+        _need_process_group(world)
         self._load_rank_rows(preprocess, rank, world, mode, swap_dsize)
         slabs, (own_lo, own_hi) = self.processMapHalo(rank=rank, world=world, batching=batching, accumulate=accumulate)
         (h, w), halo = self.dem_shape, self.image_size - self.stride
-        names = ("mean", "std", "good")
+        names = [name for name, _ in PRODUCTS]
         plans = [halo_strip_plan((h, w), np.dtype(dt).itemsize, self.image_size, self.stride, self.tile_size, world)
-                 for dt in (np.float32, np.float32, np.uint16)]
+                 for _, dt in PRODUCTS]
         local = all(p["local"] for p in plans)
         self.products_path = "rank0" if local or world == 1 else "gathered"
         self.handover_rows = {}

@@ -67,6 +67,15 @@ def blend_window(image_size: int) -> np.ndarray:
 
 
 _CARRIED = ("sx", "sy", "mm_sel", "keys", "dmm")     # the compaction's five outputs, in the order of the kernel's arguments
+PRODUCTS = (("mean", np.float32), ("std", np.float32), ("good", np.uint16))     # (name, dtype of its file), in processMap's order
+
+
+def _need_process_group(world: int) -> None:
+    """The rank-local writers gather their strips to rank 0: with more than one rank that takes a process group."""
+    if world > 1:
+        import torch.distributed as dist
+        if not (dist.is_available() and dist.is_initialized()):
+            raise RuntimeError("products='rank0' needs an initialised process group")
 
 
 class DEMSuperResolution:
@@ -299,11 +308,14 @@ class DEMSuperResolution:
             data = data[:, :, 0]
         elif len(data.shape) != 2:
             raise ValueError("Data is of incorrect shape")
+        geotiff.write_geotiff(self._product_path(name), data, getattr(self, "geo_meta", None), nodata=self.no_value,
+                              dtype=out_type, compress="lzw", predictor=2, encoder=self.encoder, device=self.device,
+                              transfers=self.transfers, tile=self.product_tile, overviews=self.overviews)
+
+    def _product_path(self, name: str) -> str:
+        """``<save_path>/<map_name>_<name>.tiff``, its directory made."""
         os.makedirs(self.save_path, exist_ok=True)
-        geotiff.write_geotiff(os.path.join(self.save_path, self.map_name + "_" + name + ".tiff"), data,
-                              getattr(self, "geo_meta", None), nodata=self.no_value, dtype=out_type, compress="lzw",
-                              predictor=2, encoder=self.encoder, device=self.device, transfers=self.transfers,
-                              tile=self.product_tile, overviews=self.overviews)
+        return os.path.join(self.save_path, self.map_name + "_" + name + ".tiff")
 
     def preprocess(self, swap_dsize: bool = True, rows: Optional[Tuple[int, int]] = None) -> None:
         """process_full_tiles.py:226-244: in-fill the ortho (stored in ``self.image`` and, as in the reference, never
@@ -404,9 +416,8 @@ class DEMSuperResolution:
             if preprocess:
                 self.preprocess(swap_dsize=swap_dsize)
             mean, std, good = self.processMap()
-        self.saveGTiff(mean, mean.dtype, "mean")
-        self.saveGTiff(std, std.dtype, "std")
-        self.saveGTiff(good, good.dtype, "good")
+        for (name, _), data in zip(PRODUCTS, (mean, std, good)):
+            self.saveGTiff(data, data.dtype, name)
 
     def _load_rank_rows(self, preprocess: bool, rank: int, world: int, mode: str, swap_dsize: bool = True
                         ) -> Tuple[int, int]:
@@ -455,14 +466,10 @@ class DEMSuperResolution:
             raise ValueError(f"products='rank0' is built for mode='tiles', got mode={mode!r}")
         if sharded:
             raise TypeError(f"processFiles: mode='tiles' takes no {sorted(sharded)}")
-        if world > 1:
-            import torch.distributed as dist
-            if not (dist.is_available() and dist.is_initialized()):
-                raise RuntimeError("products='rank0' needs an initialised process group")
+        _need_process_group(world)
         self._load_rank_rows(preprocess, rank, world, mode, swap_dsize)
         shape, T = self.dem_shape, self.tile_size
-        plans = {name: strip_plan(shape, np.dtype(dt).itemsize, T, world)
-                 for name, dt in (("mean", np.float32), ("std", np.float32), ("good", np.uint16))}
+        plans = {name: strip_plan(shape, np.dtype(dt).itemsize, T, world) for name, dt in PRODUCTS}
         local = world > 1 and not any(p["straddles"] for p in plans.values())
         self.products_path = "rank0" if local or world == 1 else "gathered"
         self.padInputs()
@@ -472,12 +479,12 @@ class DEMSuperResolution:
             mean, std, good = process_map_sharded(shape, T, tiles, self.processTile, rank, world, gather=True,
                                                   device=self.device, as_tensor=self.resident, transfers=self.transfers)
             if rank == 0:
-                for name, data in (("mean", mean), ("std", std), ("good", good)):
+                for (name, _), data in zip(PRODUCTS, (mean, std, good)):
                     self.saveGTiff(data, data.dtype, name)
             return
         mine = process_map_sharded(shape, T, tiles, self.processTile, rank, world, device=self.device, as_tensor=True,
                                    local=True)
-        for name, data in zip(("mean", "std", "good"), mine):
+        for (name, _), data in zip(PRODUCTS, mine):
             r0, r1 = plans[name]["rows"][rank]
             assert tuple(data.shape) == (r1 - r0, shape[1]), (tuple(data.shape), (r0, r1), shape)
             self._encode_gather_write(name, data, plans[name], rank, world)
@@ -489,7 +496,7 @@ class DEMSuperResolution:
         rank 0 writes the file."""
         from . import geotiff
         shape = self.dem_shape
-        dt = np.dtype(np.uint16 if name == "good" else np.float32)
+        dt = np.dtype(dict(PRODUCTS)[name])
         s0, s1 = plan["strips"][rank]
         if self.encoder == "host" and data.numel():
             self._log("d2h", data.numel() * data.element_size(), f"{name} product rows")
@@ -505,9 +512,8 @@ class DEMSuperResolution:
                 strips = [s for part in gathered for s in part]
         if rank == 0:
             assert len(strips) == plan["n_strips"], (len(strips), plan["n_strips"])
-            os.makedirs(self.save_path, exist_ok=True)
-            geotiff.write_strips(os.path.join(self.save_path, self.map_name + "_" + name + ".tiff"), strips, shape, dt,
-                                 plan["rps"], getattr(self, "geo_meta", None), nodata=self.no_value)
+            geotiff.write_strips(self._product_path(name), strips, shape, dt, plan["rps"], getattr(self, "geo_meta", None),
+                                 nodata=self.no_value)
 
     def padInputs(self) -> None:
         """process_full_tiles.py:246-267: no_value canvas ((dim//1024)+1)*1024 + 2(S-s), data at offset (S-s).

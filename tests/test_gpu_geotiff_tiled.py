@@ -5,7 +5,8 @@
      pattern in which every count 0 .. 4 occurs, NaNs and both zeros; float32 without no-data; uint8 and uint16;
   2. the files of write_geotiff(encoder="device", tile=, overviews=) equal the host-encoded files byte for byte: over the shapes,
      dtypes, predictors and tiles of the CPU list, with band_bytes=1 (one tile row per band, several bands) and the default,
-     from a NumPy array and from a CUDA tensor, overviews 0 and 2; a uint8 tensor into a uint16 file;
+     from a NumPy array and from a CUDA tensor, overviews 0 and 2; a uint8 tensor into a uint16 file; and the device encoder
+     and decoder meet the digests pinned in tests/golden/geotiff_bytes.json (strips too; tests/geotiff_pinned_cases.py);
   3. read_geotiff(decoder="device", overview=k) returns the host reader's bits;
   4. the driver: product_tile=(16, 16), overviews=2, encoder="device", resident=True on the smallest raster of
      tests/resident_cases.py — level 0 of each product equals the raster of the strip-layout run, levels 1 and 2 the twin, and
@@ -20,6 +21,7 @@ import torch
 
 from moonsuperresolution_amd import _lib
 from moonsuperresolution_amd import geotiff as G
+from tests import geotiff_pinned_cases as pinned
 from tests import geotiff_tiled_cases as cases
 from tests import resident_cases
 
@@ -120,6 +122,26 @@ def test_cropped_tensor_view_and_strips_unchanged(tmp_path, dev):
     G.write_geotiff(str(tmp_path / "hs.tif"), a, nodata=NV)
     G.write_geotiff(str(tmp_path / "ds.tif"), t, nodata=NV, encoder="device", tile=None, overviews=0)
     assert open(tmp_path / "ds.tif", "rb").read() == open(tmp_path / "hs.tif", "rb").read()
+
+
+@pytest.mark.parametrize("case", pinned.LZW_CASES, ids=[c[0] for c in pinned.LZW_CASES])
+def test_device_codecs_meet_the_pinned_digests(tmp_path, dev, case):
+    """The cases of tests/test_geotiff_bytes_pinned.py (strips and tiles, BigTIFF, a big-endian meta, the nodata spellings)
+    through the device encoder — band_bytes=1 and the default, from an array and from a CUDA tensor — and the device decoder:
+    the digests pinned for the host codecs.  The decoder refuses 64-bit samples, and says so."""
+    want = pinned.pinned()[case[0]]
+    a = np.array(cases.raster(case[1], case[2]))                                # a copy: the shared raster is read-only
+    p = str(tmp_path / "d.tif")
+    for band_bytes in (1, 256 << 20):
+        for data in (a, torch.from_numpy(a).to(dev)):
+            pinned.write(p, case, data, encoder="device", band_bytes=band_bytes)
+            assert pinned.sha(open(p, "rb").read()) == want["file"], (band_bytes, type(data).__name__)
+    if np.dtype(case[4]["dtype"]).itemsize == 8:
+        with pytest.raises(ValueError, match="does not read 64-bit samples"):
+            G.read_geotiff(p, decoder="device")
+    else:
+        assert pinned.digests(p, case, decoder="device") == want
+        assert pinned.digests(p, case, decoder="device", band_bytes=1) == want
 
 
 # ---- 3. reading --------------------------------------------------------------------------------------------------------------
