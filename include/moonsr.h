@@ -400,6 +400,32 @@ int msr_lzw_encode_strips(msr_handle* h, const uint8_t* src_dev, const int64_t* 
                           int32_t n_strips, int32_t sample_bytes, int32_t row_bytes,
                           uint8_t* dst_dev, const int64_t* dst_off_dev, const int32_t* dst_cap_dev, int32_t* dst_len_dev,
                           void* stream);
+/* The same streams for n_blocks blocks (tiles) read IN PLACE from row-major rasters in DEVICE memory, one launch, one block per
+ * one-wave workgroup (grid-stride): no padded frame and no tile-major copy is needed (geotiff.py write_geotiff(layout="cog",
+ * encoder="device")).  A block is block_h rows of block_w_bytes bytes.  Byte q of block i is row y = q / block_w_bytes, column
+ * byte x = q % block_w_bytes: src_dev[blk_off[i] + y * blk_pitch[i] + x] where y < blk_rows[i] and x < blk_wbytes[i] (the
+ * valid part: what of the block lies in the raster), zero elsewhere (the padding of an edge tile).  blk_off is the byte offset
+ * of the block's first sample, blk_pitch the bytes between raster rows of the block's level: it is per block, so blocks of
+ * several levels, each row-major at its own pitch in one allocation, share a launch.  All offset arithmetic is 64-bit.
+ * sample_bytes as above, with the padding in place BEFORE the predictor, which restarts on every block row: the first padding
+ * sample of a row is 0 - the last valid sample.  The stream of block i is msr_lzw_encode of those block_w_bytes * block_h
+ * bytes, byte for byte; dst_off / dst_cap / dst_len as above, and dst_len[i] = -1 too where blk_wbytes[i] is outside
+ * [0, block_w_bytes] or blk_rows[i] outside [0, block_h].  The caller keeps every valid part inside src (geotiff.py checks it
+ * on the host).  All seven arrays are device memory.  h may be NULL.  MSR_ERR_INVALID before any launch, with a message that
+ * names the argument: a null pointer, n_blocks < 0, a sample_bytes outside {0, 1, 2, 4}, a block_w_bytes that is not a positive
+ * multiple of sample_bytes (of 1 for 0), block_h <= 0, a block of more than 2^30 bytes.  n_blocks == 0 is MSR_OK without a
+ * launch.  Asynchronous on `stream`; no allocation. */
+int msr_lzw_encode_blocks(msr_handle* h, const uint8_t* src_dev, const int64_t* blk_off_dev, const int64_t* blk_pitch_dev,
+                          const int32_t* blk_wbytes_dev, const int32_t* blk_rows_dev, int32_t n_blocks, int32_t block_w_bytes,
+                          int32_t block_h, int32_t sample_bytes, uint8_t* dst_dev, const int64_t* dst_off_dev,
+                          const int32_t* dst_cap_dev, int32_t* dst_len_dev, void* stream);
+/* HOST code: the function msr_lzw_encode_blocks runs for one block (csrc/lzw_strip.h: the in-place fetch and the automaton),
+ * run with one lane on host buffers, so that it can be checked against msr_lzw_encode of the padded, differenced block
+ * without a GPU.  The block's first sample is at src.  Returns the stream's length, or -1 when it exceeds cap (no byte at or
+ * beyond dst + cap is written) and for an argument msr_lzw_encode_blocks rejects, a valid part outside the block, or a cap
+ * that is negative or above INT32_MAX. */
+int64_t msr_lzw_encode_block_host(const uint8_t* src, int64_t pitch, int32_t valid_w_bytes, int32_t valid_rows,
+                                  int32_t block_w_bytes, int32_t block_h, int32_t sample_bytes, uint8_t* dst, int64_t cap);
 
 /* The reverse: n_strips independent TIFF LZW blocks (strips or tiles) in DEVICE memory decoded in one launch, one block per
  * one-wave workgroup (csrc/geotiff_codec.hip, csrc/lzw_unstrip.h; geotiff.py read_geotiff(decoder="device")).  Block i is

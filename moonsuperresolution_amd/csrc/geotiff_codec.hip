@@ -1,5 +1,6 @@
 // geotiff_codec.hip — TIFF strips encoded on the device: horizontal predictor + LZW, one strip per one-wave workgroup
-// (msr_lzw_encode_strips, include/moonsr.h; moonsuperresolution_amd/geotiff.py write_geotiff(encoder="device")), and TIFF
+// (msr_lzw_encode_strips, include/moonsr.h; moonsuperresolution_amd/geotiff.py write_geotiff(encoder="device")) or one tile
+// read in place from its raster per workgroup (msr_lzw_encode_blocks; write_geotiff(layout="cog", encoder="device")), and TIFF
 // strips / tiles decoded on the device: LZW, one block per one-wave workgroup (msr_lzw_decode_strips), then predictor,
 // conversion to float32 and placement in the raster window, one block row per wave (msr_tiff_blocks_to_f32;
 // read_geotiff(decoder="device")).
@@ -28,6 +29,26 @@ __global__ __launch_bounds__(64) void lzw_encode_strips_kernel(const uint8_t* __
             len = lzw_encode_strip(&ws, src + src_off[s], n, sample_bytes, row_bytes, dst + dst_off[s], dst_cap[s],
                                    (int)threadIdx.x, 64);
         if (threadIdx.x == 0) dst_len[s] = len;
+    }
+}
+
+// The same, for blocks (tiles) read where they lie in a row-major raster: block b is block_h rows of block_w_bytes bytes whose
+// valid part, blk_rows[b] rows of blk_wbytes[b] bytes at src + blk_off[b] with blk_pitch[b] bytes between rows, is read in
+// place and whose padding is synthesised (lzw_fetch_block).  The pitch is per block, so tiles of several levels share a launch.
+__global__ __launch_bounds__(64) void lzw_encode_blocks_kernel(const uint8_t* __restrict__ src, const int64_t* __restrict__ blk_off,
+                                                               const int64_t* __restrict__ blk_pitch,
+                                                               const int32_t* __restrict__ blk_wbytes,
+                                                               const int32_t* __restrict__ blk_rows, int32_t n_blocks,
+                                                               int32_t block_w_bytes, int32_t block_h, int32_t sample_bytes,
+                                                               uint8_t* __restrict__ dst, const int64_t* __restrict__ dst_off,
+                                                               const int32_t* __restrict__ dst_cap, int32_t* __restrict__ dst_len) {
+    __shared__ LzwWorkspace ws;
+    for (int32_t b = blockIdx.x; b < n_blocks; b += gridDim.x) {
+        const LzwBlock blk = {src + blk_off[b], blk_pitch[b], blk_wbytes[b], blk_rows[b], block_w_bytes};
+        int32_t len = -1;                                      // a valid part that is not inside the block has no stream
+        if (blk.valid_w_bytes >= 0 && blk.valid_w_bytes <= block_w_bytes && blk.valid_rows >= 0 && blk.valid_rows <= block_h)
+            len = lzw_encode_block(&ws, blk, block_h, sample_bytes, dst + dst_off[b], dst_cap[b], (int)threadIdx.x, 64);
+        if (threadIdx.x == 0) dst_len[b] = len;
     }
 }
 
@@ -155,6 +176,33 @@ extern "C" int msr_tiff_blocks_to_f32(msr_handle* h, const uint8_t* src_dev, con
     else if (sample_bytes == 2) MSR_PLACE(2);
     else MSR_PLACE(4);
 #undef MSR_PLACE
+    HIPCHK(h, hipGetLastError());
+    return MSR_OK;
+}
+
+extern "C" int msr_lzw_encode_blocks(msr_handle* h, const uint8_t* src_dev, const int64_t* blk_off_dev, const int64_t* blk_pitch_dev,
+                                     const int32_t* blk_wbytes_dev, const int32_t* blk_rows_dev, int32_t n_blocks,
+                                     int32_t block_w_bytes, int32_t block_h, int32_t sample_bytes, uint8_t* dst_dev,
+                                     const int64_t* dst_off_dev, const int32_t* dst_cap_dev, int32_t* dst_len_dev, void* stream) {
+    const char* null = !src_dev ? "src_dev" : !blk_off_dev ? "blk_off_dev" : !blk_pitch_dev ? "blk_pitch_dev" :
+                       !blk_wbytes_dev ? "blk_wbytes_dev" : !blk_rows_dev ? "blk_rows_dev" : !dst_dev ? "dst_dev" :
+                       !dst_off_dev ? "dst_off_dev" : !dst_cap_dev ? "dst_cap_dev" : !dst_len_dev ? "dst_len_dev" : nullptr;
+    if (null) return fail(h, MSR_ERR_INVALID, "msr_lzw_encode_blocks: null pointer %s", null);
+    if (n_blocks < 0) return fail(h, MSR_ERR_INVALID, "msr_lzw_encode_blocks: n_blocks %d < 0", n_blocks);
+    if (sample_bytes != 0 && sample_bytes != 1 && sample_bytes != 2 && sample_bytes != 4)
+        return fail(h, MSR_ERR_INVALID, "msr_lzw_encode_blocks: sample_bytes %d is not 0, 1, 2 or 4", sample_bytes);
+    if (block_w_bytes <= 0 || (sample_bytes && block_w_bytes % sample_bytes))
+        return fail(h, MSR_ERR_INVALID, "msr_lzw_encode_blocks: block_w_bytes %d is not a positive multiple of sample_bytes %d",
+                    block_w_bytes, sample_bytes);
+    if (block_h <= 0) return fail(h, MSR_ERR_INVALID, "msr_lzw_encode_blocks: block_h %d <= 0", block_h);
+    if ((int64_t)block_w_bytes * block_h > ((int64_t)1 << 30))
+        return fail(h, MSR_ERR_INVALID, "msr_lzw_encode_blocks: block_w_bytes %d x block_h %d is more than 2^30 bytes",
+                    block_w_bytes, block_h);
+    if (n_blocks == 0) return MSR_OK;
+    const int blocks = std::min<int32_t>(n_blocks, 256 * 4);       // four resident per CU, and a tile is long work: one each
+    hipLaunchKernelGGL(lzw_encode_blocks_kernel, dim3(blocks), dim3(64), 0, static_cast<hipStream_t>(stream), src_dev,
+                       blk_off_dev, blk_pitch_dev, blk_wbytes_dev, blk_rows_dev, n_blocks, block_w_bytes, block_h, sample_bytes,
+                       dst_dev, dst_off_dev, dst_cap_dev, dst_len_dev);
     HIPCHK(h, hipGetLastError());
     return MSR_OK;
 }

@@ -2,6 +2,7 @@
 // TIFF 6.0 LZW: MSB-first codes of 9..12 bits, ClearCode 256, EndOfInformation 257, first free code 258, the
 // width grows one code EARLY (at 511 / 1023 / 2047 entries), the table is cleared when it holds 4094 entries.
 #include "../../include/moonsr.h"
+#include "lzw_strip.h"
 #include "lzw_unstrip.h"
 
 #include <cstdint>
@@ -63,6 +64,19 @@ int64_t msr_lzw_decode_strip_host(const uint8_t* in, int64_t n_in, uint8_t* out,
     if (!in || !out || n_in < 0 || cap < 0 || n_in > INT32_MAX || cap > INT32_MAX) return -1;
     static thread_local msr::LzwDecodeWorkspace ws;
     return msr::lzw_decode_strip(&ws, in, (int32_t)n_in, out, (int32_t)cap, 0, 1);
+}
+
+// The block encoder the device runs (lzw_strip.h: lzw_fetch_block + the automaton), with one lane on host buffers: the CPU
+// suite checks it against msr_lzw_encode of the padded, differenced block without a GPU.
+int64_t msr_lzw_encode_block_host(const uint8_t* src, int64_t pitch, int32_t valid_w_bytes, int32_t valid_rows,
+                                  int32_t block_w_bytes, int32_t block_h, int32_t sample_bytes, uint8_t* dst, int64_t cap) {
+    if (!src || !dst || cap < 0 || cap > INT32_MAX || block_w_bytes <= 0 || block_h <= 0) return -1;
+    if (sample_bytes != 0 && sample_bytes != 1 && sample_bytes != 2 && sample_bytes != 4) return -1;
+    if ((sample_bytes && block_w_bytes % sample_bytes) || (int64_t)block_w_bytes * block_h > ((int64_t)1 << 30)) return -1;
+    if (valid_w_bytes < 0 || valid_w_bytes > block_w_bytes || valid_rows < 0 || valid_rows > block_h) return -1;
+    static thread_local msr::LzwWorkspace ws;
+    const msr::LzwBlock blk = {src, pitch, valid_w_bytes, valid_rows, block_w_bytes};
+    return msr::lzw_encode_block(&ws, blk, block_h, sample_bytes, dst, (int32_t)cap, 0, 1);
 }
 
 int64_t msr_lzw_encode(const uint8_t* in, int64_t n_in, uint8_t* out, int64_t cap) {

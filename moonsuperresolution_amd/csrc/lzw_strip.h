@@ -1,6 +1,8 @@
 // lzw_strip.h — the TIFF 6.0 LZW encoder of ONE strip, with the horizontal predictor fused into its input fetch, as one
 // __host__ __device__ function: the kernel of geotiff_codec.hip runs it with the 64 lanes of a one-wave workgroup, a host
-// program can run it with one "lane" (nlanes = 1) under a sanitizer against msr_lzw_encode (host_codecs.cpp).
+// program can run it with one "lane" (nlanes = 1) under a sanitizer against msr_lzw_encode (host_codecs.cpp).  The input is
+// a strip that lies contiguous in memory (lzw_fetch, lzw_encode_strip) or a block — a tile — read where it lies in a
+// row-major raster, its padding synthesised (lzw_fetch_block, lzw_encode_block); the automaton (lzw_encode_stream) is one.
 //
 // The stream is byte for byte msr_lzw_encode's for the same (differenced) bytes: ClearCode first, MSB-first codes of 9..12
 // bits, the width grows when `next` reaches 512 / 1024 / 2048, Clear when it reaches 4095, one more ++next (and width bump)
@@ -82,6 +84,51 @@ LZW_HD inline void lzw_fetch(LzwWorkspace* ws, const uint8_t* src, int32_t n, in
     lzw_sync();
 }
 
+// A block of a row-major raster, read where it lies: byte q of the block is row q / block_w_bytes, column byte
+// q % block_w_bytes; it is src[row * pitch + column] inside the valid part (row < valid_rows, column < valid_w_bytes) and zero
+// elsewhere: the padding of an edge tile, the 4 bytes in front of the block and the tail of the last chunk.  src points at the
+// block's first sample; row * pitch is 64-bit (a block of a 4.2 GB level lies past the 2 GiB and 4 GiB lines).
+struct LzwBlock {
+    const uint8_t* src;
+    int64_t pitch;                            // bytes between raster rows
+    int32_t valid_w_bytes, valid_rows;        // the part of the block that lies in the raster
+    int32_t block_w_bytes;                    // a block row, padding included
+};
+
+LZW_HD inline uint8_t lzw_block_byte(const LzwBlock& b, int64_t q) {
+    if (q < 0) return 0;
+    const uint32_t y = (uint32_t)q / (uint32_t)b.block_w_bytes;                 // q < 2^30 + LZW_CHUNK: 32-bit division
+    const uint32_t x = (uint32_t)q - y * (uint32_t)b.block_w_bytes;
+    return (y < (uint32_t)b.valid_rows && x < (uint32_t)b.valid_w_bytes) ? b.src[(int64_t)y * b.pitch + x] : (uint8_t)0;
+}
+
+// lzw_fetch for a block read in place: bytes [base, base + LZW_CHUNK) of the block into ws->in.  The padding is there before
+// the predictor, which restarts on every block row: the first padding sample of a row is 0 - the last valid sample.  The
+// sample in front of a chunk comes from the same rule (block position q - sample_bytes), not from memory in front of the row.
+LZW_HD inline void lzw_fetch_block(LzwWorkspace* ws, const LzwBlock& blk, int64_t base, int32_t sample_bytes, int lane,
+                                   int nlanes) {
+    for (int i = lane; i < LZW_CHUNK + 4; i += nlanes) ws->raw[i] = lzw_block_byte(blk, base + i - 4);
+    lzw_sync();
+    for (int i = lane; i < LZW_CHUNK; i += nlanes) {
+        const uint8_t* r = ws->raw + 4 + i;
+        uint8_t v = r[0];
+        if (sample_bytes > 0) {
+            const int32_t col = (int32_t)((uint32_t)(base + i) % (uint32_t)blk.block_w_bytes);
+            const int32_t k = col & (sample_bytes - 1);         // byte of the sample; samples never straddle a chunk
+            if (col - k > 0) {
+                uint32_t cur = 0, prev = 0;
+                for (int b = 0; b <= k; ++b) {                  // as in lzw_fetch: bytes 0..k decide byte k
+                    cur |= (uint32_t)r[b - k] << (8 * b);
+                    prev |= (uint32_t)r[b - k - sample_bytes] << (8 * b);
+                }
+                v = (uint8_t)((cur - prev) >> (8 * k));
+            }
+        }
+        ws->in[i] = v;
+    }
+    lzw_sync();
+}
+
 LZW_HD inline void lzw_clear(LzwWorkspace* ws, int lane, int nlanes) {
     for (int i = lane; i < LZW_SLOTS; i += nlanes) ws->tab[i] = LZW_EMPTY;
     lzw_sync();
@@ -95,10 +142,11 @@ LZW_HD inline void lzw_store(const LzwWorkspace* ws, uint8_t* dst, int64_t from,
     lzw_sync();
 }
 
-// Encodes the n bytes at src (n >= 0) to dst[0 .. cap).  Returns the stream's byte count, or -1 when it exceeds cap; no
-// byte at or beyond dst + cap is written either way.  Every lane of the nlanes that call it together gets the same result.
-LZW_HD inline int32_t lzw_encode_strip(LzwWorkspace* ws, const uint8_t* src, int32_t n, int32_t sample_bytes, int32_t row_bytes,
-                                       uint8_t* dst, int32_t cap, int lane, int nlanes) {
+// The automaton: encodes the n bytes (n >= 0) that ``fetch(base)`` puts into ws->in, LZW_CHUNK at a time, to dst[0 .. cap).
+// Returns the stream's byte count, or -1 when it exceeds cap; no byte at or beyond dst + cap is written either way.  Every
+// lane of the nlanes that call it together gets the same result.
+template <class Fetch>
+LZW_HD inline int32_t lzw_encode_stream(LzwWorkspace* ws, int32_t n, Fetch fetch, uint8_t* dst, int32_t cap, int lane, int nlanes) {
     uint64_t bitbuf = 0;
     int nbits = 0, width = 9, next = 258;
     int64_t op = 0, stored = 0;                // bytes produced / bytes handed to lzw_store
@@ -125,7 +173,7 @@ LZW_HD inline int32_t lzw_encode_strip(LzwWorkspace* ws, const uint8_t* src, int
     int cur = 0;
     bool overflow = false;
     for (int64_t base = 0; base < n && !overflow; base += LZW_CHUNK) {
-        lzw_fetch(ws, src, n, base, sample_bytes, row_bytes, lane, nlanes);
+        fetch(base);
         const int m = n - base < LZW_CHUNK ? (int)(n - base) : LZW_CHUNK;
         const uint32_t* in32 = reinterpret_cast<const uint32_t*>(ws->in);
         uint32_t word = lzw_uniform(in32[0]);
@@ -170,6 +218,23 @@ LZW_HD inline int32_t lzw_encode_strip(LzwWorkspace* ws, const uint8_t* src, int
     lzw_store(ws, dst, stored, op, capl, lane, nlanes);
 #undef LZW_PUT
     return op > capl ? -1 : (int32_t)op;
+}
+
+// Encodes the n bytes at src (n >= 0) to dst[0 .. cap): lzw_encode_stream of what lzw_fetch reads.
+LZW_HD inline int32_t lzw_encode_strip(LzwWorkspace* ws, const uint8_t* src, int32_t n, int32_t sample_bytes, int32_t row_bytes,
+                                       uint8_t* dst, int32_t cap, int lane, int nlanes) {
+    return lzw_encode_stream(
+        ws, n, [=](int64_t base) { lzw_fetch(ws, src, n, base, sample_bytes, row_bytes, lane, nlanes); }, dst, cap, lane, nlanes);
+}
+
+// Encodes a block of block_h rows of block_w_bytes bytes read in place from a raster (LzwBlock) to dst[0 .. cap):
+// lzw_encode_stream of what lzw_fetch_block reads, so the stream is lzw_encode_strip's of the padded block laid out contiguous
+// with row_bytes = block_w_bytes.  block_w_bytes * block_h <= 2^30.
+LZW_HD inline int32_t lzw_encode_block(LzwWorkspace* ws, const LzwBlock& blk, int32_t block_h, int32_t sample_bytes, uint8_t* dst,
+                                       int32_t cap, int lane, int nlanes) {
+    return lzw_encode_stream(
+        ws, blk.block_w_bytes * block_h, [=](int64_t base) { lzw_fetch_block(ws, blk, base, sample_bytes, lane, nlanes); }, dst,
+        cap, lane, nlanes);
 }
 
 }  // namespace msr

@@ -18,8 +18,10 @@ and ``_good.tiff`` (UInt16) as LZW GeoTIFFs with ``PREDICTOR=2`` and a nodata ta
   ``overviews=n`` adds n reduced-resolution levels as chained IFDs (GDAL's internal-overview layout), each the 2 x 2
   reduction ``overview_reference`` of the one before.  The blocks of either layout are differenced and encoded one by one
   on the host (default; _encode_block) or, ``encoder="device"``, band by band on the GPU (_encode_band_device:
-  csrc/geotiff_codec.hip, the levels reduced by csrc/tiff_overview.hip) with the same bytes out; one container writer
-  (_write_container) puts either layout into the file, with the GDAL_NODATA tag and the GeoTIFF georeferencing tags of the
+  csrc/geotiff_codec.hip, the levels reduced by csrc/tiff_overview.hip) with the same bytes out; ``layout="cog"`` puts the
+  tiles and IFDs of such a file in the order of a cloud-optimised GeoTIFF (IFDs first, coarse levels before fine ones, every
+  tile framed by its length), and its device encoder reads the tiles where their level lies (_device_levels_in_place); one
+  container writer (_write_container) puts either layout into the file, with the GDAL_NODATA tag and the GeoTIFF georeferencing tags of the
   input **passed through verbatim** (ModelPixelScale 33550, ModelTiepoint 33922, ModelTransformation 34264,
   GeoKeyDirectory 34735, GeoDoubleParams 34736, GeoAsciiParams 34737, GDAL_METADATA 42112) — the output keeps the
   input's geotransform and projection byte for byte, which is what ``saveGTiff`` does with ``SetGeoTransform`` /
@@ -723,6 +725,15 @@ def check_layout(tile, overviews, shape: Optional[Tuple[int, int]] = None, dt: O
     return tile, overviews
 
 
+def check_file_order(layout, tile) -> str:
+    """write_geotiff's ``layout`` checked against its ``tile``: the layout, or the ValueError that names the keyword."""
+    if layout not in ("plain", "cog"):
+        raise ValueError(f"layout must be 'plain' or 'cog', got {layout!r}")
+    if layout == "cog" and tile is None:
+        raise ValueError("layout='cog' needs tile=(tile_h, tile_w): a cloud-optimised file is written in tiles")
+    return layout
+
+
 def _host_tiles(arr: np.ndarray, dt: np.dtype, th: int, tw: int, comp: int, predictor: int) -> list:
     """The tiles of ``arr`` in row-major order encoded on the host (_encode_block), an edge tile padded with zero bytes."""
     rows, cols = arr.shape
@@ -799,10 +810,141 @@ def _device_levels(data, dt: np.dtype, tile: Tuple[int, int], overviews: int, no
     return levels
 
 
+def _encode_blocks_device(buf, offsets, pitches, valid_w_bytes, valid_rows, block_w_bytes: int, block_h: int, sample_bytes: int,
+                          stream=None):
+    """One msr_lzw_encode_blocks launch on ``buf``'s device: block i is ``block_h`` rows of ``block_w_bytes`` bytes whose valid
+    part, ``valid_rows[i]`` rows of ``valid_w_bytes[i]`` bytes, lies at ``buf[offsets[i]]`` with ``pitches[i]`` bytes between rows
+    and is read there; the rest of the block is zero.  What _launch_blocks checks for lengths is checked here for the valid parts:
+    one entry per block in every array, each valid part inside its block and every byte of it inside ``buf``.  Returns (dst,
+    dst_off, dst_len) as _encode_strips_device does, the slots n + n // 2 + 1024 bytes for the n bytes of a block."""
+    import torch
+    lib = _lib.load()
+    if not (isinstance(buf, torch.Tensor) and buf.is_cuda and buf.dtype == torch.uint8 and buf.is_contiguous()):
+        raise ValueError("lzw_encode_blocks_device needs a contiguous uint8 CUDA tensor")
+    off, pitch, wb, vr = (np.ascontiguousarray(a, dtype=np.int64).reshape(-1) for a in (offsets, pitches, valid_w_bytes, valid_rows))
+    if any(a.size != off.size for a in (pitch, wb, vr)):
+        raise ValueError("offsets, pitches, valid_w_bytes and valid_rows differ in length")
+    bw, bh = int(block_w_bytes), int(block_h)
+    if off.size and (wb.min() < 0 or wb.max() > bw or vr.min() < 0 or vr.max() > bh):
+        raise ValueError(f"a valid part is not inside its block of {bh} rows of {bw} bytes")
+    some = (wb > 0) & (vr > 0)                   # a block without a valid byte reads nothing
+    if off.size and (off.min() < 0 or pitch.min() < 0 or
+                     (some.any() and int((off + (vr - 1) * pitch + wb)[some].max()) > buf.numel())):
+        raise ValueError("a block's valid part lies outside the buffer")
+    n = int(off.size)
+    size = bw * bh
+    cap = np.full(n, size + size // 2 + 1024, np.int64)
+    dst_off = np.arange(n, dtype=np.int64) * (size + size // 2 + 1024)
+    dev = buf.device
+    if n == 0:                                   # nothing to launch (and empty tables have no address to hand over)
+        return torch.empty(0, dtype=torch.uint8, device=dev), dst_off, torch.empty(0, dtype=torch.int32, device=dev)
+    with torch.cuda.device(dev):
+        s = torch.cuda.current_stream(dev) if stream is None else stream
+        with torch.cuda.stream(s):
+            table = torch.from_numpy(np.concatenate([off, pitch, dst_off])).to(dev)                  # int64: off | pitch | dst_off
+            table32 = torch.from_numpy(np.concatenate([wb, vr, cap]).astype(np.int32)).to(dev)       # int32: w | rows | dst_cap
+            dst = torch.empty(int(cap.sum()), dtype=torch.uint8, device=dev)
+            dst_len = torch.full((n,), -1, dtype=torch.int32, device=dev)
+            p64, p32 = table.data_ptr(), table32.data_ptr()
+            rc = lib.msr_lzw_encode_blocks(None, buf.data_ptr(), p64, p64 + 8 * n, p32, p32 + 4 * n, n, bw, bh, int(sample_bytes),
+                                           dst.data_ptr(), p64 + 16 * n, p32 + 8 * n, dst_len.data_ptr(), C.c_void_p(s.cuda_stream))
+            _lib.raise_for(lib, None, rc, "msr_lzw_encode_blocks")
+            for t in (buf, table, table32):
+                t.record_stream(s)
+    return dst, dst_off, dst_len[:n]
+
+
+def lzw_encode_blocks_device(buf, offsets, pitches, valid_w_bytes, valid_rows, block_w_bytes: int, block_h: int,
+                             sample_bytes: int = 0, stream=None) -> list:
+    """TIFF LZW streams of blocks (tiles) of ``block_h`` rows of ``block_w_bytes`` bytes read in place from the uint8 CUDA tensor
+    ``buf``, encoded on its device in one launch (msr_lzw_encode_blocks; the arguments: _encode_blocks_device): byte for byte
+    ``lzw_encode`` of each block padded with zero bytes and, with ``sample_bytes`` 1 / 2 / 4, differenced along its rows
+    afterwards.  The pitch is per block, so blocks of several rasters in ``buf`` share the launch."""
+    import torch
+    dst, dst_off, dst_len = _encode_blocks_device(buf, offsets, pitches, valid_w_bytes, valid_rows, block_w_bytes, block_h,
+                                                  sample_bytes, stream)
+    if stream is not None:
+        torch.cuda.current_stream(buf.device).wait_stream(stream)
+    return _download_strips(dst, dst_off, dst_len)
+
+
+def _tile_table(rows: int, cols: int, th: int, tw: int, sb: int, base: int = 0):
+    """The tiles of a [rows, cols] raster of ``sb``-byte samples that lies row-major at byte ``base``, in row-major order, as
+    the arrays of _encode_blocks_device: (offsets, pitches, valid_w_bytes, valid_rows)."""
+    ty, tx = np.meshgrid(np.arange(-(-rows // th), dtype=np.int64), np.arange(-(-cols // tw), dtype=np.int64), indexing="ij")
+    ty, tx = ty.reshape(-1), tx.reshape(-1)
+    pitch = cols * sb
+    return (base + ty * th * pitch + tx * tw * sb, np.full(ty.size, pitch, np.int64), np.minimum(tw, cols - tx * tw) * sb,
+            np.minimum(th, rows - ty * th))
+
+
+def _device_levels_in_place(data, dt: np.dtype, tile: Tuple[int, int], overviews: int, nodata: Optional[float], predictor: int,
+                            device, band_bytes: int, transfers: Optional[list] = None) -> list:
+    """_device_levels for layout="cog", with the same bytes: the tiles are encoded where their level lies
+    (msr_lzw_encode_blocks reads a tile's rows at the level's pitch and makes the padding of an edge tile itself), so there is
+    no zero-padded frame and no tile-major copy.  Level 0 goes through in the bands of _device_levels: the band's bytes
+    (_band_bytes_on_device), msr_overview_half of the band into its rows of level 1, one encode launch on the band, compaction
+    and download.  Levels 1 .. n lie back to back in ONE allocation, each row-major at its own pitch; levels 2 .. n are the
+    chain of msr_overview_half, and the tiles of all of them go through ONE further launch.  A write issues
+    len(plan_bands(level 0)) + (1 if overviews else 0) encode launches.  Device memory is about 2.5 x band_bytes, plus 2.5 x the
+    reduced levels (a third of the raster), which are held and encoded at once."""
+    import torch
+    lib = _lib.load()
+    dev = _torch_device(device, data=data)
+    th, tw = tile
+    sb = dt.itemsize
+    psb = sb if predictor == 2 else 0
+    has_nodata = int(dt.kind == "f" and nodata is not None)
+    shapes = [(int(data.shape[0]), int(data.shape[1]))]
+    for _ in range(overviews):
+        shapes.append((-(-shapes[-1][0] // 2), -(-shapes[-1][1] // 2)))
+    sizes = [(r * c * sb + 15) // 16 * 16 for r, c in shapes[1:]]            # a level starts on a 16-byte boundary
+    bases = [int(b) for b in np.cumsum([0] + sizes[:-1])] if sizes else []
+
+    def encode(buf, table, raw):
+        enc = _download_strips(*_encode_blocks_device(buf, *table, tw * sb, th, psb))
+        if transfers is not None:
+            if raw is not None:
+                transfers.append(("h2d", raw, "raw product band"))
+            # per block: offset, pitch and slot (3 x int64), valid width, valid rows and capacity (3 x int32) going up
+            transfers.append(("h2d", 36 * len(enc), "tile tables of the encoder"))
+            transfers.append(("d2h", 4 * len(enc), "encoded tile lengths"))
+            transfers.append(("d2h", sum(len(b) for b in enc), "compressed output tiles"))
+        return enc
+
+    with torch.cuda.device(dev):
+        s = torch.cuda.current_stream(dev)
+
+        def half(src_ptr, rows, cols, dst_ptr):
+            rc = lib.msr_overview_half(None, src_ptr, rows, cols, ord(dt.kind), sb, has_nodata, float(nodata) if has_nodata else 0.0,
+                                       dst_ptr, C.c_void_p(s.cuda_stream))
+            _lib.raise_for(lib, None, rc, "msr_overview_half")
+
+        pyramid = torch.empty(max(sum(sizes), 1), dtype=torch.uint8, device=dev) if overviews else None
+        rows, cols = shapes[0]
+        level0 = []
+        for t0, t1 in plan_bands(rows, -(-cols // tw) * tw * sb, th, band_bytes):
+            r0, r1 = t0 * th, min(t1 * th, rows)
+            band = _band_bytes_on_device(data, r0, r1, dt, dev)
+            if overviews:            # a band starts on an even row: its rows of level 1 depend on this band alone
+                half(band.data_ptr(), r1 - r0, cols, pyramid.data_ptr() + (r0 // 2) * shapes[1][1] * sb)
+            level0 += encode(band, _tile_table(r1 - r0, cols, th, tw, sb), band.numel() if isinstance(data, np.ndarray) else None)
+        levels = [(rows, cols, level0)]
+        if overviews:
+            for k in range(1, overviews):
+                half(pyramid.data_ptr() + bases[k - 1], shapes[k][0], shapes[k][1], pyramid.data_ptr() + bases[k])
+            tables = [_tile_table(r, c, th, tw, sb, base) for (r, c), base in zip(shapes[1:], bases)]
+            enc = encode(pyramid, tuple(np.concatenate(col) for col in zip(*tables)), None)
+            for (r, c), table in zip(shapes[1:], tables):
+                levels.append((r, c, enc[:table[0].size]))
+                enc = enc[table[0].size:]
+    return levels
+
+
 def write_geotiff(path: str, data: np.ndarray, meta: Optional[dict] = None, nodata: Optional[float] = None,
                   dtype=np.float32, compress: str = "lzw", predictor: int = 2, bigtiff: Optional[bool] = None,
                   encoder: str = "host", device=None, band_bytes: int = 256 << 20, transfers: Optional[list] = None, *,
-                  tile: Optional[Tuple[int, int]] = None, overviews: int = 0) -> None:
+                  tile: Optional[Tuple[int, int]] = None, overviews: int = 0, layout: str = "plain") -> None:
     """Write a single-band GeoTIFF the way saveGTiff does (process_full_tiles.py:481-531): LZW, PREDICTOR=2,
     nodata tag, geotransform / projection taken from ``meta`` (as returned by ``read_geotiff``).
 
@@ -821,38 +963,92 @@ def write_geotiff(path: str, data: np.ndarray, meta: Optional[dict] = None, noda
     File order: header, the tiles of level 0, 1 ... n, then the IFDs in order, each followed by its out-of-line values — GDAL's
     convention for internal overviews.  Both encoders write the same bytes; on the device the levels are reduced there too
     (msr_overview_half; _device_levels).  ``read_geotiff(overview=k)`` reads level k.  With the defaults, None and 0, the file
-    is the one written before these keywords existed."""
+    is the one written before these keywords existed.
+
+    ``layout="cog"`` (needs ``tile``; default "plain": everything above) writes the same tiles, levels and tags in the order of a
+    cloud-optimised GeoTIFF, so that a reader finds all it needs at the front of the file: the header, a 183-byte ASCII block
+    that names the organisation (COG_GHOST) and a zero byte; the IFD of level 0 at offset 192 (BigTIFF: 200) followed by its
+    out-of-line values except TileOffsets / TileByteCounts, then the IFDs of levels 1 .. n in the same way, chained as above; the
+    TileOffsets and TileByteCounts arrays of all levels in IFD order; then the tiles, level n (the smallest) first and level 0
+    last, row-major inside a level, each as its length (4 bytes, little-endian), the payload TileOffsets points at, the
+    payload's last 4 bytes once more, and a pad byte where the next payload would start odd.  These rules restate the file
+    organisation of GDAL's COG driver and are not checked against GDAL here.  Both encoders write the same bytes; on the device
+    the tiles are encoded where their level lies, those of all reduced levels in one launch (_device_levels_in_place), and
+    ``transfers`` gets one "tile tables" entry per encode launch.  ``read_geotiff`` follows the IFD chain and reads either
+    layout."""
     dt, comp, predictor = _checked_format(dtype, compress, predictor, encoder)
     if data.ndim != 2:
         raise ValueError("Data must be a 2-D array (the reference raises for rank != 2 too, process_full_tiles.py:505-519).")
     rows, cols = data.shape
     tile, overviews = check_layout(tile, overviews, (rows, cols), dt)
+    check_file_order(layout, tile)
     rps = None
     if tile is None:
         rps = _rows_per_strip(rows, cols * dt.itemsize)
         levels = [(rows, cols, encode_strips(data, dt, rps, compress, predictor, encoder, device, band_bytes, transfers))]
     elif encoder == "device":
-        levels = _device_levels(data, dt, tile, overviews, nodata, predictor, device, band_bytes, transfers)
+        levels = (_device_levels_in_place if layout == "cog" else _device_levels)(data, dt, tile, overviews, nodata, predictor,
+                                                                                  device, band_bytes, transfers)
     else:
         levels = _host_levels(np.ascontiguousarray(data, dtype=dt), dt, tile, overviews, nodata, comp, predictor)
-    _write_container(path, levels, dt, rps, tile, comp, predictor, meta, nodata, bigtiff)
+    _write_container(path, levels, dt, rps, tile, comp, predictor, meta, nodata, bigtiff, layout)
+
+
+# What a cloud-optimised file says about its own organisation, straight behind the header (write_geotiff(layout="cog")): the
+# first line gives the length of the rest, and the block ends in one space.
+COG_GHOST = (b"GDAL_STRUCTURAL_METADATA_SIZE=000140 bytes\n"
+             b"LAYOUT=IFDS_BEFORE_DATA\nBLOCK_ORDER=ROW_MAJOR\nBLOCK_LEADER=SIZE_AS_UINT4\n"
+             b"BLOCK_TRAILER=LAST_4_BYTES_REPEATED\nKNOWN_INCOMPATIBLE_EDITION=NO\n ")
+
+
+def _pack_ifd(entries: dict, ifd_off: int, big: bool, last: bool, elsewhere: Optional[dict] = None) -> bytes:
+    """The IFD of ``entries`` = {tag: (type, count, raw bytes)} for file offset ``ifd_off``, followed by its out-of-line values on
+    word boundaries.  ``elsewhere`` = {tag: file offset}: out-of-line values the caller writes there, not behind the IFD.  The
+    IFD points to the position behind the values, which is padded to a word boundary, or with ``last`` ends the chain."""
+    off_t = "Q" if big else "I"
+    esz, vsz = (20, 8) if big else (12, 4)
+    tags = sorted(entries)
+    extra_off = ifd_off + (8 if big else 2) + len(tags) * esz + (8 if big else 4)
+    ifd = bytearray(struct.pack("<Q" if big else "<H", len(tags)))
+    extra = bytearray()
+    for tag in tags:
+        typ, cnt, raw = entries[tag]
+        ifd += struct.pack("<HH", tag, typ) + struct.pack("<" + off_t, cnt)
+        if len(raw) <= vsz:
+            ifd += raw.ljust(vsz, b"\0")
+        elif elsewhere and tag in elsewhere:
+            ifd += struct.pack("<" + off_t, elsewhere[tag])
+        else:
+            if len(extra) & 1:
+                extra += b"\0"
+            ifd += struct.pack("<" + off_t, extra_off + len(extra))
+            extra += raw
+    if not last and len(extra) & 1:
+        extra += b"\0"                                           # the next IFD starts on a word boundary
+    ifd += struct.pack("<" + off_t, 0 if last else extra_off + len(extra))
+    return bytes(ifd + extra)
 
 
 def _write_container(path: str, levels: list, dt: np.dtype, rps: Optional[int], tile: Optional[Tuple[int, int]], comp: int,
-                     predictor: int, meta: Optional[dict], nodata: Optional[float], bigtiff: Optional[bool]) -> None:
+                     predictor: int, meta: Optional[dict], nodata: Optional[float], bigtiff: Optional[bool],
+                     layout: str = "plain") -> None:
     """The TIFF around the encoded blocks of ``levels`` = [(rows, cols, blocks), ...], the raster first and then its reduced
-    levels: header, the blocks level after level, then one IFD per level, each followed by its out-of-line values and chained
-    to the next; classic or BigTIFF by size.  The blocks are strips of ``rps`` rows (``tile`` None; one level) or tiles of
+    levels; classic or BigTIFF by size.  The blocks are strips of ``rps`` rows (``tile`` None; one level) or tiles of
     ``tile`` = (tile_h, tile_w) in row-major order.  The first IFD carries the geo tags; the others NewSubfileType = 1; all
-    of them the nodata tag."""
+    of them the nodata tag.  ``layout="plain"``: header, the blocks level after level, then one IFD per level, each followed by
+    its out-of-line values and chained to the next.  ``layout="cog"`` (tiles): header, COG_GHOST and a zero byte, the same IFDs
+    with their values but the offset and count arrays, those arrays in IFD order, then the tiles from the last level to the
+    first, each between its length and a repeat of its last four bytes (write_geotiff)."""
     n_blocks = sum(len(blocks) for _, _, blocks in levels)
     total = sum(len(b) for _, _, blocks in levels for b in blocks)
     geo = dict((meta or {}).get("geo", {}))
-    big = total + 8 * n_blocks * 2 + sum(len(v[2]) for v in geo.values()) + 4096 * len(levels) > 0xFFFF0000
+    cog = layout == "cog"
+    big = (total + 8 * n_blocks * (3 if cog else 2) + sum(len(v[2]) for v in geo.values()) + 4096 * len(levels)
+           + (256 if cog else 0) > 0xFFFF0000)                   # cog: 8 more bytes frame every tile
     if bigtiff is not None:
         big = bool(bigtiff)
     off_t = "Q" if big else "I"
-    esz, vsz = (20, 8) if big else (12, 4)
+    vsz = 8 if big else 4
     pos = 16 if big else 8
     ifds = []
     for k, (rows, cols, blocks) in enumerate(levels):
@@ -876,10 +1072,6 @@ def _write_container(path: str, levels: list, dt: np.dtype, rps: Optional[int], 
         if nodata is not None:
             txt = (repr(float(nodata)) if float(nodata) != int(nodata) else str(int(nodata))).encode() + b"\0"
             entries[GDAL_NODATA] = (2, len(txt), txt)
-        offsets = []
-        for b in blocks:
-            offsets.append(pos)
-            pos += len(b) + (len(b) & 1)
         n = len(blocks)
         if tile is None:
             entries[278] = (4, 1, struct.pack("<I", rps))
@@ -888,45 +1080,67 @@ def _write_container(path: str, levels: list, dt: np.dtype, rps: Optional[int], 
             entries[322] = (4, 1, struct.pack("<I", tile[1]))
             entries[323] = (4, 1, struct.pack("<I", tile[0]))
             tag_off, tag_cnt = 324, 325
-        entries[tag_off] = (16 if big else 4, n, struct.pack("<" + off_t * n, *offsets))
+        entries[tag_off] = (16 if big else 4, n, bytes(vsz * n))     # set below, where the layout has placed the blocks
         entries[tag_cnt] = (16 if big else 4, n, struct.pack("<" + off_t * n, *(len(b) for b in blocks)))
         ifds.append(entries)
-    first_ifd = pos
-    tail = bytearray()
+
+    def place(k: int, frame: int) -> None:
+        """Level k's blocks from ``pos`` on, each on a word boundary with ``frame`` bytes in front and behind."""
+        nonlocal pos
+        offsets = []
+        for b in levels[k][2]:
+            offsets.append(pos + frame)
+            pos += 2 * frame + len(b) + (len(b) & 1)
+        ifds[k][tag_off] = ifds[k][tag_off][:2] + (struct.pack("<" + off_t * len(offsets), *offsets),)
+
+    header = (lambda first: b"II" + (struct.pack("<HHHQ", 43, 8, 0, first) if big else struct.pack("<HI", 42, first)))
+    if not cog:
+        for k in range(len(levels)):
+            place(k, 0)
+        first_ifd = pos
+        tail = bytearray()
+        for k, entries in enumerate(ifds):
+            tail += _pack_ifd(entries, pos, big, k == len(ifds) - 1)
+            pos = first_ifd + len(tail)
+        with open(path, "wb") as f:
+            f.write(header(first_ifd))
+            for _, _, blocks in levels:
+                for b in blocks:
+                    f.write(b)
+                    if len(b) & 1:
+                        f.write(b"\0")
+            f.write(bytes(tail))
+        return
+    # cog.  The size of an IFD and of the values behind it does not depend on the offsets it holds, so the IFDs are laid out
+    # with the arrays of zeros first, then the arrays and the tiles, and packed once the tiles have their places.
+    first_ifd = pos = pos + len(COG_GHOST) + 1
+    ifd_offs, arrays = [], []
     for k, entries in enumerate(ifds):
-        tags = sorted(entries)
-        ifd_off = pos
-        ifd_size = (8 if big else 2) + len(tags) * esz + (8 if big else 4)
-        extra_off = ifd_off + ifd_size
-        ifd = bytearray(struct.pack("<Q" if big else "<H", len(tags)))
-        extra = bytearray()
-        for tag in tags:
-            typ, cnt, raw = entries[tag]
-            ifd += struct.pack("<HH", tag, typ) + struct.pack("<" + off_t, cnt)
-            if len(raw) <= vsz:
-                ifd += raw.ljust(vsz, b"\0")
-            else:
-                if len(extra) & 1:
-                    extra += b"\0"
-                ifd += struct.pack("<" + off_t, extra_off + len(extra))
-                extra += raw
-        last = k == len(ifds) - 1
-        if not last and len(extra) & 1:
-            extra += b"\0"                                       # the next IFD starts on a word boundary
-        pos = extra_off + len(extra)
-        ifd += struct.pack("<" + off_t, 0 if last else pos)
-        tail += ifd + extra
+        ifd_offs.append(pos)
+        later = dict.fromkeys((t for t in (tag_off, tag_cnt) if len(entries[t][2]) > vsz), 0)
+        pos += len(_pack_ifd(entries, pos, big, k == len(ifds) - 1, later))
+        pos += pos & 1
+        arrays.append(later)
+    for k, later in enumerate(arrays):               # the arrays of all levels behind the last IFD, in IFD order
+        for t in later:
+            later[t] = pos
+            pos += len(ifds[k][t][2])
+            pos += pos & 1
+    for k in reversed(range(len(levels))):           # the smallest level first
+        # a tile of 16 x 16 samples or more has a stream of more than 4 bytes: the trailer repeats whole bytes of it
+        assert all(len(b) >= 4 for b in levels[k][2]), "a tile payload under 4 bytes"
+        place(k, 4)
     with open(path, "wb") as f:
-        if big:
-            f.write(b"II" + struct.pack("<HHHQ", 43, 8, 0, first_ifd))
-        else:
-            f.write(b"II" + struct.pack("<HI", 42, first_ifd))
-        for _, _, blocks in levels:
-            for b in blocks:
-                f.write(b)
-                if len(b) & 1:
-                    f.write(b"\0")
-        f.write(bytes(tail))
+        f.write(header(first_ifd) + COG_GHOST + b"\0")
+        for k, (entries, later) in enumerate(zip(ifds, arrays)):
+            ifd = _pack_ifd(entries, ifd_offs[k], big, k == len(ifds) - 1, later)
+            f.write(ifd + b"\0" * (len(ifd) & 1))
+        for k, later in enumerate(arrays):
+            for t in later:
+                f.write(ifds[k][t][2] + b"\0" * (len(ifds[k][t][2]) & 1))
+        for k in reversed(range(len(levels))):
+            for b in levels[k][2]:
+                f.write(struct.pack("<I", len(b)) + b + b[-4:] + b"\0" * (len(b) & 1))
 
 
 def geotransform(meta: dict) -> Optional[Tuple[float, float, float, float, float, float]]:

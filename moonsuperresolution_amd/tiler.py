@@ -112,6 +112,10 @@ class DEMSuperResolution:
             reduced-resolution levels (``overviews`` > 0 needs ``product_tile``); with ``encoder="device"`` the levels are
             reduced and the tiles encoded on the GPU.  The rank-local writer (processFiles(products="rank0")) knows strips
             only and refuses ``product_tile``.
+        product_layout: "plain" (default) or "cog" (needs ``product_tile``) — what saveGTiff hands to geotiff.write_geotiff as
+            ``layout``: the same tiles, levels and tags in the order of a cloud-optimised GeoTIFF, the IFDs first and the
+            coarse levels before the fine ones; with ``encoder="device"`` the tiles are encoded where their level lies, those
+            of all reduced levels in one launch.
 
     ``transfers`` is a diagnostic: a list of ``(direction, bytes, what)``, direction "h2d" or "d2h", to which the driver,
     preprocess.py and geotiff.py append every raster-scale copy they issue themselves (and the per-block bookkeeping of the
@@ -122,9 +126,10 @@ class DEMSuperResolution:
     def __init__(self, config: DSRConfig, model: Callable = lambda x, training=False: x, device: int = 0,
                  as_implemented: bool = True, pipeline: int = 2, range_check: str = "off", encoder: str = "host",
                  decoder: str = "host", infill: str = "host", resident: bool = False,
-                 product_tile: Optional[Tuple[int, int]] = None, overviews: int = 0) -> None:
+                 product_tile: Optional[Tuple[int, int]] = None, overviews: int = 0, product_layout: str = "plain") -> None:
         from . import geotiff
         self.product_tile, self.overviews = geotiff.check_layout(product_tile, overviews)   # saveGTiff: the products' layout
+        self.product_layout = geotiff.check_file_order(product_layout, self.product_tile)
         if not isinstance(resident, bool):
             raise ValueError(f"resident must be a bool, got {resident!r}")
         self.resident = resident                     # where the rasters are held between the stages: HBM, or host memory
@@ -310,7 +315,8 @@ class DEMSuperResolution:
             raise ValueError("Data is of incorrect shape")
         geotiff.write_geotiff(self._product_path(name), data, getattr(self, "geo_meta", None), nodata=self.no_value,
                               dtype=out_type, compress="lzw", predictor=2, encoder=self.encoder, device=self.device,
-                              transfers=self.transfers, tile=self.product_tile, overviews=self.overviews)
+                              transfers=self.transfers, tile=self.product_tile, overviews=self.overviews,
+                              layout=self.product_layout)
 
     def _product_path(self, name: str) -> str:
         """``<save_path>/<map_name>_<name>.tiff``, its directory made."""
