@@ -426,6 +426,34 @@ int msr_lzw_encode_blocks(msr_handle* h, const uint8_t* src_dev, const int64_t* 
  * that is negative or above INT32_MAX. */
 int64_t msr_lzw_encode_block_host(const uint8_t* src, int64_t pitch, int32_t valid_w_bytes, int32_t valid_rows,
                                   int32_t block_w_bytes, int32_t block_h, int32_t sample_bytes, uint8_t* dst, int64_t cap);
+/* The three entries above with the TIFF Predictor tag's value given beside the samples' width: sample_bytes is 1, 2 or 4 and
+ * predictor 1, 2 or 3; row_bytes / block_w_bytes is a positive multiple of sample_bytes whatever the predictor.  Everything not
+ * said here is as above: the arrays, the slots, dst_len, the stream rules, the further argument checks, the return values.
+ * predictor 1: the bytes as they are, byte for byte the entries above with sample_bytes 0.  predictor 2: the horizontal
+ * predictor, byte for byte the entries above with this sample_bytes.  predictor 3: the floating-point predictor of TIFF
+ * Technical Note 3 for little-endian float32 samples, which needs sample_bytes 4.  Every row of w = row_bytes / 4 samples
+ * (every block row, w = block_w_bytes / 4) is regrouped into four planes, the most significant byte of every sample first:
+ * regrouped byte q = p * w + x is T(q) = byte 3 - p of sample x.  Then every byte but the row's first is differenced over the
+ * whole regrouped row, across the plane boundaries: the encoder sees T(0), T(1) - T(0), ..., T(4w - 1) - T(4w - 2) modulo 256
+ * (libtiff's fpDiff with stride 1; geotiff.py fp_predictor_reference is the NumPy twin).  A strip holds whole rows.  In a block
+ * the padding is in place BEFORE the predictor and the predictor restarts on every block row; a sample that does not lie whole
+ * inside the valid part (inside the strip's src_len bytes) is padding, so blk_wbytes is meant to be a multiple of 4; row offsets
+ * are y * blk_pitch in 64-bit.  Rows that start on a 4-byte boundary are read with aligned 32-bit loads, others byte by byte;
+ * the stream is the same.  MSR_ERR_INVALID before any launch, with a message that names the argument, also for a predictor
+ * outside {1, 2, 3}, a sample_bytes outside {1, 2, 4}, and predictor 3 with another sample_bytes than 4;
+ * msr_tiff_encode_block_host returns -1 for these.  The read-side counterpart is the host reader (geotiff.py read_geotiff):
+ * msr_tiff_blocks_to_f32 undoes predictors 1 and 2 only. */
+int msr_tiff_encode_strips(msr_handle* h, const uint8_t* src_dev, const int64_t* src_off_dev, const int32_t* src_len_dev,
+                           int32_t n_strips, int32_t sample_bytes, int32_t predictor, int32_t row_bytes,
+                           uint8_t* dst_dev, const int64_t* dst_off_dev, const int32_t* dst_cap_dev, int32_t* dst_len_dev,
+                           void* stream);
+int msr_tiff_encode_blocks(msr_handle* h, const uint8_t* src_dev, const int64_t* blk_off_dev, const int64_t* blk_pitch_dev,
+                           const int32_t* blk_wbytes_dev, const int32_t* blk_rows_dev, int32_t n_blocks, int32_t block_w_bytes,
+                           int32_t block_h, int32_t sample_bytes, int32_t predictor, uint8_t* dst_dev, const int64_t* dst_off_dev,
+                           const int32_t* dst_cap_dev, int32_t* dst_len_dev, void* stream);
+int64_t msr_tiff_encode_block_host(const uint8_t* src, int64_t pitch, int32_t valid_w_bytes, int32_t valid_rows,
+                                   int32_t block_w_bytes, int32_t block_h, int32_t sample_bytes, int32_t predictor, uint8_t* dst,
+                                   int64_t cap);
 
 /* The reverse: n_strips independent TIFF LZW blocks (strips or tiles) in DEVICE memory decoded in one launch, one block per
  * one-wave workgroup (csrc/geotiff_codec.hip, csrc/lzw_unstrip.h; geotiff.py read_geotiff(decoder="device")).  Block i is

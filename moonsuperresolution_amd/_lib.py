@@ -88,6 +88,11 @@ SYMBOLS = [
     ("msr_lzw_encode_strips", C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     ("msr_lzw_encode_blocks", C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
     ("msr_lzw_encode_block_host", C.c_int64, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, C.c_int64]),
+    ("msr_tiff_encode_strips", C.c_int, [_P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P, _P, _P]),
+    ("msr_tiff_encode_blocks", C.c_int, [_P, _P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P, _P, _P,
+                                         _P, _P]),
+    ("msr_tiff_encode_block_host", C.c_int64, [_P, C.c_int64, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, _P,
+                                               C.c_int64]),
     ("msr_lzw_decode_strips", C.c_int, [_P, _P, _P, _P, C.c_int32, _P, _P, _P, _P, _P]),
     ("msr_tiff_blocks_to_f32", C.c_int, [_P, _P, _P, _P, _P, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32, C.c_int32,
                                          _P, C.c_int32, C.c_int32, C.c_int32, _P]),

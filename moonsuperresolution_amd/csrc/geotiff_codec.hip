@@ -1,6 +1,7 @@
 // geotiff_codec.hip — TIFF strips encoded on the device: horizontal predictor + LZW, one strip per one-wave workgroup
 // (msr_lzw_encode_strips, include/moonsr.h; moonsuperresolution_amd/geotiff.py write_geotiff(encoder="device")) or one tile
-// read in place from its raster per workgroup (msr_lzw_encode_blocks; write_geotiff(layout="cog", encoder="device")), and TIFF
+// read in place from its raster per workgroup (msr_lzw_encode_blocks; write_geotiff(layout="cog", encoder="device")), either
+// with the floating-point predictor instead for float32 samples (msr_tiff_encode_strips / _blocks, predictor 3), and TIFF
 // strips / tiles decoded on the device: LZW, one block per one-wave workgroup (msr_lzw_decode_strips), then predictor,
 // conversion to float32 and placement in the raster window, one block row per wave (msr_tiff_blocks_to_f32;
 // read_geotiff(decoder="device")).
@@ -48,6 +49,39 @@ __global__ __launch_bounds__(64) void lzw_encode_blocks_kernel(const uint8_t* __
         int32_t len = -1;                                      // a valid part that is not inside the block has no stream
         if (blk.valid_w_bytes >= 0 && blk.valid_w_bytes <= block_w_bytes && blk.valid_rows >= 0 && blk.valid_rows <= block_h)
             len = lzw_encode_block(&ws, blk, block_h, sample_bytes, dst + dst_off[b], dst_cap[b], (int)threadIdx.x, 64);
+        if (threadIdx.x == 0) dst_len[b] = len;
+    }
+}
+
+// The two kernels above with the floating-point predictor (PREDICTOR=3, float32 samples; lzw_strip.h lzw_fetch_fp) in place of
+// the horizontal one.  They are kernels of their own, so the code of the two above is what it was before these existed.
+__global__ __launch_bounds__(64) void tiff_encode_strips_fp_kernel(const uint8_t* __restrict__ src, const int64_t* __restrict__ src_off,
+                                                                   const int32_t* __restrict__ src_len, int32_t n_strips,
+                                                                   int32_t row_bytes, uint8_t* __restrict__ dst,
+                                                                   const int64_t* __restrict__ dst_off,
+                                                                   const int32_t* __restrict__ dst_cap, int32_t* __restrict__ dst_len) {
+    __shared__ LzwWorkspace ws;
+    for (int32_t s = blockIdx.x; s < n_strips; s += gridDim.x) {
+        const int32_t n = src_len[s];
+        int32_t len = -1;                                      // a negative length has no stream
+        if (n >= 0) len = lzw_encode_strip_fp(&ws, src + src_off[s], n, row_bytes, dst + dst_off[s], dst_cap[s], (int)threadIdx.x, 64);
+        if (threadIdx.x == 0) dst_len[s] = len;
+    }
+}
+
+__global__ __launch_bounds__(64) void tiff_encode_blocks_fp_kernel(const uint8_t* __restrict__ src, const int64_t* __restrict__ blk_off,
+                                                                   const int64_t* __restrict__ blk_pitch,
+                                                                   const int32_t* __restrict__ blk_wbytes,
+                                                                   const int32_t* __restrict__ blk_rows, int32_t n_blocks,
+                                                                   int32_t block_w_bytes, int32_t block_h, uint8_t* __restrict__ dst,
+                                                                   const int64_t* __restrict__ dst_off,
+                                                                   const int32_t* __restrict__ dst_cap, int32_t* __restrict__ dst_len) {
+    __shared__ LzwWorkspace ws;
+    for (int32_t b = blockIdx.x; b < n_blocks; b += gridDim.x) {
+        const LzwBlock blk = {src + blk_off[b], blk_pitch[b], blk_wbytes[b], blk_rows[b], block_w_bytes};
+        int32_t len = -1;                                      // a valid part that is not inside the block has no stream
+        if (blk.valid_w_bytes >= 0 && blk.valid_w_bytes <= block_w_bytes && blk.valid_rows >= 0 && blk.valid_rows <= block_h)
+            len = lzw_encode_block_fp(&ws, blk, block_h, dst + dst_off[b], dst_cap[b], (int)threadIdx.x, 64);
         if (threadIdx.x == 0) dst_len[b] = len;
     }
 }
@@ -180,49 +214,113 @@ extern "C" int msr_tiff_blocks_to_f32(msr_handle* h, const uint8_t* src_dev, con
     return MSR_OK;
 }
 
+// The checks and the launch of msr_lzw_encode_blocks / msr_tiff_encode_blocks, whose name `who` the messages carry.  fp: the
+// floating-point predictor's kernel (sample_bytes is 4 then); else sample_bytes is msr_lzw_encode_blocks'.
+static int encode_blocks(const char* who, msr_handle* h, const uint8_t* src_dev, const int64_t* blk_off_dev, const int64_t* blk_pitch_dev,
+                         const int32_t* blk_wbytes_dev, const int32_t* blk_rows_dev, int32_t n_blocks, int32_t block_w_bytes,
+                         int32_t block_h, int32_t sample_bytes, bool fp, uint8_t* dst_dev, const int64_t* dst_off_dev,
+                         const int32_t* dst_cap_dev, int32_t* dst_len_dev, void* stream) {
+    const char* null = !src_dev ? "src_dev" : !blk_off_dev ? "blk_off_dev" : !blk_pitch_dev ? "blk_pitch_dev" :
+                       !blk_wbytes_dev ? "blk_wbytes_dev" : !blk_rows_dev ? "blk_rows_dev" : !dst_dev ? "dst_dev" :
+                       !dst_off_dev ? "dst_off_dev" : !dst_cap_dev ? "dst_cap_dev" : !dst_len_dev ? "dst_len_dev" : nullptr;
+    if (null) return fail(h, MSR_ERR_INVALID, "%s: null pointer %s", who, null);
+    if (n_blocks < 0) return fail(h, MSR_ERR_INVALID, "%s: n_blocks %d < 0", who, n_blocks);
+    if (sample_bytes != 0 && sample_bytes != 1 && sample_bytes != 2 && sample_bytes != 4)
+        return fail(h, MSR_ERR_INVALID, "%s: sample_bytes %d is not 0, 1, 2 or 4", who, sample_bytes);
+    if (block_w_bytes <= 0 || (sample_bytes && block_w_bytes % sample_bytes))
+        return fail(h, MSR_ERR_INVALID, "%s: block_w_bytes %d is not a positive multiple of sample_bytes %d", who, block_w_bytes,
+                    sample_bytes);
+    if (block_h <= 0) return fail(h, MSR_ERR_INVALID, "%s: block_h %d <= 0", who, block_h);
+    if ((int64_t)block_w_bytes * block_h > ((int64_t)1 << 30))
+        return fail(h, MSR_ERR_INVALID, "%s: block_w_bytes %d x block_h %d is more than 2^30 bytes", who, block_w_bytes, block_h);
+    if (n_blocks == 0) return MSR_OK;
+    const int blocks = std::min<int32_t>(n_blocks, 256 * 4);       // four resident per CU, and a tile is long work: one each
+    if (fp)
+        hipLaunchKernelGGL(tiff_encode_blocks_fp_kernel, dim3(blocks), dim3(64), 0, static_cast<hipStream_t>(stream), src_dev,
+                           blk_off_dev, blk_pitch_dev, blk_wbytes_dev, blk_rows_dev, n_blocks, block_w_bytes, block_h, dst_dev,
+                           dst_off_dev, dst_cap_dev, dst_len_dev);
+    else
+        hipLaunchKernelGGL(lzw_encode_blocks_kernel, dim3(blocks), dim3(64), 0, static_cast<hipStream_t>(stream), src_dev,
+                           blk_off_dev, blk_pitch_dev, blk_wbytes_dev, blk_rows_dev, n_blocks, block_w_bytes, block_h, sample_bytes,
+                           dst_dev, dst_off_dev, dst_cap_dev, dst_len_dev);
+    HIPCHK(h, hipGetLastError());
+    return MSR_OK;
+}
+
+// The same for msr_lzw_encode_strips / msr_tiff_encode_strips.
+static int encode_strips(const char* who, msr_handle* h, const uint8_t* src_dev, const int64_t* src_off_dev, const int32_t* src_len_dev,
+                         int32_t n_strips, int32_t sample_bytes, bool fp, int32_t row_bytes, uint8_t* dst_dev,
+                         const int64_t* dst_off_dev, const int32_t* dst_cap_dev, int32_t* dst_len_dev, void* stream) {
+    if (!src_dev || !src_off_dev || !src_len_dev || !dst_dev || !dst_off_dev || !dst_cap_dev || !dst_len_dev)
+        return fail(h, MSR_ERR_INVALID, "%s: null pointer", who);
+    if (n_strips < 0) return fail(h, MSR_ERR_INVALID, "%s: n_strips %d < 0", who, n_strips);
+    if (sample_bytes != 0 && sample_bytes != 1 && sample_bytes != 2 && sample_bytes != 4)
+        return fail(h, MSR_ERR_INVALID, "%s: sample_bytes %d is not 0, 1, 2 or 4", who, sample_bytes);
+    if (sample_bytes && (row_bytes <= 0 || row_bytes % sample_bytes))
+        return fail(h, MSR_ERR_INVALID, "%s: row_bytes %d is not a positive multiple of sample_bytes %d", who, row_bytes,
+                    sample_bytes);
+    if (n_strips == 0) return MSR_OK;
+    const int blocks = std::min<int32_t>(n_strips, 256 * 4 * 4);   // four resident per CU; short strips leave early
+    if (fp)
+        hipLaunchKernelGGL(tiff_encode_strips_fp_kernel, dim3(blocks), dim3(64), 0, static_cast<hipStream_t>(stream), src_dev,
+                           src_off_dev, src_len_dev, n_strips, row_bytes, dst_dev, dst_off_dev, dst_cap_dev, dst_len_dev);
+    else
+        hipLaunchKernelGGL(lzw_encode_strips_kernel, dim3(blocks), dim3(64), 0, static_cast<hipStream_t>(stream), src_dev,
+                           src_off_dev, src_len_dev, n_strips, sample_bytes, row_bytes, dst_dev, dst_off_dev, dst_cap_dev,
+                           dst_len_dev);
+    HIPCHK(h, hipGetLastError());
+    return MSR_OK;
+}
+
+// What the two msr_tiff_encode_* entries check of their own before anything else: 0, or the failure.
+static int check_predictor(const char* who, msr_handle* h, int32_t sample_bytes, int32_t predictor) {
+    if (predictor != 1 && predictor != 2 && predictor != 3)
+        return fail(h, MSR_ERR_INVALID, "%s: predictor %d is not 1, 2 or 3", who, predictor);
+    if (sample_bytes != 1 && sample_bytes != 2 && sample_bytes != 4)
+        return fail(h, MSR_ERR_INVALID, "%s: sample_bytes %d is not 1, 2 or 4", who, sample_bytes);
+    if (predictor == 3 && sample_bytes != 4)
+        return fail(h, MSR_ERR_INVALID, "%s: sample_bytes %d with predictor 3, which is built for 4 (float32)", who, sample_bytes);
+    return MSR_OK;
+}
+
 extern "C" int msr_lzw_encode_blocks(msr_handle* h, const uint8_t* src_dev, const int64_t* blk_off_dev, const int64_t* blk_pitch_dev,
                                      const int32_t* blk_wbytes_dev, const int32_t* blk_rows_dev, int32_t n_blocks,
                                      int32_t block_w_bytes, int32_t block_h, int32_t sample_bytes, uint8_t* dst_dev,
                                      const int64_t* dst_off_dev, const int32_t* dst_cap_dev, int32_t* dst_len_dev, void* stream) {
-    const char* null = !src_dev ? "src_dev" : !blk_off_dev ? "blk_off_dev" : !blk_pitch_dev ? "blk_pitch_dev" :
-                       !blk_wbytes_dev ? "blk_wbytes_dev" : !blk_rows_dev ? "blk_rows_dev" : !dst_dev ? "dst_dev" :
-                       !dst_off_dev ? "dst_off_dev" : !dst_cap_dev ? "dst_cap_dev" : !dst_len_dev ? "dst_len_dev" : nullptr;
-    if (null) return fail(h, MSR_ERR_INVALID, "msr_lzw_encode_blocks: null pointer %s", null);
-    if (n_blocks < 0) return fail(h, MSR_ERR_INVALID, "msr_lzw_encode_blocks: n_blocks %d < 0", n_blocks);
-    if (sample_bytes != 0 && sample_bytes != 1 && sample_bytes != 2 && sample_bytes != 4)
-        return fail(h, MSR_ERR_INVALID, "msr_lzw_encode_blocks: sample_bytes %d is not 0, 1, 2 or 4", sample_bytes);
-    if (block_w_bytes <= 0 || (sample_bytes && block_w_bytes % sample_bytes))
-        return fail(h, MSR_ERR_INVALID, "msr_lzw_encode_blocks: block_w_bytes %d is not a positive multiple of sample_bytes %d",
-                    block_w_bytes, sample_bytes);
-    if (block_h <= 0) return fail(h, MSR_ERR_INVALID, "msr_lzw_encode_blocks: block_h %d <= 0", block_h);
-    if ((int64_t)block_w_bytes * block_h > ((int64_t)1 << 30))
-        return fail(h, MSR_ERR_INVALID, "msr_lzw_encode_blocks: block_w_bytes %d x block_h %d is more than 2^30 bytes",
-                    block_w_bytes, block_h);
-    if (n_blocks == 0) return MSR_OK;
-    const int blocks = std::min<int32_t>(n_blocks, 256 * 4);       // four resident per CU, and a tile is long work: one each
-    hipLaunchKernelGGL(lzw_encode_blocks_kernel, dim3(blocks), dim3(64), 0, static_cast<hipStream_t>(stream), src_dev,
-                       blk_off_dev, blk_pitch_dev, blk_wbytes_dev, blk_rows_dev, n_blocks, block_w_bytes, block_h, sample_bytes,
-                       dst_dev, dst_off_dev, dst_cap_dev, dst_len_dev);
-    HIPCHK(h, hipGetLastError());
-    return MSR_OK;
+    return encode_blocks("msr_lzw_encode_blocks", h, src_dev, blk_off_dev, blk_pitch_dev, blk_wbytes_dev, blk_rows_dev, n_blocks,
+                         block_w_bytes, block_h, sample_bytes, false, dst_dev, dst_off_dev, dst_cap_dev, dst_len_dev, stream);
+}
+
+extern "C" int msr_tiff_encode_blocks(msr_handle* h, const uint8_t* src_dev, const int64_t* blk_off_dev, const int64_t* blk_pitch_dev,
+                                      const int32_t* blk_wbytes_dev, const int32_t* blk_rows_dev, int32_t n_blocks,
+                                      int32_t block_w_bytes, int32_t block_h, int32_t sample_bytes, int32_t predictor,
+                                      uint8_t* dst_dev, const int64_t* dst_off_dev, const int32_t* dst_cap_dev, int32_t* dst_len_dev,
+                                      void* stream) {
+    const char* who = "msr_tiff_encode_blocks";
+    if (const int rc = check_predictor(who, h, sample_bytes, predictor)) return rc;
+    if (block_w_bytes <= 0 || block_w_bytes % sample_bytes)         // of the samples' width with predictor 1 as well
+        return fail(h, MSR_ERR_INVALID, "%s: block_w_bytes %d is not a positive multiple of sample_bytes %d", who, block_w_bytes,
+                    sample_bytes);
+    return encode_blocks(who, h, src_dev, blk_off_dev, blk_pitch_dev, blk_wbytes_dev, blk_rows_dev, n_blocks, block_w_bytes,
+                         block_h, predictor == 1 ? 0 : sample_bytes, predictor == 3, dst_dev, dst_off_dev, dst_cap_dev, dst_len_dev,
+                         stream);
 }
 
 extern "C" int msr_lzw_encode_strips(msr_handle* h, const uint8_t* src_dev, const int64_t* src_off_dev, const int32_t* src_len_dev,
                                      int32_t n_strips, int32_t sample_bytes, int32_t row_bytes, uint8_t* dst_dev,
                                      const int64_t* dst_off_dev, const int32_t* dst_cap_dev, int32_t* dst_len_dev, void* stream) {
-    if (!src_dev || !src_off_dev || !src_len_dev || !dst_dev || !dst_off_dev || !dst_cap_dev || !dst_len_dev)
-        return fail(h, MSR_ERR_INVALID, "msr_lzw_encode_strips: null pointer");
-    if (n_strips < 0) return fail(h, MSR_ERR_INVALID, "msr_lzw_encode_strips: n_strips %d < 0", n_strips);
-    if (sample_bytes != 0 && sample_bytes != 1 && sample_bytes != 2 && sample_bytes != 4)
-        return fail(h, MSR_ERR_INVALID, "msr_lzw_encode_strips: sample_bytes %d is not 0, 1, 2 or 4", sample_bytes);
-    if (sample_bytes && (row_bytes <= 0 || row_bytes % sample_bytes))
-        return fail(h, MSR_ERR_INVALID, "msr_lzw_encode_strips: row_bytes %d is not a positive multiple of sample_bytes %d",
-                    row_bytes, sample_bytes);
-    if (n_strips == 0) return MSR_OK;
-    const int blocks = std::min<int32_t>(n_strips, 256 * 4 * 4);   // four resident per CU; short strips leave early
-    hipLaunchKernelGGL(lzw_encode_strips_kernel, dim3(blocks), dim3(64), 0, static_cast<hipStream_t>(stream), src_dev,
-                       src_off_dev, src_len_dev, n_strips, sample_bytes, row_bytes, dst_dev, dst_off_dev, dst_cap_dev,
-                       dst_len_dev);
-    HIPCHK(h, hipGetLastError());
-    return MSR_OK;
+    return encode_strips("msr_lzw_encode_strips", h, src_dev, src_off_dev, src_len_dev, n_strips, sample_bytes, false, row_bytes,
+                         dst_dev, dst_off_dev, dst_cap_dev, dst_len_dev, stream);
+}
+
+extern "C" int msr_tiff_encode_strips(msr_handle* h, const uint8_t* src_dev, const int64_t* src_off_dev, const int32_t* src_len_dev,
+                                      int32_t n_strips, int32_t sample_bytes, int32_t predictor, int32_t row_bytes, uint8_t* dst_dev,
+                                      const int64_t* dst_off_dev, const int32_t* dst_cap_dev, int32_t* dst_len_dev, void* stream) {
+    const char* who = "msr_tiff_encode_strips";
+    if (const int rc = check_predictor(who, h, sample_bytes, predictor)) return rc;
+    if (row_bytes <= 0 || row_bytes % sample_bytes)                 // of the samples' width with predictor 1 as well
+        return fail(h, MSR_ERR_INVALID, "%s: row_bytes %d is not a positive multiple of sample_bytes %d", who, row_bytes,
+                    sample_bytes);
+    return encode_strips(who, h, src_dev, src_off_dev, src_len_dev, n_strips, predictor == 1 ? 0 : sample_bytes, predictor == 3,
+                         row_bytes, dst_dev, dst_off_dev, dst_cap_dev, dst_len_dev, stream);
 }

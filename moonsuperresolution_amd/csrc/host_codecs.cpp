@@ -79,6 +79,24 @@ int64_t msr_lzw_encode_block_host(const uint8_t* src, int64_t pitch, int32_t val
     return msr::lzw_encode_block(&ws, blk, block_h, sample_bytes, dst, (int32_t)cap, 0, 1);
 }
 
+// The same with an explicit predictor: 1 and 2 are msr_lzw_encode_block_host with sample_bytes 0 and sample_bytes; 3 is the
+// block encoder of the floating-point predictor (lzw_strip.h: lzw_fetch_fp + the automaton) with one lane.
+int64_t msr_tiff_encode_block_host(const uint8_t* src, int64_t pitch, int32_t valid_w_bytes, int32_t valid_rows,
+                                   int32_t block_w_bytes, int32_t block_h, int32_t sample_bytes, int32_t predictor, uint8_t* dst,
+                                   int64_t cap) {
+    if (predictor < 1 || predictor > 3 || (sample_bytes != 1 && sample_bytes != 2 && sample_bytes != 4)) return -1;
+    if (block_w_bytes <= 0 || block_w_bytes % sample_bytes) return -1;
+    if (predictor != 3)
+        return msr_lzw_encode_block_host(src, pitch, valid_w_bytes, valid_rows, block_w_bytes, block_h,
+                                         predictor == 2 ? sample_bytes : 0, dst, cap);
+    if (sample_bytes != 4) return -1;
+    if (!src || !dst || cap < 0 || cap > INT32_MAX || block_h <= 0 || (int64_t)block_w_bytes * block_h > ((int64_t)1 << 30)) return -1;
+    if (valid_w_bytes < 0 || valid_w_bytes > block_w_bytes || valid_rows < 0 || valid_rows > block_h) return -1;
+    static thread_local msr::LzwWorkspace ws;
+    const msr::LzwBlock blk = {src, pitch, valid_w_bytes, valid_rows, block_w_bytes};
+    return msr::lzw_encode_block_fp(&ws, blk, block_h, dst, (int32_t)cap, 0, 1);
+}
+
 int64_t msr_lzw_encode(const uint8_t* in, int64_t n_in, uint8_t* out, int64_t cap) {
     if (!in || !out || n_in < 0 || cap < 8) return -1;
     // trie over (prefix code, byte): child / sibling lists

@@ -3,6 +3,8 @@
 // program can run it with one "lane" (nlanes = 1) under a sanitizer against msr_lzw_encode (host_codecs.cpp).  The input is
 // a strip that lies contiguous in memory (lzw_fetch, lzw_encode_strip) or a block — a tile — read where it lies in a
 // row-major raster, its padding synthesised (lzw_fetch_block, lzw_encode_block); the automaton (lzw_encode_stream) is one.
+// For float32 samples either input can go through the floating-point predictor instead (lzw_fetch_fp, lzw_encode_strip_fp,
+// lzw_encode_block_fp).
 //
 // The stream is byte for byte msr_lzw_encode's for the same (differenced) bytes: ClearCode first, MSB-first codes of 9..12
 // bits, the width grows when `next` reaches 512 / 1024 / 2048, Clear when it reaches 4095, one more ++next (and width bump)
@@ -129,6 +131,54 @@ LZW_HD inline void lzw_fetch_block(LzwWorkspace* ws, const LzwBlock& blk, int64_
     lzw_sync();
 }
 
+// ---- the floating-point predictor (PREDICTOR=3, TIFF Technical Note 3) for float32 samples ------------------------------------
+// A row of w samples (row_bytes = 4 w) is regrouped into four planes, the most significant byte of every sample first:
+// regrouped byte q = p * w + x is T(q) = byte 3 - p of (little-endian) sample x.  The regrouped row is then byte-differenced
+// from end to end, across the plane boundaries: output byte q is T(q) - T(q - 1) for q > 0 and T(0) for q = 0 (libtiff's
+// fpDiff with stride 1).  Consecutive q of a plane read the same byte of consecutive samples, so the fetch is not contiguous
+// and ws->raw with its "4 bytes in front" is not used: T(q - 1) comes from the same rule.
+
+// Sample x of a row that begins at `row`.  A row on a 4-byte boundary is read with one aligned load per sample, the byte
+// extracted by the caller; any other row byte by byte.
+LZW_HD inline uint32_t lzw_fp_sample(const uint8_t* row, uint32_t x, bool aligned) {
+    const uint8_t* s = row + 4 * (int64_t)x;
+    if (aligned) return *reinterpret_cast<const uint32_t*>(s);
+    return (uint32_t)s[0] | (uint32_t)s[1] << 8 | (uint32_t)s[2] << 16 | (uint32_t)s[3] << 24;
+}
+
+// Output bytes [base, base + LZW_CHUNK) of the predictor into ws->in, zero past n, for a raster of rows of row_bytes bytes (a
+// multiple of 4) whose sample x of row r is ``sample(r, x)``.  A lane takes runs of four consecutive output bytes: one division
+// finds the position (row, plane, sample) of the byte in front of its run, the rest is stepping, so a chunk boundary inside a
+// plane, a plane boundary inside a chunk and a row restart are all the same step.  base + LZW_CHUNK < 2^31 + LZW_CHUNK.
+template <class Sample>
+LZW_HD inline void lzw_fetch_fp(LzwWorkspace* ws, int32_t n, int64_t base, int32_t row_bytes, Sample sample, int lane, int nlanes) {
+    const uint32_t w = (uint32_t)row_bytes >> 2;
+    uint32_t* in32 = reinterpret_cast<uint32_t*>(ws->in);
+    lzw_sync();                                                  // the automaton has read the chunk before: ws->in is free
+    for (int i = 4 * lane; i < LZW_CHUNK; i += 4 * nlanes) {
+        const uint32_t g = (uint32_t)(base + i);                 // the run's first byte, counted from the strip's start
+        uint32_t r = 0, p = 0, x = 0, prev = 0;
+        if (g > 0 && g < (uint32_t)n) {                          // the byte in front of the run, then one step
+            r = (g - 1) / (uint32_t)row_bytes;
+            const uint32_t q = (g - 1) - r * (uint32_t)row_bytes;
+            p = q / w;
+            x = q - p * w;
+            prev = (sample(r, x) >> (8 * (3 - p))) & 0xFF;
+            if (++x == w) { x = 0; if (++p == 4) { p = 0; ++r; } }
+        }
+        uint32_t out = 0;
+        for (int j = 0; j < 4; ++j) {
+            if (g + j >= (uint32_t)n) break;                     // zero past n
+            const uint32_t cur = (sample(r, x) >> (8 * (3 - p))) & 0xFF;
+            out |= (((p | x) ? cur - prev : cur) & 0xFF) << (8 * j);     // the first byte of a row passes through
+            prev = cur;
+            if (++x == w) { x = 0; if (++p == 4) { p = 0; ++r; } }
+        }
+        in32[i >> 2] = out;
+    }
+    lzw_sync();
+}
+
 LZW_HD inline void lzw_clear(LzwWorkspace* ws, int lane, int nlanes) {
     for (int i = lane; i < LZW_SLOTS; i += nlanes) ws->tab[i] = LZW_EMPTY;
     lzw_sync();
@@ -235,6 +285,35 @@ LZW_HD inline int32_t lzw_encode_block(LzwWorkspace* ws, const LzwBlock& blk, in
     return lzw_encode_stream(
         ws, blk.block_w_bytes * block_h, [=](int64_t base) { lzw_fetch_block(ws, blk, base, sample_bytes, lane, nlanes); }, dst,
         cap, lane, nlanes);
+}
+
+// lzw_encode_strip with the floating-point predictor (lzw_fetch_fp): the n bytes at src are whole rows of row_bytes bytes of
+// float32 samples, row_bytes a positive multiple of 4; a sample that does not lie whole inside the n bytes counts as zero.
+LZW_HD inline int32_t lzw_encode_strip_fp(LzwWorkspace* ws, const uint8_t* src, int32_t n, int32_t row_bytes, uint8_t* dst,
+                                          int32_t cap, int lane, int nlanes) {
+    const bool aligned = (reinterpret_cast<uintptr_t>(src) & 3) == 0;       // of every row: row_bytes is a multiple of 4
+    const auto sample = [=](uint32_t r, uint32_t x) -> uint32_t {
+        const int64_t row = (int64_t)r * row_bytes;
+        return row + 4 * (int64_t)x + 4 <= n ? lzw_fp_sample(src + row, x, aligned) : 0u;
+    };
+    return lzw_encode_stream(
+        ws, n, [=](int64_t base) { lzw_fetch_fp(ws, n, base, row_bytes, sample, lane, nlanes); }, dst, cap, lane, nlanes);
+}
+
+// lzw_encode_block with the floating-point predictor: LzwBlock's geometry with block_w_bytes a positive multiple of 4.  A
+// sample is zero unless it lies whole inside the valid part: the padding is in place before the predictor, which restarts on
+// every block row; row offsets are y * pitch in 64-bit.  The stream is lzw_encode_strip_fp's of the padded block laid out
+// contiguous with row_bytes = block_w_bytes.
+LZW_HD inline int32_t lzw_encode_block_fp(LzwWorkspace* ws, const LzwBlock& blk, int32_t block_h, uint8_t* dst, int32_t cap,
+                                          int lane, int nlanes) {
+    const bool aligned = ((reinterpret_cast<uintptr_t>(blk.src) | (uint64_t)blk.pitch) & 3) == 0;
+    const auto sample = [=](uint32_t y, uint32_t x) -> uint32_t {
+        return (y < (uint32_t)blk.valid_rows && 4 * (int64_t)x + 4 <= blk.valid_w_bytes)
+                   ? lzw_fp_sample(blk.src + (int64_t)y * blk.pitch, x, aligned) : 0u;
+    };
+    const int32_t n = blk.block_w_bytes * block_h;
+    return lzw_encode_stream(
+        ws, n, [=](int64_t base) { lzw_fetch_fp(ws, n, base, blk.block_w_bytes, sample, lane, nlanes); }, dst, cap, lane, nlanes);
 }
 
 }  // namespace msr

@@ -13,8 +13,8 @@ and ``_good.tiff`` (UInt16) as LZW GeoTIFFs with ``PREDICTOR=2`` and a nodata ta
   metadata (shape included) from the header alone — what a rank of a sharded run needs to read only its own rows.
   The blocks are decoded on the host (default) or, ``decoder="device"``, LZW files on the GPU (csrc/geotiff_codec.hip:
   LZW per block, then predictor, conversion and placement) with the same bits out.
-* write: single band, little-endian, LZW + horizontal predictor (or none / deflate), classic TIFF or BigTIFF chosen by
-  size, in blocks that are strips of whole rows (default) or, ``tile=(tile_h, tile_w)``, zero-padded tiles; with tiles,
+* write: single band, little-endian, LZW + horizontal predictor (or none / deflate; ``predictor=3``: the floating-point
+  predictor for float samples, fp_predictor_reference), classic TIFF or BigTIFF chosen by size, in blocks that are strips of whole rows (default) or, ``tile=(tile_h, tile_w)``, zero-padded tiles; with tiles,
   ``overviews=n`` adds n reduced-resolution levels as chained IFDs (GDAL's internal-overview layout), each the 2 x 2
   reduction ``overview_reference`` of the one before.  The blocks of either layout are differenced and encoded one by one
   on the host (default; _encode_block) or, ``encoder="device"``, band by band on the GPU (_encode_band_device:
@@ -348,13 +348,36 @@ def _rows_per_strip(rows: int, row_bytes: int) -> int:
     return max(1, min(rows, (1 << 16) // max(row_bytes, 1)))
 
 
+def fp_predictor_reference(block: np.ndarray) -> np.ndarray:
+    """The floating-point predictor (PREDICTOR=3, TIFF Technical Note 3) of the rows of ``block``, [h, w] little-endian
+    float32 or float64: the NumPy twin that DEFINES what write_geotiff(predictor=3) hands to the compressor and whose bytes the
+    device fetch (csrc/lzw_strip.h lzw_fetch_fp) reproduces.  Returns [h, w * itemsize] uint8.  Every row is regrouped into
+    ``itemsize`` planes, the most significant byte of every sample first — byte ``p * w + x`` is byte ``itemsize - 1 - p`` of
+    sample x — and then every byte but the row's first becomes ``t[q] - t[q - 1]`` modulo 256, over the whole regrouped row and
+    so across the plane boundaries (libtiff's fpDiff with stride 1).  It is the inverse of what read_geotiff undoes for
+    predictor 3."""
+    a = np.asarray(block)
+    if a.ndim != 2 or a.dtype.kind != "f" or a.dtype.itemsize not in (4, 8):
+        raise ValueError(f"fp_predictor_reference takes a 2-D float32 or float64 array, got {a.dtype} {a.shape}")
+    h, w = a.shape
+    size = a.dtype.itemsize
+    raw = np.ascontiguousarray(a, dtype=a.dtype.newbyteorder("<")).view(np.uint8).reshape(h, w, size)
+    t = np.ascontiguousarray(raw[:, :, ::-1].transpose(0, 2, 1)).reshape(h, size * w)
+    out = t.copy()
+    out[:, 1:] = t[:, 1:] - t[:, :-1]
+    return out
+
+
 def _encode_block(blk: np.ndarray, dt: np.dtype, comp: int, predictor: int) -> bytes:
     """One block of a file — a strip, or a tile padded to its full size — encoded on the host: the horizontal predictor
-    differences every row of it in NumPy, then msr_lzw_encode / zlib / nothing."""
+    differences every row of it in NumPy (the floating-point predictor: fp_predictor_reference), then msr_lzw_encode / zlib /
+    nothing."""
     if predictor == 2:
         u = blk.view(np.dtype(f"<u{dt.itemsize}"))
         blk = u.copy()
         blk[:, 1:] = u[:, 1:] - u[:, :-1]
+    elif predictor == 3:
+        blk = fp_predictor_reference(blk)
     raw = np.ascontiguousarray(blk)
     return raw.tobytes() if comp == 1 else lzw_encode(raw) if comp == 5 else zlib.compress(raw.tobytes(), 6)
 
@@ -419,14 +442,21 @@ def _launch_blocks(who: str, buf, arrays, slots, limit: int, errors, stream, ent
     return dst, dst_off, dst_len[:n]
 
 
-def _encode_strips_device(buf, offsets, lengths, sample_bytes: int, row_bytes: int, stream=None):
+def _encode_strips_device(buf, offsets, lengths, sample_bytes: int, row_bytes: int, stream=None, predictor: Optional[int] = None):
     """One msr_lzw_encode_strips launch on ``buf``'s device: (dst, dst_off, dst_len) with dst / dst_len device tensors (the
     slots of capacity n + n // 2 + 1024 at dst_off, a host int64 array; dst_len int32, -1 = the slot was too small).
-    Asynchronous on ``stream`` (default: the current stream); the tensors it returns keep the inputs of the launch alive."""
+    Asynchronous on ``stream`` (default: the current stream); the tensors it returns keep the inputs of the launch alive.
+    ``predictor`` 1 / 2 / 3: msr_tiff_encode_strips with that predictor instead, ``sample_bytes`` the samples' width."""
+    if predictor is None:
+        entry = "msr_lzw_encode_strips"
+        call = lambda lib, head, tail: lib.msr_lzw_encode_strips(*head, int(sample_bytes), int(row_bytes), *tail)
+    else:
+        entry = "msr_tiff_encode_strips"
+        call = lambda lib, head, tail: lib.msr_tiff_encode_strips(*head, int(sample_bytes), int(predictor), int(row_bytes), *tail)
     return _launch_blocks(
         "lzw_encode_device", buf, (offsets, lengths), lambda ln: (ln + ln // 2 + 1024,) * 2, 1 << 30,
         ("offsets and lengths differ in length", "a strip lies outside the buffer (or is longer than 2^30 bytes)"), stream,
-        "msr_lzw_encode_strips", lambda lib, head, tail: lib.msr_lzw_encode_strips(*head, int(sample_bytes), int(row_bytes), *tail))
+        entry, call)
 
 
 def _download_strips(dst, dst_off: np.ndarray, dst_len) -> list:
@@ -442,13 +472,16 @@ def _download_strips(dst, dst_off: np.ndarray, dst_len) -> list:
     return [packed[e - l:e] for e, l in zip(ends, lens.tolist())]
 
 
-def lzw_encode_device(buf, offsets, lengths, sample_bytes: int = 0, row_bytes: int = 0, stream=None) -> list:
+def lzw_encode_device(buf, offsets, lengths, sample_bytes: int = 0, row_bytes: int = 0, stream=None,
+                      predictor: Optional[int] = None) -> list:
     """TIFF LZW streams of the strips ``buf[offsets[i] : offsets[i] + lengths[i]]`` of a uint8 CUDA tensor, encoded on its
     device in one launch (msr_lzw_encode_strips): byte for byte ``lzw_encode`` of the same bytes.  ``sample_bytes`` 1 / 2 / 4
     applies the horizontal predictor on the fly to little-endian samples of that width, restarting every ``row_bytes``.
+    ``predictor`` 1 / 2 / 3 (default None: the above) names the TIFF predictor instead, with ``sample_bytes`` the samples'
+    width (msr_tiff_encode_strips): 3 is the floating-point predictor of float32 rows, ``fp_predictor_reference``.
     ValueError if a stream does not fit its slot of n + n // 2 + 1024 bytes (the host wrapper's rule)."""
     import torch
-    dst, dst_off, dst_len = _encode_strips_device(buf, offsets, lengths, sample_bytes, row_bytes, stream)
+    dst, dst_off, dst_len = _encode_strips_device(buf, offsets, lengths, sample_bytes, row_bytes, stream, predictor)
     if stream is not None:
         torch.cuda.current_stream(buf.device).wait_stream(stream)
     return _download_strips(dst, dst_off, dst_len)
@@ -581,12 +614,19 @@ def _band_bytes_on_device(data, r0: int, r1: int, dt: np.dtype, dev):
     return out.view(torch.uint8).reshape(-1)
 
 
+def _device_predictor(sb: int, predictor: int) -> Tuple[int, Optional[int]]:
+    """(sample_bytes, predictor) as the device encoders take them, for a file's sample width and predictor in force: predictors
+    1 and 2 go through the entries that know the horizontal predictor alone (sample_bytes 0: none), 3 through msr_tiff_encode_*."""
+    return (sb, 3) if predictor == 3 else (sb if predictor == 2 else 0, None)
+
+
 def _encode_band_device(blocks, offsets, lengths, sample_bytes: int, row_bytes: int, transfers: Optional[list], kind: str,
-                        raw: Optional[int]) -> list:
+                        raw: Optional[int], predictor: Optional[int] = None) -> list:
     """The last steps of a band of the device encoder, strips or tiles (``kind``: "strip" / "tile"): ``blocks``, the band laid
-    out block after block as a uint8 device tensor, goes through one launch, compaction and download (lzw_encode_device), and
-    ``transfers`` takes the band's entries; ``raw``: the bytes of the band where it was uploaded from the host, else None."""
-    enc = lzw_encode_device(blocks, offsets, lengths, sample_bytes, row_bytes)
+    out block after block as a uint8 device tensor, goes through one launch, compaction and download (lzw_encode_device, which
+    ``sample_bytes`` and ``predictor`` go to: _device_predictor), and ``transfers`` takes the band's entries; ``raw``: the bytes
+    of the band where it was uploaded from the host, else None."""
+    enc = lzw_encode_device(blocks, offsets, lengths, sample_bytes, row_bytes, predictor=predictor)
     if transfers is not None:
         if raw is not None:
             transfers.append(("h2d", raw, "raw product band"))
@@ -604,14 +644,15 @@ def _device_strips(data, dt: np.dtype, rps: int, predictor: int, device, band_by
     rows, cols = data.shape
     row_bytes = cols * dt.itemsize
     dev = _torch_device(device, data=data)
+    psb, pred = _device_predictor(dt.itemsize, predictor)
     strips = []
     for s0, s1 in plan_bands(rows, row_bytes, rps, band_bytes):
         r0, r1 = s0 * rps, min(s1 * rps, rows)
         buf = _band_bytes_on_device(data, r0, r1, dt, dev)
         starts = np.arange(r0, r1, rps, dtype=np.int64)
         lengths = (np.minimum(starts + rps, r1) - starts) * row_bytes
-        strips += _encode_band_device(buf, (starts - r0) * row_bytes, lengths, dt.itemsize if predictor == 2 else 0, row_bytes,
-                                      transfers, "strip", buf.numel() if isinstance(data, np.ndarray) else None)
+        strips += _encode_band_device(buf, (starts - r0) * row_bytes, lengths, psb, row_bytes, transfers, "strip",
+                                      buf.numel() if isinstance(data, np.ndarray) else None, pred)
     return strips
 
 
@@ -625,8 +666,12 @@ def _checked_format(dtype, compress: str, predictor: int, encoder: str):
     if dt.kind not in "uif" or dt.itemsize not in (1, 2, 4, 8):
         raise ValueError(f"unsupported dtype {dtype}")
     comp = {"none": 1, "lzw": 5, "deflate": 8}[compress]
+    if predictor == 3 and dt.kind != "f":
+        raise ValueError(f"predictor 3 is the floating-point predictor: it is not defined for dtype {dt.name}")
     if comp == 1 or dt.itemsize == 8 and predictor == 2:
         predictor = 1
+    if encoder == "device" and predictor == 3 and dt.itemsize != 4:
+        raise ValueError(f"encoder='device' applies predictor 3 to float32 only, got dtype {dt.name}; encoder='host' does")
     return dt, comp, predictor
 
 
@@ -774,6 +819,7 @@ def _device_levels(data, dt: np.dtype, tile: Tuple[int, int], overviews: int, no
     th, tw = tile
     sb = dt.itemsize
     bits = getattr(torch, _TORCH_BITS[sb])           # the container of a sample's bits: they are only copied here
+    psb, pred = _device_predictor(sb, predictor)
     has_nodata = int(dt.kind == "f" and nodata is not None)
     levels = []
     cur = data
@@ -803,20 +849,20 @@ def _device_levels(data, dt: np.dtype, tile: Tuple[int, int], overviews: int, no
                 tiles = band.view(nt, th, across, tw).permute(0, 2, 1, 3).contiguous().view(torch.uint8).reshape(-1)
                 lengths = np.full(nt * across, th * tw * sb, np.int64)
                 raw = (r1 - r0) * cols * sb if k == 0 and isinstance(data, np.ndarray) else None
-                blocks += _encode_band_device(tiles, np.cumsum(lengths) - lengths, lengths, sb if predictor == 2 else 0, tw * sb,
-                                              transfers, "tile", raw)
+                blocks += _encode_band_device(tiles, np.cumsum(lengths) - lengths, lengths, psb, tw * sb, transfers, "tile", raw, pred)
             levels.append((rows, cols, blocks))
             cur = nxt
     return levels
 
 
 def _encode_blocks_device(buf, offsets, pitches, valid_w_bytes, valid_rows, block_w_bytes: int, block_h: int, sample_bytes: int,
-                          stream=None):
+                          stream=None, predictor: Optional[int] = None):
     """One msr_lzw_encode_blocks launch on ``buf``'s device: block i is ``block_h`` rows of ``block_w_bytes`` bytes whose valid
     part, ``valid_rows[i]`` rows of ``valid_w_bytes[i]`` bytes, lies at ``buf[offsets[i]]`` with ``pitches[i]`` bytes between rows
     and is read there; the rest of the block is zero.  What _launch_blocks checks for lengths is checked here for the valid parts:
     one entry per block in every array, each valid part inside its block and every byte of it inside ``buf``.  Returns (dst,
-    dst_off, dst_len) as _encode_strips_device does, the slots n + n // 2 + 1024 bytes for the n bytes of a block."""
+    dst_off, dst_len) as _encode_strips_device does, the slots n + n // 2 + 1024 bytes for the n bytes of a block.
+    ``predictor`` 1 / 2 / 3: msr_tiff_encode_blocks with that predictor instead, ``sample_bytes`` the samples' width."""
     import torch
     lib = _lib.load()
     if not (isinstance(buf, torch.Tensor) and buf.is_cuda and buf.dtype == torch.uint8 and buf.is_contiguous()):
@@ -846,23 +892,28 @@ def _encode_blocks_device(buf, offsets, pitches, valid_w_bytes, valid_rows, bloc
             dst = torch.empty(int(cap.sum()), dtype=torch.uint8, device=dev)
             dst_len = torch.full((n,), -1, dtype=torch.int32, device=dev)
             p64, p32 = table.data_ptr(), table32.data_ptr()
-            rc = lib.msr_lzw_encode_blocks(None, buf.data_ptr(), p64, p64 + 8 * n, p32, p32 + 4 * n, n, bw, bh, int(sample_bytes),
-                                           dst.data_ptr(), p64 + 16 * n, p32 + 8 * n, dst_len.data_ptr(), C.c_void_p(s.cuda_stream))
-            _lib.raise_for(lib, None, rc, "msr_lzw_encode_blocks")
+            head = (None, buf.data_ptr(), p64, p64 + 8 * n, p32, p32 + 4 * n, n, bw, bh, int(sample_bytes))
+            tail = (dst.data_ptr(), p64 + 16 * n, p32 + 8 * n, dst_len.data_ptr(), C.c_void_p(s.cuda_stream))
+            if predictor is None:
+                _lib.raise_for(lib, None, lib.msr_lzw_encode_blocks(*head, *tail), "msr_lzw_encode_blocks")
+            else:
+                _lib.raise_for(lib, None, lib.msr_tiff_encode_blocks(*head, int(predictor), *tail), "msr_tiff_encode_blocks")
             for t in (buf, table, table32):
                 t.record_stream(s)
     return dst, dst_off, dst_len[:n]
 
 
 def lzw_encode_blocks_device(buf, offsets, pitches, valid_w_bytes, valid_rows, block_w_bytes: int, block_h: int,
-                             sample_bytes: int = 0, stream=None) -> list:
+                             sample_bytes: int = 0, stream=None, predictor: Optional[int] = None) -> list:
     """TIFF LZW streams of blocks (tiles) of ``block_h`` rows of ``block_w_bytes`` bytes read in place from the uint8 CUDA tensor
     ``buf``, encoded on its device in one launch (msr_lzw_encode_blocks; the arguments: _encode_blocks_device): byte for byte
     ``lzw_encode`` of each block padded with zero bytes and, with ``sample_bytes`` 1 / 2 / 4, differenced along its rows
-    afterwards.  The pitch is per block, so blocks of several rasters in ``buf`` share the launch."""
+    afterwards.  The pitch is per block, so blocks of several rasters in ``buf`` share the launch.  ``predictor`` 1 / 2 / 3
+    (default None: the above): lzw_encode_device's, through msr_tiff_encode_blocks; 3 is ``fp_predictor_reference`` of the
+    padded float32 block."""
     import torch
     dst, dst_off, dst_len = _encode_blocks_device(buf, offsets, pitches, valid_w_bytes, valid_rows, block_w_bytes, block_h,
-                                                  sample_bytes, stream)
+                                                  sample_bytes, stream, predictor)
     if stream is not None:
         torch.cuda.current_stream(buf.device).wait_stream(stream)
     return _download_strips(dst, dst_off, dst_len)
@@ -893,7 +944,7 @@ def _device_levels_in_place(data, dt: np.dtype, tile: Tuple[int, int], overviews
     dev = _torch_device(device, data=data)
     th, tw = tile
     sb = dt.itemsize
-    psb = sb if predictor == 2 else 0
+    psb, pred = _device_predictor(sb, predictor)
     has_nodata = int(dt.kind == "f" and nodata is not None)
     shapes = [(int(data.shape[0]), int(data.shape[1]))]
     for _ in range(overviews):
@@ -902,7 +953,7 @@ def _device_levels_in_place(data, dt: np.dtype, tile: Tuple[int, int], overviews
     bases = [int(b) for b in np.cumsum([0] + sizes[:-1])] if sizes else []
 
     def encode(buf, table, raw):
-        enc = _download_strips(*_encode_blocks_device(buf, *table, tw * sb, th, psb))
+        enc = _download_strips(*_encode_blocks_device(buf, *table, tw * sb, th, psb, predictor=pred))
         if transfers is not None:
             if raw is not None:
                 transfers.append(("h2d", raw, "raw product band"))
@@ -953,6 +1004,12 @@ def write_geotiff(path: str, data: np.ndarray, meta: Optional[dict] = None, noda
     to ``dtype`` on the device), ``device`` the HIP device (default: the tensor's, else the current one), and the raster
     goes through the device in bands of whole strips of at most ``band_bytes`` raw bytes.  LZW only; no CPU fallback.
     ``transfers``: encode_strips'.
+
+    ``predictor=3`` (float32 or float64 data; ValueError for an integer ``dtype``) is the floating-point predictor of TIFF
+    Technical Note 3, GDAL's PREDICTOR=3: every row of a strip or padded tile goes through ``fp_predictor_reference`` in place of
+    the horizontal differencing, in every layout below, and every IFD carries Predictor = 3.  Both encoders write the same
+    bytes; the device encoder takes float32 only (msr_tiff_encode_strips / msr_tiff_encode_blocks).  ``read_geotiff`` reads
+    these files with ``decoder="host"``; its ``decoder="device"`` refuses predictor 3.  ``compress="none"`` forces predictor 1.
 
     ``tile=(tile_h, tile_w)`` (positive multiples of 16) writes tiles in row-major order instead of strips: TileWidth /
     TileLength / TileOffsets / TileByteCounts and no strip tag; an edge tile is padded with zero bytes before the predictor,

@@ -82,7 +82,7 @@ class HaloShardedSuperResolution(DEMSuperResolution):
     """DEMSuperResolution with the halo mode added: ``processMapHalo(rank, world)``.
 
     ``resident`` is accepted and must be False: the halo mode's inputs and its default products still end on the host.
-    ``product_tile``, ``overviews`` and ``product_layout`` are DEMSuperResolution's, checked there.
+    ``product_tile``, ``overviews``, ``product_layout`` and ``product_predictor`` are DEMSuperResolution's, checked there.
 
     ``processFiles(mode="halo", rank=, world=)`` is the driver on files (DEMSuperResolution.processFiles; ``batching`` and
     ``accumulate`` go to processMapHalo).  With the default ``products="gathered"`` every rank all-gathers the three slabs,

@@ -116,6 +116,10 @@ class DEMSuperResolution:
             ``layout``: the same tiles, levels and tags in the order of a cloud-optimised GeoTIFF, the IFDs first and the
             coarse levels before the fine ones; with ``encoder="device"`` the tiles are encoded where their level lies, those
             of all reduced levels in one launch.
+        product_predictor: 2 (default: the horizontal predictor saveGTiff asks GDAL for) or 3 — the floating-point predictor
+            (GDAL's PREDICTOR=3; geotiff.fp_predictor_reference) for the float32 products ``mean`` and ``std``, with every
+            encoder, layout and writer; ``good`` (uint16) keeps predictor 2.  The rasters read back are the same bit for bit
+            (geotiff.read_geotiff with ``decoder="host"``); any other value is a ValueError.
 
     ``transfers`` is a diagnostic: a list of ``(direction, bytes, what)``, direction "h2d" or "d2h", to which the driver,
     preprocess.py and geotiff.py append every raster-scale copy they issue themselves (and the per-block bookkeeping of the
@@ -126,10 +130,14 @@ class DEMSuperResolution:
     def __init__(self, config: DSRConfig, model: Callable = lambda x, training=False: x, device: int = 0,
                  as_implemented: bool = True, pipeline: int = 2, range_check: str = "off", encoder: str = "host",
                  decoder: str = "host", infill: str = "host", resident: bool = False,
-                 product_tile: Optional[Tuple[int, int]] = None, overviews: int = 0, product_layout: str = "plain") -> None:
+                 product_tile: Optional[Tuple[int, int]] = None, overviews: int = 0, product_layout: str = "plain",
+                 product_predictor: int = 2) -> None:
         from . import geotiff
         self.product_tile, self.overviews = geotiff.check_layout(product_tile, overviews)   # saveGTiff: the products' layout
         self.product_layout = geotiff.check_file_order(product_layout, self.product_tile)
+        if isinstance(product_predictor, bool) or product_predictor not in (2, 3):
+            raise ValueError(f"product_predictor must be 2 or 3, got {product_predictor!r}")
+        self.product_predictor = int(product_predictor)   # saveGTiff: the predictor of the float32 products
         if not isinstance(resident, bool):
             raise ValueError(f"resident must be a bool, got {resident!r}")
         self.resident = resident                     # where the rasters are held between the stages: HBM, or host memory
@@ -314,9 +322,14 @@ class DEMSuperResolution:
         elif len(data.shape) != 2:
             raise ValueError("Data is of incorrect shape")
         geotiff.write_geotiff(self._product_path(name), data, getattr(self, "geo_meta", None), nodata=self.no_value,
-                              dtype=out_type, compress="lzw", predictor=2, encoder=self.encoder, device=self.device,
+                              dtype=out_type, compress="lzw", predictor=self._predictor(out_type), encoder=self.encoder,
+                              device=self.device,
                               transfers=self.transfers, tile=self.product_tile, overviews=self.overviews,
                               layout=self.product_layout)
+
+    def _predictor(self, dtype) -> int:
+        """The predictor of a product file of ``dtype``: ``product_predictor`` for float32, 2 for the integer ``good``."""
+        return self.product_predictor if np.dtype(dtype).kind == "f" else 2
 
     def _product_path(self, name: str) -> str:
         """``<save_path>/<map_name>_<name>.tiff``, its directory made."""
@@ -507,8 +520,8 @@ class DEMSuperResolution:
         if self.encoder == "host" and data.numel():
             self._log("d2h", data.numel() * data.element_size(), f"{name} product rows")
             data = data.cpu().numpy()
-        strips = geotiff.encode_strips(data, dt, plan["rps"], encoder=self.encoder, device=self.device,
-                                       transfers=self.transfers) if data.shape[0] else []
+        strips = geotiff.encode_strips(data, dt, plan["rps"], predictor=self._predictor(dt), encoder=self.encoder,
+                                       device=self.device, transfers=self.transfers) if data.shape[0] else []
         assert len(strips) == s1 - s0, (name, rank, len(strips), (s0, s1))
         if world > 1:
             import torch.distributed as dist
@@ -519,7 +532,7 @@ class DEMSuperResolution:
         if rank == 0:
             assert len(strips) == plan["n_strips"], (len(strips), plan["n_strips"])
             geotiff.write_strips(self._product_path(name), strips, shape, dt, plan["rps"], getattr(self, "geo_meta", None),
-                                 nodata=self.no_value)
+                                 nodata=self.no_value, predictor=self._predictor(dt))
 
     def padInputs(self) -> None:
         """process_full_tiles.py:246-267: no_value canvas ((dim//1024)+1)*1024 + 2(S-s), data at offset (S-s).
