@@ -749,6 +749,29 @@ int msr_range_embed_bounds(msr_handle* h, msr_range_stat* out, int32_t cap, int3
  * or a multiple of 256.  Fills *out_stat (tensor empty, producer -1).  Bad arguments: MSR_ERR_INVALID before any allocation. */
 int msr_op_range_scan(msr_handle* h, const void* img_dev, int32_t format, int32_t B, int32_t r, int32_t C, int32_t padded,
                       msr_range_stat* out_stat, void* stream);
+/* ---- dirty-workspace test aids --------------------------------------------------------------------- */
+/* Debug, read-only; builds the plan if the handle has none.  One line of "key=value" words per device buffer of the handle:
+ *   name     the key msr_debug_tensor knows, or scratch.mom_partial | scratch.dense_partial | scratch.conv_partial |
+ *            scratch.stat_ws (the raw scratch buffers that exist), or table.range_items | table.range_records |
+ *            table.blend_window | table.stitch_grid
+ *   kind     ws (activations, moments: keys that begin with "ws.") | scratch | weight (every other key: weight images, .wexp,
+ *            folded scales) | table
+ *   bytes    the size   zeroed  1 if the buffer was zero-filled when allocated   counted  1 if bytes is part of msr_device_bytes
+ *            (the lines with counted=1 add up to it)
+ *   r C written   zero-bordered buffers [B, r + 2, r + 2, C] only: the float slots per pixel their producer writes; the slots
+ *            beyond `written` and the border stay zero and the consumer may read them.
+ * NUL-terminated; MSR_ERR_INVALID when cap is too small (64 KB is enough) or an argument is null. */
+int msr_debug_workspace_list(msr_handle* h, char* out, int64_t cap);
+/* Debug: synchronises the device, then sets every byte of the chosen parts of the workspace to `byte` (0..255) with hipMemset /
+ * hipMemset2D and synchronises again; *bytes_filled = the bytes written.  `what` is a sum of
+ *   1  every kind=ws buffer with zeroed=0 and every kind=scratch buffer, in full
+ *   2  the interior pixels of every zero-bordered buffer, slots 0 .. written - 1
+ *   4  the border of every zero-bordered buffer, every slot (to show that the convs read it, and to restore the zeros)
+ * It writes to nothing else: weights, .wexp, ws.zero_bias, the blend window, stitch_grid, the range-scan tables and whatever
+ * else holds a constant, an index or an offset keep their contents, so a kernel that reads a stale word computes a wrong number
+ * and never a wild address.  Captured graphs are kept.  A forward that follows must give the bits it gives on a fresh handle:
+ * its result is a function of its inputs and the weights only.  MSR_ERR_INVALID for a null argument or a bad what / byte. */
+int msr_debug_fill_workspace(msr_handle* h, int32_t what, int32_t byte, int64_t* bytes_filled);
 /* Bytes of device memory held by the handle (weights + workspace). */
 int msr_device_bytes(const msr_handle* h, int64_t* bytes);
 

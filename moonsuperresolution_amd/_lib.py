@@ -143,6 +143,8 @@ SYMBOLS = [
     ("msr_debug_conv_forms", C.c_int, [_P, _P, C.c_int64]),
     ("msr_debug_f16c_kernel", C.c_int, [C.c_int32, C.c_int32, C.c_int32]),
     ("msr_debug_form_table", C.c_int, [C.POINTER(MsrConfig), _P, C.c_int64]),
+    ("msr_debug_workspace_list", C.c_int, [_P, _P, C.c_int64]),
+    ("msr_debug_fill_workspace", C.c_int, [_P, C.c_int32, C.c_int32, C.POINTER(C.c_int64)]),
     ("msr_device_bytes", C.c_int, [_P, C.POINTER(C.c_int64)]),
     ("msr_range_scan", C.c_int, [_P, _P]),
     ("msr_range_read", C.c_int, [_P, C.POINTER(MsrRangeStat), C.c_int32, C.POINTER(C.c_int32)]),

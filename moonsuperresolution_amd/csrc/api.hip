@@ -51,6 +51,7 @@ int dev_alloc(msr_handle* h, const std::string& key, size_t floats, bool zero, f
     }
     h->dev[key] = p;
     h->dev_bytes[key] = floats * sizeof(float);
+    h->dev_zeroed[key] = zero;
     h->total_bytes += floats * sizeof(float);
     *out = p;
     return MSR_OK;

@@ -280,6 +280,106 @@ int msr_range_embed_bounds(msr_handle* h, msr_range_stat* out, int32_t cap, int3
     return MSR_OK;
 }
 
+int msr_debug_workspace_list(msr_handle* h, char* out, int64_t cap) {
+    if (!h || !out || cap < 1) return MSR_ERR_INVALID;
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    int rc = ensure_plan(h);
+    if (rc) return rc;
+    std::string txt;
+    char b[256];
+    auto line = [&](const std::string& name, const char* kind, size_t bytes, int zeroed, int counted) {
+        snprintf(b, sizeof b, "name=%s kind=%s bytes=%zu zeroed=%d counted=%d", name.c_str(), kind, bytes, zeroed, counted);
+        txt += b;
+    };
+    for (const auto& kv : h->dev) {
+        const bool ws = kv.first.compare(0, 3, "ws.") == 0;
+        const auto z = h->dev_zeroed.find(kv.first);
+        line(kv.first, ws ? "ws" : "weight", h->dev_bytes[kv.first], z != h->dev_zeroed.end() && z->second ? 1 : 0, 1);
+        const auto p = h->dev_padded.find(kv.first);
+        if (p != h->dev_padded.end()) {
+            snprintf(b, sizeof b, " r=%d C=%d written=%d", p->second.r, p->second.C, p->second.written);
+            txt += b;
+        }
+        txt += "\n";
+    }
+    if (h->mom_partial) { line("scratch.mom_partial", "scratch", h->mom_partial_bytes, 0, 1); txt += "\n"; }
+    if (h->dense_partial) { line("scratch.dense_partial", "scratch", h->dense_partial_bytes, 0, 1); txt += "\n"; }
+    if (h->conv_partial) { line("scratch.conv_partial", "scratch", h->conv_partial_floats * sizeof(float), 0, 1); txt += "\n"; }
+    if (h->stat_ws) { line("scratch.stat_ws", "scratch", h->stat_ws_floats * sizeof(float), 0, 1); txt += "\n"; }
+    // tables: indices, offsets and constants.  The tiler's two are not part of msr_device_bytes.
+    if (h->range_cap) {
+        line("table.range_items", "table", h->range_cap * sizeof(RangeScanItem), 0, 1); txt += "\n";
+        line("table.range_records", "table", h->range_cap * sizeof(RangeScanRecord), 0, 1); txt += "\n";
+    }
+    if (h->window) {
+        const size_t ws = (size_t)(h->S - 2 * (h->S / 16));
+        line("table.blend_window", "table", ws * ws * sizeof(double), 0, 0); txt += "\n";
+    }
+    if (h->stitch_grid) { line("table.stitch_grid", "table", (size_t)h->stitch_grid_cap * sizeof(int), 0, 0); txt += "\n"; }
+    if ((int64_t)txt.size() + 1 > cap) return fail(h, MSR_ERR_INVALID, "msr_debug_workspace_list: %zu bytes needed", txt.size() + 1);
+    memcpy(out, txt.c_str(), txt.size() + 1);
+    return MSR_OK;
+}
+
+int msr_debug_fill_workspace(msr_handle* h, int32_t what, int32_t byte, int64_t* bytes_filled) {
+    if (!h || !bytes_filled) return MSR_ERR_INVALID;
+    *bytes_filled = 0;
+    if (what < 1 || what > 7 || byte < 0 || byte > 255)
+        return fail(h, MSR_ERR_INVALID, "msr_debug_fill_workspace: what must be in 1..7 and byte in 0..255, got %d and %d", what, byte);
+    HIPCHK(h, hipSetDevice(h->cfg.device));
+    int rc = ensure_plan(h);                 // a planned handle returns at once: captured graphs stay
+    if (rc) return rc;
+    HIPCHK(h, hipDeviceSynchronize());
+    size_t total = 0;
+    // Only activations and partial sums are written here: the keys that begin with "ws." and the four scratch buffers.  Weights,
+    // .wexp, the folded scales, ws.zero_bias (zeroed, not padded), the blend window, stitch_grid and the range-scan tables hold
+    // constants, indices or offsets and are never touched, so that a stale read shows as a wrong number, never as an address.
+    if (what & 1) {
+        for (const auto& kv : h->dev) {
+            const auto z = h->dev_zeroed.find(kv.first);
+            if (kv.first.compare(0, 3, "ws.") != 0 || z == h->dev_zeroed.end() || z->second) continue;
+            const size_t n = h->dev_bytes[kv.first];
+            if (n) HIPCHK(h, hipMemset(kv.second, byte, n));
+            total += n;
+        }
+        const struct { void* p; size_t n; } scratch[] = {{h->mom_partial, h->mom_partial_bytes},
+                                                         {h->dense_partial, h->dense_partial_bytes},
+                                                         {h->conv_partial, h->conv_partial_floats * sizeof(float)},
+                                                         {h->stat_ws, h->stat_ws_floats * sizeof(float)}};
+        for (const auto& s : scratch)
+            if (s.p && s.n) { HIPCHK(h, hipMemset(s.p, byte, s.n)); total += s.n; }
+    }
+    for (const auto& kv : h->dev_padded) {
+        const auto it = h->dev.find(kv.first);
+        if (it == h->dev.end() || !(what & 6)) continue;
+        const size_t r = (size_t)kv.second.r, C = (size_t)kv.second.C, wr = (size_t)kv.second.written, F = sizeof(float);
+        const size_t py = (r + 2) * C, pb = (r + 2) * py;
+        if (h->dev_bytes[kv.first] != (size_t)h->B * pb * F)
+            return fail(h, MSR_ERR_STATE, "msr_debug_fill_workspace: %s is not [%d, %zu, %zu, %zu]", kv.first.c_str(), h->B, r + 2, r + 2, C);
+        for (int bi = 0; bi < h->B; ++bi) {
+            float* img = it->second + (size_t)bi * pb;
+            if (what & 2) {                  // interior pixels, the slots the producer writes
+                if (wr == C) {
+                    HIPCHK(h, hipMemset2D(img + py + C, py * F, byte, r * C * F, r));
+                } else {
+                    for (size_t y = 1; y <= r; ++y) HIPCHK(h, hipMemset2D(img + y * py + C, C * F, byte, wr * F, r));
+                }
+                total += r * r * wr * F;
+            }
+            if (what & 4) {                  // the border: rows 0 and r + 1, columns 0 and r + 1 of the rows between, every slot
+                HIPCHK(h, hipMemset(img, byte, py * F));
+                HIPCHK(h, hipMemset(img + (r + 1) * py, byte, py * F));
+                HIPCHK(h, hipMemset2D(img + py, py * F, byte, C * F, r));
+                HIPCHK(h, hipMemset2D(img + py + (r + 1) * C, py * F, byte, C * F, r));
+                total += (2 * py + 2 * r * C) * F;
+            }
+        }
+    }
+    HIPCHK(h, hipDeviceSynchronize());
+    *bytes_filled = (int64_t)total;
+    return MSR_OK;
+}
+
 int msr_device_bytes(const msr_handle* h, int64_t* bytes) {
     if (!h || !bytes) return MSR_ERR_INVALID;
     *bytes = (int64_t)h->total_bytes;

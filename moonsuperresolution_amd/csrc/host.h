@@ -131,6 +131,9 @@ struct msr_handle {
     std::map<std::string, int> spec_index;
     std::map<std::string, float*> dev;          // device tensors: weights (re-laid-out) and workspace
     std::map<std::string, size_t> dev_bytes;
+    std::map<std::string, bool> dev_zeroed;      // dev_alloc zero-filled the buffer (msr_debug_workspace_list)
+    struct PaddedInfo { int r, C, written; };    // alloc_padded: [B, r + 2, r + 2, C], the producer writes `written` slots per pixel
+    std::map<std::string, PaddedInfo> dev_padded;
     std::map<std::string, int> dev_img;          // WeightImage of every conv weight uploaded by upload_conv_weight
     std::map<std::string, std::vector<float>> host_small;   // small host copies needed at plan time (BN, head)
     size_t total_bytes = 0;
@@ -139,6 +142,7 @@ struct msr_handle {
     double fwd_flops = 0;
     double* mom_partial = nullptr;
     float* dense_partial = nullptr;
+    size_t mom_partial_bytes = 0, dense_partial_bytes = 0;   // as counted in total_bytes
     float* conv_partial = nullptr;     // split-K workspace [ksplit][M][N]
     size_t conv_partial_floats = 0;
     float* stat_ws = nullptr;          // fused-moments slabs [P][3][N] of the conv that ran last

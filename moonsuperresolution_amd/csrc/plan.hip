@@ -5,8 +5,11 @@
 
 namespace msr {
 
-static int alloc_padded(msr_handle* h, const std::string& key, int r, int C, Padded* out) {
+// `written`: the float slots per pixel the buffer's producer writes (-1: all C).  The rest stays zero from here on, and the
+// consumer may read it (msr_debug_fill_workspace keeps out of it).
+static int alloc_padded(msr_handle* h, const std::string& key, int r, int C, Padded* out, int written = -1) {
     out->r = r; out->C = C;
+    h->dev_padded[key] = {r, C, written < 0 ? C : written};
     return dev_alloc(h, key, (size_t)h->B * (r + 2) * (r + 2) * C, true, &out->base);
 }
 
@@ -138,7 +141,7 @@ static int plan_spade(msr_handle* h) {
         const int r = sw << (i - 1);
         const int shift = i > 1 ? 1 : 0;   // block input = UpSampling2D(previous output), folded into the index
         const bool learned = f != cin;
-        float *x1, *skip = nullptr, *outb, *m1, *s1, *mo, *so;
+        float *x1, *skip = nullptr, *outb, *m1, *s1, *mo = nullptr, *so = nullptr;
         snprintf(n, sizeof n, "ws.gen.rb%d.x1", i); rc = dev_alloc(h, n, (size_t)B * r * r * f, false, &x1); if (rc) return rc;
         // fused head: the last block's output exists only as the head's partial sums (32 floats per pixel instead of 128)
         const bool to_head = i == 6 && head_fused_form(h);
@@ -146,8 +149,10 @@ static int plan_spade(msr_handle* h) {
         else { snprintf(n, sizeof n, "ws.gen.rb%d.out", i); rc = dev_alloc(h, n, (size_t)B * r * r * f, false, &outb); if (rc) return rc; }
         snprintf(n, sizeof n, "ws.gen.rb%d.mean1", i); rc = dev_alloc(h, n, f, false, &m1); if (rc) return rc;
         snprintf(n, sizeof n, "ws.gen.rb%d.std1", i); rc = dev_alloc(h, n, f, false, &s1); if (rc) return rc;
-        snprintf(n, sizeof n, "ws.gen.rb%d.meano", i); rc = dev_alloc(h, n, f, false, &mo); if (rc) return rc;
-        snprintf(n, sizeof n, "ws.gen.rb%d.stdo", i); rc = dev_alloc(h, n, f, false, &so); if (rc) return rc;
+        if (!to_head) {   // under the fused head nothing computes or reads the last block's output moments: no buffer either
+            snprintf(n, sizeof n, "ws.gen.rb%d.meano", i); rc = dev_alloc(h, n, f, false, &mo); if (rc) return rc;
+            snprintf(n, sizeof n, "ws.gen.rb%d.stdo", i); rc = dev_alloc(h, n, f, false, &so); if (rc) return rc;
+        }
         if (learned) { snprintf(n, sizeof n, "ws.gen.rb%d.skip", i); rc = dev_alloc(h, n, (size_t)B * r * r * f, false, &skip); if (rc) return rc; }
 
         // one SPADE layer + its consumer conv:  a = lrelu(SPADE(x)) ; y = conv_j(a), both in the forms of the handle's table
@@ -162,7 +167,9 @@ static int plan_spade(msr_handle* h) {
             };
             Padded hb, ab;
             int rc2;
-            snprintf(k, sizeof k, "ws.gen.rb%d.a%d", i, j); rc2 = alloc_padded(h, k, r, sf.aslots, &ab); if (rc2) return rc2;
+            snprintf(k, sizeof k, "ws.gen.rb%d.a%d", i, j);
+            // bf8 bytes: one per channel, in slots of four; aslots pads them to the fp8 conv's K
+            rc2 = alloc_padded(h, k, r, sf.aslots, &ab, sf.a_split == OUT_BF8 ? C / 4 : sf.aslots); if (rc2) return rc2;
             if (sf.ranges > 0) {
                 // conv_gb_resident: the embedding never exists in HBM (no mask-embedding launch, no h buffer); one launch
                 // does resize + embedding + gamma|beta conv + SPADE epilogue and writes the consumer's f16c image
@@ -183,7 +190,8 @@ static int plan_spade(msr_handle* h) {
                 g.flops = 2.0 * B * r * r * 128.0 * (2 * C) * 9 + 2.0 * B * r * r * 18.0 * 128;
                 h->ops.push_back(g);
             } else {
-                snprintf(k, sizeof k, "ws.gen.rb%d.h%d", i, j); rc2 = alloc_padded(h, k, r, sf.hslots, &hb); if (rc2) return rc2;
+                snprintf(k, sizeof k, "ws.gen.rb%d.h%d", i, j);
+                rc2 = alloc_padded(h, k, r, sf.hslots, &hb, sf.h_split == OUT_BF8 ? 128 / 4 : sf.hslots); if (rc2) return rc2;
                 Op em; em.type = OP_SMALLCIN; em.src_is_input = true;
                 SmallCinParams& p = em.sc;
                 snprintf(k, sizeof k, "gen.rb%d.spade_%d.conv.kernel", i, j); p.w = need(k);
@@ -289,7 +297,9 @@ static int plan_spade(msr_handle* h) {
     mom_doubles = std::max<size_t>(mom_doubles, (size_t)128 * 3 * 1024);  // also the slab-group scratch
     HIPCHK(h, hipMalloc(&h->mom_partial, std::max<size_t>(mom_doubles, 16) * sizeof(double)));
     HIPCHK(h, hipMalloc(&h->dense_partial, std::max<size_t>(dense_part, 16) * sizeof(float)));
-    h->total_bytes += mom_doubles * sizeof(double) + dense_part * sizeof(float);
+    h->mom_partial_bytes = mom_doubles * sizeof(double);
+    h->dense_partial_bytes = dense_part * sizeof(float);
+    h->total_bytes += h->mom_partial_bytes + h->dense_partial_bytes;
     return MSR_OK;
 }
 
@@ -479,6 +489,8 @@ int ensure_plan(msr_handle* h) {
     }
     if (h->mom_partial) { hipFree(h->mom_partial); h->mom_partial = nullptr; }
     if (h->dense_partial) { hipFree(h->dense_partial); h->dense_partial = nullptr; }
+    h->total_bytes -= h->mom_partial_bytes + h->dense_partial_bytes;     // a re-plan allocates and counts them again
+    h->mom_partial_bytes = h->dense_partial_bytes = 0;
     int rc = h->variant == MSR_PIX2PIX ? plan_pix2pix(h) : plan_spade(h);
     if (rc) return rc;
     h->fwd_flops = 0;

@@ -46,6 +46,10 @@ def form_table(image_size: int, batch_size: int, variant: str = "gaugan", flags:
 
 F16_MAX = 65504.0
 
+# msr_debug_fill_workspace `what`: the un-zeroed ws.* buffers and the scratch buffers; the interior of the zero-bordered
+# buffers (the slots their producers write); their borders
+FILL_WORKSPACE, FILL_INTERIOR, FILL_BORDER = 1, 2, 4
+
 
 class RangeReport:
     """Result of an activation-range scan (msr_range_scan): ``records`` — one dict per narrow activation tensor of the plan, in
@@ -393,6 +397,23 @@ class Generator:
         """Whether the plan took ``head="fused"``: it holds the gather op (the separate head runs at shapes where the last
         residual conv does not run the stream kernel on whole tiles)."""
         return any(op.get("kind") == "head_gather" for op in self.conv_forms())
+
+    # -- dirty-workspace test aids -------------------------------------------------------------------
+    def workspace_list(self) -> list:
+        """One dict per device buffer of the planned handle (msr_debug_workspace_list): name, kind (ws | scratch | weight |
+        table), bytes, zeroed, counted, and r, C, written for the zero-bordered buffers."""
+        buf = C.create_string_buffer(1 << 17)
+        rc = self._lib.msr_debug_workspace_list(self._h, buf, len(buf))
+        _lib.raise_for(self._lib, self._h, rc, "msr_debug_workspace_list")
+        return parse_conv_forms(buf.value.decode())
+
+    def fill_workspace(self, what: int, byte: int) -> int:
+        """Set every byte of the chosen parts of the workspace to ``byte`` (msr_debug_fill_workspace; ``what``: FILL_WORKSPACE |
+        FILL_INTERIOR | FILL_BORDER) and return the number of bytes written.  Synchronises the device."""
+        n = C.c_int64()
+        rc = self._lib.msr_debug_fill_workspace(self._h, int(what), int(byte), C.byref(n))
+        _lib.raise_for(self._lib, self._h, rc, "msr_debug_fill_workspace")
+        return n.value
 
     # -- activation ranges -----------------------------------------------------------------------------
     def range_scan_async(self) -> None:
